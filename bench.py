@@ -2,21 +2,28 @@
 
 One "step" = one tick (collide -> QuickStep -> clear contacts, main.c:211-215) over the whole batch of synthetic bodies.
 
-N = 1   BASELINE.json configs[1]: 1 048 576 free-falling boxes, no contacts, dt = 1/60, f32; the same scene in f64
-        (`f64`), an HBM-resident size (`hbm_resident`: 16 Mi bodies, far beyond the 256 MB Infinity Cache) and several ticks
-        per launch (`fused`) ride along as extra objects of the one JSON line.
+N = 1   BASELINE.json configs[1]: 1 048 576 free-falling boxes, no contacts, dt = 1/60, f32.  With --full, the same scene
+        in f64 (`f64`), an HBM-resident size (`hbm_resident`: 16 Mi bodies, far beyond the 256 MB Infinity Cache), several
+        ticks per launch (`fused`), the other configs (`configs`), the reference's pen and call (`reference_pen`,
+        `reference_main_c`) and the CPU baselines ride along as extra objects of the one JSON line.
 N > 1   BASELINE.json configs[3] as written: the SAME 1 048 576 bodies, in N disjoint slabs >= 10 m apart, one slab of
-        1 048 576 / N bodies per GPU (strong scaling), the slabs' boundary rows all-gathered over RCCL / xGMI.  The weak-scaled
-        run (one whole configs[1] slab per GPU) is the extra object `weak`.
+        1 048 576 / N bodies per GPU (strong scaling), the slabs' boundary rows all-gathered over RCCL / xGMI.  With --full,
+        the weak-scaled run (one whole configs[1] slab per GPU) is the extra object `weak`.
+
+A plain run (no --full) sets up, warms up, times the headline's --steps ticks and prints the line: nothing else.
+--dump-outputs DIR then writes the state the headline's last timed tick left (pos, quat, lvel, avel of every body the rank
+owns, in the run's dtype) as DIR/<name>.npy -- a fixed, seeded sample of the bodies when they exceed 64 MB; rank r of N > 1
+writes DIR/rank<r>_<name>.npy.  The scenes are seeded, so the same arguments give the same inputs on every run.
 
 `python bench.py --gpus N` starts by itself: without WORLD_SIZE in the environment the parent spawns the N rank
 processes (before it makes any GPU call) and relays rank 0's JSON line; under `torch.distributed.run` the ranks are
 already there.  On a box with fewer GPUs than ranks the ranks share cuda:0 and the collectives are staged through gloo --
 a functional rehearsal, flagged as such in `data`, never a measurement.
 
-Timing: W untimed warm-up ticks, then blocks of exactly K ticks, each bracketed by barrier + torch.cuda.synchronize().
-When a block is shorter than 50 ms it is repeated and the MEDIAN block is reported (`steps` stays K).  The closing
-timestamp is taken after the local synchronize and before the closing barrier; the job's time is the MAX over ranks.
+Timing: W untimed warm-up ticks, then ONE block of exactly K ticks (the headline: `ms_per_step` = block time / K),
+bracketed by barrier + torch.cuda.synchronize().  The --full companions time blocks of their own step counts; when one
+of those is shorter than 50 ms it is repeated and the MEDIAN block is reported.  The closing timestamp is taken after
+the local synchronize and before the closing barrier; the job's time is the MAX over ranks.
 """
 import argparse
 import hashlib
@@ -47,8 +54,10 @@ KERNEL_OF = {"free": "integrate_free", "plane": "step_plane", "convex": "np_conv
              "small": "step_plane / ex_small_front + ex_narrow + ex_small_back + solve_island_wg"}
 SOR_FLOP_PER_ROW_SWEEP = 50      # 20 sweeps x rows x ~50 flop
 HULL_FLOP_PER_POINT = 36         # R p (15) + x (3) - box centre (3) -> box frame (15): np_convex_static, per hull point walked
-MIN_REGION_S = 0.050             # blocks shorter than this are repeated; the median block is reported
+MIN_REGION_S = 0.050             # (--full companions) blocks shorter than this are repeated; the median block is reported
 MAX_BLOCKS = 401
+DUMP_BYTES = 64_000_000          # --dump-outputs: at most this much in all (over the ranks)
+DUMP_SEED = 20240601             # the fixed sample of bodies when the state exceeds DUMP_BYTES
 
 
 def parse():
@@ -79,6 +88,11 @@ def parse():
     ap.add_argument("--hbm-side", type=int, default=4096, help="grid side of the hbm_resident extra (4096^2 = 16 Mi bodies)")
     ap.add_argument("--gyro", type=int, default=2, choices=[0, 1, 2], help="0 off, 1 explicit, 2 implicit (ODE default)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other configs, f64, hbm_resident, fused, weak, the reference's "
+                         "pen and call, the CPU baselines (each still subject to the --no-* switches above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the headline's last timed tick left as DIR/<name>.npy (pos, quat, lvel, avel)")
     return ap.parse_args()
 
 
@@ -362,9 +376,10 @@ def tile_scene(np, base, reps_x):
 
 
 def measure(cx, a, scene, layout, kind, dtype, *, exchanging, every_tick=False, ticks_per_launch=1, settle_steps=0,
-            steps=None, warmup=None, setup=None, one_block=False):
+            steps=None, warmup=None, setup=None, one_block=False, dump=None):
     """Build the batch and the tick loop for `scene`, warm up, time blocks of `steps` ticks.  Any failure raises: a run
-    that could not exchange is no run (there is no substitute path)."""
+    that could not exchange is no run (there is no substitute path).  `dump(w, n_own)`, if given, is called once the
+    timed ticks are settled, before the batch is freed."""
     torch, dist, pkg, np = cx.torch, cx.dist, cx.pkg, cx.np
     steps = a.steps if steps is None else steps
     warmup = a.warmup if warmup is None else warmup
@@ -471,6 +486,8 @@ def measure(cx, a, scene, layout, kind, dtype, *, exchanging, every_tick=False, 
             st.close()
         torch.cuda.synchronize()
         t_close = cx.max_over_ranks([time.perf_counter() - t_close])[0]
+        if dump is not None:
+            dump(w, layout.n_active if exchanging else scene.n)
         n_ex = exchanges() - ex0
         if graphed:
             n_ex = nblocks * steps              # a captured graph counts its exchanges once, at capture
@@ -684,10 +701,28 @@ def rank_main(a):
 
     if kind == "small":       # (configs[0] as the headline: the throw-away pass config_leg describes)
         measure(cx, a, scene, layout, kind, dtype, exchanging=False, settle_steps=settle, steps=steps_override, warmup=10, one_block=True)
+    dumped = {}
+
+    def keep_state(w, n_own):
+        """the arrays a caller of the tick loop receives: the bodies' state after the last timed tick (a seeded sample when large)"""
+        budget = DUMP_BYTES // world
+        rows = budget // (13 * rsize)                       # pos 3 + quat 4 + lvel 3 + avel 3 reals per body
+        idx = None if n_own <= rows else np.sort(np.random.default_rng(DUMP_SEED).choice(n_own, rows, replace=False))
+        for name, field in (("pos", pkg.batch.POS), ("quat", pkg.batch.QUAT), ("lvel", pkg.batch.LVEL), ("avel", pkg.batch.AVEL)):
+            arr = w.download(field, 0, n_own)
+            dumped[name] = arr if idx is None else arr[idx]
+
+    # the headline: exactly --steps timed ticks in one block (configs[0]: its 600 ticks from the start state)
     head = measure(cx, a, scene, layout, kind, dtype, exchanging=use_exchange, every_tick=a.exchange_every_tick,
                    ticks_per_launch=a.ticks_per_launch if kind == "free" else 1, settle_steps=settle, steps=steps_override,
-                   warmup=10 if steps_override else None, one_block=kind == "small",
-                   setup=(lambda w: w.set_class_pairs(pkg.scenes.GEOM_CONVEX, pkg.scenes.GEOM_CONVEX, False)) if kind == "convex" else None)
+                   warmup=10 if steps_override else None, one_block=True,
+                   setup=(lambda w: w.set_class_pairs(pkg.scenes.GEOM_CONVEX, pkg.scenes.GEOM_CONVEX, False)) if kind == "convex" else None,
+                   dump=keep_state if a.dump_outputs else None)
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        prefix = f"rank{rank}_" if world > 1 else ""
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, f"{prefix}{name}.npy"), arr)
 
     def parallelism_text(m, bodies_per_gpu):
         if not m["exchanging"]:
@@ -714,8 +749,7 @@ def rank_main(a):
         "vs_baseline": None, "dtype": a.dtype, "data": data,
         "timing": {"blocks": head["blocks"], "block_ms_median": head["dt"] * 1e3, "block_ms_min": head["wall_min"] * 1e3,
                    "block_ms_max": head["wall_max"] * 1e3,
-                   "note": "blocks of exactly `steps` ticks, each bracketed by barrier + synchronize; the median block is reported "
-                           "when one block is shorter than 50 ms"},
+                   "note": "one block of exactly `steps` ticks, bracketed by barrier + synchronize"},
         "config": {"workload": workload, "bodies_per_gpu": scene.n, "bodies_total": total_bodies, "dt": "1/60",
                    "parallelism": parallelism_text(head, scene.n),
                    "collide": collide_text(head, a, kind),
@@ -733,8 +767,8 @@ def rank_main(a):
                                          "rank boundaries, which configs[3]'s disjoint slabs are -- an island reaching across two ranks raises there): "
                                          + str(head["c_loop_error"]))
     out["timing"]["ms_per_step_mean"] = head["mean_dt"] * 1e3 / head["steps"]
-    out["timing"]["note"] += ("; ms_per_step_mean = (all blocks + the close of the last open chunk) / all timed ticks: every chunk close "
-                              "(zone test, flag read) is in it, which a median of short blocks leaves out")
+    out["timing"]["note"] += ("; ms_per_step_mean = (the block + the close of the last open chunk) / the timed ticks: every chunk close "
+                              "(zone test, flag read) is in it")
     if world > 1 and config == 4:
         out["config"]["target_claim"] = (
             "north_star's >= 6x at 8 GPUs is judged on THIS line (value at N vs value at N = 1, both one launch per tick, ticks_per_launch 1). "
@@ -761,7 +795,7 @@ def rank_main(a):
                "ms_per_step": m["dt"] * 1e3 / m["steps"], "ms_per_step_mean": m["mean_dt"] * 1e3 / m["steps"], "steps": m["steps"],
                "blocks": m["blocks"], "contacts_last_tick": m["contacts"], "collide": collide_text(m, a, kd),
                "roofline": roofline_of(m, kd, rsize, profile_evidence(kd, a.dtype, sc.n), hp)}
-        if not a.no_cpu_baseline:
+        if cpu_baselines:
             try:
                 leg["cpu_baseline"] = config_cpu_baseline(pkg, build_config, cfg, dtype, min(a.cpu_seconds, 3.0))
             except Exception as e:      # noqa: BLE001
@@ -778,7 +812,8 @@ def rank_main(a):
                                             "are body pairs, every tick runs the pair search and the islands"}
         return leg
 
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras          # a plain run is the headline and nothing else
+    cpu_baselines = a.full and not a.no_cpu_baseline
     if extras and world == 1 and config == 2 and not a.side and not a.no_configs:
         # the other single-GPU BASELINE configs, each with the bound of ITS dominant kernel (configs[3] is the N > 1 headline)
         out["configs"] = {}
@@ -807,7 +842,7 @@ def rank_main(a):
                     w.close()
             except Exception as e:      # noqa: BLE001
                 out["reference_pen"][f"{nb_pen}_bodies"] = {"error": f"{type(e).__name__}: {e}"}
-        if not a.no_cpu_baseline and "error" not in out["reference_pen"].get("400_bodies", {"error": 1}):
+        if cpu_baselines and "error" not in out["reference_pen"].get("400_bodies", {"error": 1}):
             try:        # the oracle on the same 400-body pile, same 240 settling ticks: one core
                 from oracle.orc_ctypes import Oracle
                 ow = Oracle(dtype).world()
@@ -822,7 +857,7 @@ def rank_main(a):
                 out["reference_pen"]["400_bodies"]["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
         # ... and the reference's own CALL: dWorldStep at 1/120 through the ODE API from C (main.c:211-215)
         try:
-            out["reference_main_c"] = reference_main_c(pkg, dtype, min(a.cpu_seconds, 8.0), with_cpu=not a.no_cpu_baseline)
+            out["reference_main_c"] = reference_main_c(pkg, dtype, min(a.cpu_seconds, 8.0), with_cpu=cpu_baselines)
             if dtype == "float32":
                 out["reference_main_c"]["f64"] = reference_main_c(pkg, "float64", 0, with_cpu=False)
         except Exception as e:      # noqa: BLE001
@@ -890,7 +925,7 @@ def rank_main(a):
                                    "note": f"{reps} copies of the headline scene side by side: {big.n * 17 * rsize / 1e6:.0f} MB of live state "
                                            "and constants per tick, beyond the 256 MB Infinity Cache, so the fraction is HBM traffic"}
             del big
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_baselines:
         out["cpu_baseline"] = cpu_baseline(scene, dtype, kind, a.cpu_seconds)
         allc = cpu_baseline_all_cores(scene, dtype, kind, min(6.0, a.cpu_seconds))
         if allc is not None:

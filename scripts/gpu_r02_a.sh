@@ -3,10 +3,10 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02a; mkdir -p $O; cd $R
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/summary.txt
 tail -3 $O/pytest.log
-python bench.py --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?" | tee -a $O/summary.txt
-python bench.py --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?" | tee -a $O/summary.txt
-python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_g2_20.json 2> $O/bench_g2_20.err; echo "bench g2/20 rc=$?" | tee -a $O/summary.txt
-python bench.py --gpus 2 --steps 300 --warmup 50 > $O/bench_g2_300.json 2> $O/bench_g2_300.err; echo "bench g2/300 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_g2_20.json 2> $O/bench_g2_20.err; echo "bench g2/20 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --gpus 2 --steps 300 --warmup 50 > $O/bench_g2_300.json 2> $O/bench_g2_300.err; echo "bench g2/300 rc=$?" | tee -a $O/summary.txt
 for st in 20 1000; do
 python bench.py --side 364 --steps $st --warmup 20 --no-extras --no-cpu-baseline > $O/bench_small_$st.json 2> $O/bench_small_$st.err; echo "small $st rc=$?" | tee -a $O/summary.txt
 done

@@ -3,10 +3,10 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo
 tail -4 $O/pytest.log
 bash scripts/profile_r02.sh > $O/profile.log 2>&1; tail -12 $O/profile.log
 cd $R
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?" | tee -a $O/summary.txt
-python bench.py --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?" | tee -a $O/summary.txt
+python bench.py --full --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?" | tee -a $O/summary.txt
 python bench.py --config 5 --no-cpu-baseline --steps 200 > $O/bench_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?" | tee -a $O/summary.txt
-( time python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_g2.json 2> $O/bench_g2.err ) 2>> $O/summary.txt; echo "g2 rc=$?" | tee -a $O/summary.txt
+( time python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_g2.json 2> $O/bench_g2.err ) 2>> $O/summary.txt; echo "g2 rc=$?" | tee -a $O/summary.txt
 for f in $O/bench_*.json; do echo "== $f"; python - "$f" <<'PY'
 import json,sys
 try:

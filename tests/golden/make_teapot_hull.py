@@ -1,17 +1,19 @@
-"""Generates tests/golden/teapot_hull.npz from the reference's res/teapot.obj with scipy's Qhull binding (run in the
-build container, where /root/reference exists; the GPU box only sees the committed fixture).
+"""Generates tests/golden/teapot_hull.npz from the reference's res/teapot.obj (stored beside it as teapot.obj.gz) with
+scipy's Qhull binding.
 
 The fixture is data derived from a data asset: the 1 265 convex-hull vertices of the OBJ's vertex list (input frame,
 OBJ units, ascending by first occurrence in the file) and Qhull's facts about the hull.  SURVEY.md section 8c pins the
 same facts: 1 265 vertices, 2 526 facets, volume 928 313.535894, area 49 871.335371.
 """
+import gzip
 import os
 
 import numpy as np
 from scipy.spatial import ConvexHull
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-v = np.array([[float(t) for t in line.split()[1:4]] for line in open("/root/reference/res/teapot.obj") if line.startswith("v ")])
+v = np.array([[float(t) for t in line.split()[1:4]] for line in gzip.open(os.path.join(HERE, "teapot.obj.gz"), "rt")
+              if line.startswith("v ")])
 h = ConvexHull(v)
 # the OBJ repeats positions (4 884 "v" lines, 4 442 distinct): keep one index per distinct hull position, the earliest
 pos = {}

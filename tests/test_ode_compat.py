@@ -1,6 +1,7 @@
 """The ODE C API boundary (include/ode/ode.h): a C program that makes the reference's own sequence of
 ODE calls (tests/harness/ode_tick_harness.c) compiles against the shim headers, links against
 libode_mi355*.so, and -- on the GPU box -- reproduces the CPU oracle's poses on the reference's scene."""
+import json
 import os
 import re
 import subprocess
@@ -115,17 +116,18 @@ def test_ode_symbols_exported(libname):
         assert hasattr(lib, n)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/main.c"), reason="reference tree not present on this box")
 def test_reference_symbol_list_is_what_main_c_calls():
-    """Reads the reference's main.c as text: every ODE function it calls is in REFERENCE_SYMBOLS, and every ODE
-    type / constant / field it names is spelled out in include/ode/*.h."""
-    src = open("/root/reference/src/main.c").read()
-    called = set(re.findall(r"\b(d[A-Z]\w*)\s*\(", src))          # dBodyAddForce sits in a // comment (main.c:532)
+    """The names the reference's main.c uses from the ODE API (recorded in tests/golden/main_c_ode_names.json): every ODE
+    function it calls is in REFERENCE_SYMBOLS, and every ODE type / constant / field it names is spelled out in include/ode/*.h."""
+    names = json.load(open(os.path.join(ROOT, "tests", "golden", "main_c_ode_names.json")))
+    called = set(names["called"])                                    # dBodyAddForce sits in a // comment (main.c:532)
     assert called == set(REFERENCE_SYMBOLS)
     hdr = "".join(open(os.path.join(ROOT, "include", "ode", h)).read() for h in ("common.h", "ode.h"))
-    for ident in sorted(set(re.findall(r"\b(d[A-Z]\w*)\b", src)) - called):
+    assert names["identifiers"] and not set(names["identifiers"]) & called
+    for ident in sorted(names["identifiers"]):
         assert re.search(r"\b%s\b" % ident, hdr), f"main.c names {ident}; include/ode does not define it"
-    for field in set(re.findall(r"\.(surface|geom|mode|mu|bounce_vel|bounce|soft_cfm|soft_erp|depth|normal|pos)\b", src)):
+    assert names["fields"]
+    for field in names["fields"]:
         assert re.search(r"\b%s\b" % field, hdr)
 
 
