@@ -271,8 +271,8 @@ static double sor_lcp(const orc_world *w, int m, int nb, const int *ibody)
  * hi, = 0 between, is solved to complementarity instead of swept 20 times.  With cfm > 0 A is positive definite, so
  * the solution is unique: any exact pivoting method reaches the lambda ODE's Dantzig solver reaches.  Here: block
  * principal pivoting (Judice & Pires) -- rows are free / at lo / at hi; solve the free block by Cholesky, flip every
- * row that violates its condition, and fall back to flipping only the highest violating row when the count of
- * violations has failed to shrink three times (Murty's rule, finite for P-matrices).
+ * row that violates its condition, and fall back to flipping only the highest violating row, for the rest of the solve,
+ * once the count of violations has failed to shrink three times (Murty's rule, finite for P-matrices).
  * Every loop below has a fixed operation order; csrc/dmx_islands.hip (lcp_island_wg) follows the same order. */
 static struct { real *A, *M, *r, *lam, *wv; int *state, *idx; size_t cap; } L;
 enum { LCP_FREE = 0, LCP_LO = 1, LCP_HI = 2 };
@@ -343,7 +343,7 @@ static double exact_lcp(orc_world *w, int m, int nb, const int *ibody)
     int *state = L.state, *idx = L.idx;
     real *lam = L.lam, *M = L.M, *r = L.r, *wv = L.wv;
     for (int i = 0; i < m; i++) { state[i] = LCP_FREE; lam[i] = 0; }
-    int best = m + 1, patience = 3, rounds = 0;
+    int best = m + 1, patience = 3, rounds = 0, single = 0;
     const int max_rounds = 20 * m + 100;
     for (;; rounds++) {
         int nf = 0;
@@ -397,10 +397,12 @@ static double exact_lcp(orc_world *w, int m, int nb, const int *ibody)
             if (v) { nv++; top = i; }
         }
         if (nv == 0 || rounds >= max_rounds) break;
-        int all = 1;
-        if (nv < best) { best = nv; patience = 3; }
+        /* once block pivoting has stalled, Murty's single flips to the end: returning to block flips whenever a single flip
+         * lowers the count lets the two undo each other, and the solve cycles to max_rounds */
+        if (nv < best) { best = nv; if (!single) patience = 3; }
         else if (patience > 0) patience--;
-        else all = 0;
+        else single = 1;
+        int all = !single;
         for (int i = 0; i < m; i++) {
             if (!idx[i] || (!all && i != top)) continue;
             state[i] = idx[i] == 1 ? LCP_LO : idx[i] == 2 ? LCP_HI : LCP_FREE;

@@ -19,6 +19,18 @@ GYRO_OFF, GYRO_EXPLICIT, GYRO_IMPLICIT = 0, 1, 2
 CONTACT_BOUNCE = 0x004
 SNAPSHOT_PINGPONG, SNAPSHOT_COPY = 0, 1
 EXACT_AUTO, EXACT_STAGED, EXACT_ONE_WORKGROUP = 0, 1, 2
+STEPPER_QUICK, STEPPER_EXACT = 0, 1
+ORDER_CREATION, ORDER_ODE = 0, 1
+BODY_ALIVE, BODY_KINEMATIC, BODY_NOGRAVITY, BODY_NOGYRO = 1, 2, 4, 8
+CONTACT_SOFT_ERP, CONTACT_SOFT_CFM = 0x008, 0x010
+# dmxContactJoint (include/dmx_batch.h): the C layout, padding included (tests/test_solver_dense.py checks it with offsetof)
+CONTACT_JOINT_DTYPE = np.dtype({
+    "names": ["pos", "normal", "depth", "body1", "body2", "mode", "mu", "bounce", "bounce_vel", "soft_erp", "soft_cfm"],
+    "formats": [(np.float64, 3), (np.float64, 3), np.float64, np.int32, np.int32, np.int32, np.float64, np.float64,
+                np.float64, np.float64, np.float64],
+    "offsets": [0, 24, 48, 56, 60, 64, 72, 80, 88, 96, 104],
+    "itemsize": 112})
+LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", "single", "fallback")
 
 
 class DmxError(RuntimeError):
@@ -172,6 +184,32 @@ class BatchWorld:
     # -- stepping ----------------------------------------------------------------------
     def step(self, h, nsteps=1):
         _check(self.lib.dmxBatchStep(self.h, h, nsteps), "dmxBatchStep")
+
+    # -- explicit contact joints: the callback form of the tick (dJointCreateContact + dWorldStep, include/dmx_batch.h) --
+    def step_joints(self, h, joints):
+        """one tick driven by `joints`, an array of CONTACT_JOINT_DTYPE (or anything with its fields)"""
+        j = np.ascontiguousarray(np.asarray(joints).astype(CONTACT_JOINT_DTYPE, copy=False))
+        _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
+               "dmxBatchStepJoints")
+
+    def set_stepper(self, stepper):
+        """STEPPER_QUICK (dWorldQuickStep, default) / STEPPER_EXACT (dWorldStep) for step_joints"""
+        _check(self.lib.dmxBatchSetStepper(self.h, int(stepper)), "dmxBatchSetStepper")
+
+    def lcp_stats(self):
+        """the eight counters of the grid-wide exact solve (LCP_STATS names them)"""
+        out = (C.c_int64 * 8)()
+        _check(self.lib.dmxBatchLcpStats(self.h, out), "dmxBatchLcpStats")
+        return dict(zip(LCP_STATS, out))
+
+    def upload_body_flags(self, flags, first=0):
+        """BODY_ALIVE / BODY_KINEMATIC / BODY_NOGRAVITY / BODY_NOGYRO per slot (uint8)"""
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        _check(self.lib.dmxBatchUploadBodyFlags(self.h, f.ctypes.data, first, f.shape[0]), "dmxBatchUploadBodyFlags")
+
+    def set_row_order(self, order, seed=0):
+        """ORDER_CREATION (default) / ORDER_ODE: the order QuickStep sweeps an island's rows in"""
+        _check(self.lib.dmxBatchSetRowOrder(self.h, int(order), int(seed)), "dmxBatchSetRowOrder")
 
     def set_body_collisions(self, enable):
         _check(self.lib.dmxBatchSetBodyCollisions(self.h, int(enable)), "dmxBatchSetBodyCollisions")

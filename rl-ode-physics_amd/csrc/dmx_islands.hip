@@ -993,6 +993,7 @@ __global__ __launch_bounds__(WG) void lcp_island_wg(T *__restrict__ S, const uin
     __syncthreads();
     const T tol = s_tol;
     int best = m + 1, patience = 3;                     // (only thread 0's copies matter)
+    bool single = false;
     const int max_rounds = 20 * m + 100;
     for (int round = 0;; round++) {
         if (tid == 0) {
@@ -1074,10 +1075,10 @@ __global__ __launch_bounds__(WG) void lcp_island_wg(T *__restrict__ S, const uin
             }
             int done = (nv == 0 || round >= max_rounds) ? 1 : 0;
             if (!done) {
-                bool all = true;
-                if (nv < best) { best = nv; patience = 3; }
+                if (nv < best) { best = nv; if (!single) patience = 3; }      // single flips, once begun, to the end
                 else if (patience > 0) patience--;
-                else all = false;
+                else single = true;
+                const bool all = !single;
                 for (int i = 0; i < m; i++) {
                     if (!viol[i] || (!all && i != top)) continue;
                     state[i] = viol[i] == 1 ? LCP_LO : viol[i] == 2 ? LCP_HI : LCP_FREE;

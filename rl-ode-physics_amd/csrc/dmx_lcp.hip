@@ -715,6 +715,7 @@ __device__ __forceinline__ int lds_pivot_rounds(const T *M, int m, int nu, int n
     const int lane = tid & 63, wave = tid >> 6;
     int round = 0;
     int best = m + 1, patience = murty_only ? 0 : 3;
+    bool single = false;
     if (nbd <= 0) return 0;
     for (;; round++) {
         // the free rows in order
@@ -778,11 +779,13 @@ __device__ __forceinline__ int lds_pivot_rounds(const T *M, int m, int nu, int n
         __syncthreads();
         const int nviol = s_nv, top = s_top;
         if (nviol == 0 || round >= max_rounds) break;
-        bool all = true;
-        if (nviol < best) { best = nviol; if (!murty_only) patience = 3; }
+        // once block pivoting has stalled, Murty's single flips to the end: going back to block flips when a single flip has
+        // lowered the count lets the two undo each other, and the solve cycles to max_rounds (masses 1e-3 .. 1e3 in one chain,
+        // tests/test_gpu_solver_dense.py)
+        if (nviol < best) { best = nviol; if (!murty_only && !single) patience = 3; }
         else if (patience > 0) patience--;
-        else all = false;
-        if (murty_only) all = false;
+        else single = true;
+        const bool all = !(murty_only || single);
         for (int q = tid; q < nbd; q += WG) {
             const int vi = viol[q];
             if (!vi || (!all && q != top)) continue;
@@ -1395,11 +1398,11 @@ int lcp_grid_solve(dmxBatch *b, const IslandSet<T> &I, const StepParams<T> &P, c
                 }
                 in_v.assign((size_t)nbd, 0);           // too many for one workgroup: a classical round on all of them, V starts again
             }
-            bool all = true;
-            if (nviol < best) { best = nviol; if (!g->murty_only) patience = 3; }
+            bool all = true;         // (single flips, once begun, to the end: see lds_pivot_rounds)
+            if (nviol < best) { best = nviol; if (!g->murty_only && single_rounds == 0) patience = 3; }
             else if (patience > 0) patience--;
             else all = false;
-            if (g->murty_only) all = false;
+            if (g->murty_only || single_rounds > 0) all = false;
             if (!all) single_rounds++;
             for (int q = 0; q < nbd; q++) {
                 if (!h_viol[q] || (!all && q != top)) continue;
