@@ -279,6 +279,27 @@ int dmxBatchSetStepper(dmxBatchID b, int stepper);
  * [2] most rounds in one solve, [3..5] rows / never-clamping rows / bounded rows of the last island solved, [6] rounds that
  * flipped a single row (Murty's rule), [7] ticks stepped with the SOR because an island exceeded DMX_MAX_EXACT_ROWS. */
 int dmxBatchLcpStats(dmxBatchID b, int64_t out[8]);
+/* The single-launch tick of small worlds (csrc/dmx_small.hip).  A dmxBatchStepJoints tick of a world of tens of bodies is
+ * bound by launches and copies, not arithmetic; when the tick is ELIGIBLE it runs as one kernel launch with no copy in either
+ * direction: the tick's tables are read from host-mapped pinned staging, and every body's 13 state reals are written to the
+ * slab and to a host-mapped mirror that dmxBatchDownload(DMX_STATE) serves from after waiting for the tick.  Eligible: mode
+ * AUTO; rows in creation order (not DMX_ORDER_ODE under QuickStep); the whole batch stepped from host contact geometry; at
+ * most 512 live bodies (in a batch of at most 4 096 slots) and 512 islands; QuickStep: no island of more than 256 rows;
+ * dWorldStep: every island's solve fits one workgroup's LDS.  Any other tick runs on the general path, whole: same results
+ * (the kernels share their device functions), no mixed ticks.  DMX_SMALL_TICK=0 in the environment makes OFF the default of
+ * every batch of the process; DMX_SMALL_TICK_REPORT=1 prints the counters to stderr when a batch is destroyed. */
+#define DMX_SMALL_TICK_OFF   0   /* never */
+#define DMX_SMALL_TICK_AUTO  1   /* default: when the tick is eligible */
+int dmxBatchSetSmallTick(dmxBatchID b, int mode);
+/* Counters since the batch was created: ticks on the single-launch path, ticks of dmxBatchStepJoints on the general path,
+ * then per reason the ticks that were not eligible (a tick counts under the first reason that applies, in this order). */
+enum {
+    DMX_SMALL_TICK_STAT_SMALL = 0, DMX_SMALL_TICK_STAT_GENERAL = 1, DMX_SMALL_TICK_STAT_MODE = 2, DMX_SMALL_TICK_STAT_ROW_ORDER = 3,
+    DMX_SMALL_TICK_STAT_SUBSET = 4, DMX_SMALL_TICK_STAT_BODIES = 5, DMX_SMALL_TICK_STAT_ISLANDS = 6, DMX_SMALL_TICK_STAT_SOR_ROWS = 7,
+    DMX_SMALL_TICK_STAT_LDS_FIT = 8
+};
+#define DMX_SMALL_TICK_NSTATS 9
+int dmxBatchSmallTickStats(dmxBatchID b, int64_t out[DMX_SMALL_TICK_NSTATS]);
 /* The order QuickStep's SOR sweeps an island's rows in (dmxBatchStepJoints, DMX_STEPPER_QUICK).  DMX_ORDER_CREATION (default):
  * the order the contact joints were created in, every sweep -- deterministic, and what lets islands be solved by workgroups
  * under a level schedule.  DMX_ORDER_ODE: what stock ODE does [ODE-recall]: rows numbered in the order its island builder

@@ -31,6 +31,10 @@ CONTACT_JOINT_DTYPE = np.dtype({
     "offsets": [0, 24, 48, 56, 60, 64, 72, 80, 88, 96, 104],
     "itemsize": 112})
 LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", "single", "fallback")
+# the single-launch tick of small worlds (dmxBatchSetSmallTick); the counters of dmxBatchSmallTickStats, in its order: ticks on
+# that path, step_joints ticks on the general path, then one count per reason a tick was not eligible
+SMALL_TICK_OFF, SMALL_TICK_AUTO = 0, 1
+SMALL_TICK_STATS = ("small", "general", "mode", "row_order", "subset", "bodies", "islands", "sor_rows", "lds_fit")
 
 
 class DmxError(RuntimeError):
@@ -201,6 +205,16 @@ class BatchWorld:
         out = (C.c_int64 * 8)()
         _check(self.lib.dmxBatchLcpStats(self.h, out), "dmxBatchLcpStats")
         return dict(zip(LCP_STATS, out))
+
+    def set_small_tick(self, mode):
+        """SMALL_TICK_AUTO (default): an eligible step_joints tick runs as one kernel launch; SMALL_TICK_OFF: never"""
+        _check(self.lib.dmxBatchSetSmallTick(self.h, int(mode)), "dmxBatchSetSmallTick")
+
+    def small_tick_stats(self):
+        """ticks per path and per reason a tick was not eligible (SMALL_TICK_STATS names them)"""
+        out = (C.c_int64 * len(SMALL_TICK_STATS))()
+        _check(self.lib.dmxBatchSmallTickStats(self.h, out), "dmxBatchSmallTickStats")
+        return dict(zip(SMALL_TICK_STATS, out))
 
     def upload_body_flags(self, flags, first=0):
         """BODY_ALIVE / BODY_KINEMATIC / BODY_NOGRAVITY / BODY_NOGYRO per slot (uint8)"""

@@ -14,6 +14,7 @@
 
 #include "dmx_batch_priv.hpp"
 #include "dmx_lcp.hpp"
+#include "dmx_small.hpp"
 
 // a chunk dmxBatchStep left open is closed (flag read, rollback + replay if need be) before anything observes or changes the batch
 #define SETTLE(b)                                  \
@@ -99,10 +100,14 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
         if (preload) {
             const int rb = b->precision == DMX_F32 ? 4 : 8;
             (void)dmx::dmx_touch_kernels(rb); (void)dmx::dmx_touch_islands(rb); (void)dmx::dmx_touch_broadphase(rb);
-            (void)dmx::dmx_touch_narrow(rb); (void)dmx::dmx_touch_exact(rb);
+            (void)dmx::dmx_touch_narrow(rb); (void)dmx::dmx_touch_exact(rb); (void)dmx::dmx_touch_small(rb);
         }
     }
     if (const char *v = getenv("DMX_LAZY_CHUNKS")) b->lazy_chunks = atoi(v) != 0;
+    {
+        static const int small_default = [] { const char *e = getenv("DMX_SMALL_TICK"); return e && atoi(e) == 0 ? DMX_SMALL_TICK_OFF : DMX_SMALL_TICK_AUTO; }();
+        b->small_mode = small_default;
+    }
     if (const char *v = getenv("DMX_STATIC_FAST")) b->static_fast = atoi(v) != 0;
     int rc = DMX_OK;
     do {
@@ -155,6 +160,20 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
         for (int k = 1; k < 9; k++) fprintf(stderr, "  front %-18s %7.2f us\n", fn[k], b->exs_acc[k] / (double)b->exs_ticks / 100.0);
         for (int k = 1; k < 9; k++) fprintf(stderr, "  back  %-18s %7.2f us\n", bn[k], b->exs_acc[32 + k] / (double)b->exs_ticks / 100.0);
     }
+    {
+        static const bool report = [] { const char *e = getenv("DMX_SMALL_TICK_REPORT"); return e && atoi(e) != 0; }();
+        const int64_t *s = b->small_stats;
+        if (report)
+            fprintf(stderr, "libode_mi355 small tick: small=%lld general=%lld mode=%lld row_order=%lld subset=%lld bodies=%lld islands=%lld sor_rows=%lld lds_fit=%lld\n",
+                    (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], (long long)s[5], (long long)s[6],
+                    (long long)s[7], (long long)s[8]);
+    }
+    for (int p = 0; p < 2; p++) {
+        if (b->sm_stage[p]) (void)hipHostFree(b->sm_stage[p]);
+        if (b->sm_ev[p]) (void)hipEventDestroy(b->sm_ev[p]);
+    }
+    if (b->sm_mirror) (void)hipHostFree(b->sm_mirror);
+    if (b->sm_diag) (void)hipFree(b->sm_diag);
     dmx::lcp_grid_free(b);
     if (b->slab) (void)hipFree(b->slab);
     if (b->slab_alt) (void)hipFree(b->slab_alt);
@@ -235,6 +254,7 @@ static int upload_t(dmxBatch *b, int field, const void *host, int64_t first, int
         }
         src = tmp.data();
     }
+    dmx_state_written(b);
     HIP_TRY(hipMemcpyAsync(b->stage, src, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(launch_aos_to_soa<T>((T *)b->slab, b->stride, k_field_comp0[field], k, first, count,
                                  (const T *)b->stage, b->stream));
@@ -287,6 +307,17 @@ extern "C" int dmxBatchDownload(dmxBatchID b, int field, void *host, int64_t fir
     SETTLE(b);
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
+    if (b->sm_mirror_valid && !b->slab_exposed && k_field_comp0[field] + k_field_k[field] <= C_MASS) {
+        // the last writer of body state was a single-launch tick: its kernel wrote every slot's 13 state reals (DMX_STATE order)
+        // to the host-mapped mirror -- wait for it (the one wait of such a tick), no kernel, no copy.  DMX_STATE is the whole
+        // record, the other state fields a run of it.
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        const size_t rs = b->rsize, kb = (size_t)k_field_k[field] * rs;
+        const char *src = (const char *)b->sm_mirror + ((size_t)first * C_MASS + (size_t)k_field_comp0[field]) * rs;
+        if (k_field_k[field] == C_MASS) memcpy(host, src, (size_t)count * kb);
+        else for (int64_t i = 0; i < count; i++) memcpy((char *)host + (size_t)i * kb, src + (size_t)i * C_MASS * rs, kb);
+        return DMX_OK;
+    }
     return b->precision == DMX_F32 ? download_t<float>(b, field, host, first, count)
                                    : download_t<double>(b, field, host, first, count);
 }
@@ -342,6 +373,7 @@ extern "C" void *dmxBatchDevicePtr(dmxBatchID b, int field, int component)
 {
     if (!b || field < 0 || field >= DMX_NFIELDS || component < 0 || component >= k_field_k[field]) return nullptr;
     if (dmx_settle(b) != DMX_OK) return nullptr;
+    b->slab_exposed = true;       // the caller may write the slab behind the batch's back: the mirror is no longer served
     return (char *)b->slab + (size_t)slab_ix(k_field_comp0[field] + component, 0) * b->rsize;
 }
 
@@ -378,6 +410,7 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
 {
     if (!b || !(h > 0) || nsteps < 0) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     if (b->bp_enabled) return dmx_step_collide(b, h, nsteps);
     SETTLE(b);
     int rc = b->precision == DMX_F32 ? step_t<float>(b, h, nsteps, 0, b->n_active, true)
@@ -392,6 +425,21 @@ extern "C" int dmxBatchSetStepper(dmxBatchID b, int stepper)
     if (!b || (stepper != DMX_STEPPER_QUICK && stepper != DMX_STEPPER_EXACT)) return DMX_EINVAL;
     SETTLE(b);
     b->stepper_exact = stepper == DMX_STEPPER_EXACT;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetSmallTick(dmxBatchID b, int mode)
+{
+    if (!b || (mode != DMX_SMALL_TICK_OFF && mode != DMX_SMALL_TICK_AUTO)) return DMX_EINVAL;
+    SETTLE(b);
+    b->small_mode = mode;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSmallTickStats(dmxBatchID b, int64_t out[DMX_SMALL_TICK_NSTATS])
+{
+    if (!b || !out) return DMX_EINVAL;
+    for (int k = 0; k < DMX_SMALL_TICK_NSTATS; k++) out[k] = b->small_stats[k];
     return DMX_OK;
 }
 
@@ -556,18 +604,21 @@ extern "C" int dmxBatchChunkBegin(dmxBatchID b, int *exact_only, int *ballistic)
     if (!b || !exact_only || !ballistic) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_chunk_begin(b, exact_only, ballistic);
 }
 extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_chunk_tick(b, h, check);
 }
 extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_first, int check_last)
 {
     if (!b || !(h > 0) || nticks < 0) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_chunk_ticks(b, h, nticks, check_first, check_last);
 }
 extern "C" int dmxBatchSetTicksPerLaunch(dmxBatchID b, int ticks)
@@ -590,6 +641,7 @@ extern "C" int dmxBatchRefreshGhostsOnStream(dmxBatchID b, void *hip_stream, int
     if (!b || first < b->n_active || count_lo < 0 || count_hi < 0 || first + count_lo + count_hi > b->n) return DMX_EINVAL;
     SETTLE(b);
     if (check && !b->bp_flags.p) return DMX_EINVAL;          // no chunk begun: there are no zones to test against
+    dmx_state_written(b);
     HIP_TRY(hipSetDevice(b->device));
     uint32_t *flags = (uint32_t *)b->bp_flags.p;
     if (b->precision == DMX_F32)
@@ -604,17 +656,20 @@ extern "C" int dmxBatchChunkEnd(dmxBatchID b, int *violated, int *warn)
 {
     if (!b || !violated || !warn) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_chunk_end(b, violated, warn);
 }
 extern "C" int dmxBatchChunkCommit(dmxBatchID b, int ticks, int refresh_zones)
 {
     if (!b || ticks < 0) return DMX_EINVAL;
+    dmx_state_written(b);
     return dmx_chunk_commit(b, ticks, refresh_zones);
 }
 extern "C" int dmxBatchChunkRollback(dmxBatchID b)
 {
     if (!b) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_chunk_rollback(b);
 }
 extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
@@ -622,6 +677,7 @@ extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
     if (!b || !(h > 0)) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return dmx_exact_tick(b, h);
 }
 
@@ -689,6 +745,7 @@ extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t 
     if (first % 64 != 0) return DMX_EINVAL;      // ranges start on a wave so per-wave diagnostics slots stay disjoint
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_state_written(b);
     return b->precision == DMX_F32 ? step_t<float>(b, h, 1, first, count, reset_diag != 0)
                                    : step_t<double>(b, h, 1, first, count, reset_diag != 0);
 }
@@ -736,7 +793,8 @@ static int fetch_diag(dmxBatch *b, unsigned long long *contacts, double *residua
 {
     HIP_TRY(hipSetDevice(b->device));
     if (b->last_islands) {
-        HIP_TRY(hipMemcpyAsync(b->diag_host, b->diag_isl, sizeof(StepDiag), hipMemcpyDeviceToHost, b->stream));
+        const StepDiag *src = b->last_small ? b->sm_diag + b->sm_diag_cur : b->diag_isl;      // (a single-launch tick keeps its own two slots)
+        HIP_TRY(hipMemcpyAsync(b->diag_host, src, sizeof(StepDiag), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         *contacts = b->diag_host[0].contacts; *residual = b->diag_host[0].residual;
         return DMX_OK;
@@ -825,6 +883,7 @@ static int scatter_on(dmxBatch *b, const int32_t *idx_dev, int64_t count, const 
     if (!b || count < 0 || (count > 0 && (!idx_dev || !in_dev))) return DMX_EINVAL;
     SETTLE(b);
     b->bp_valid = false;
+    dmx_state_written(b);
     HIP_TRY(hipSetDevice(b->device));
     if (b->precision == DMX_F32)
         HIP_TRY(launch_scatter<float>((float *)b->slab, b->stride, idx_dev, count, (const float *)in_dev, st));

@@ -155,7 +155,26 @@ struct dmxBatch {
     unsigned long long last_pairs = 0;
     bool last_mixed = false;                   // last tick used fused + island kernels together
     size_t jh_int_bytes = 0, jh_real_bytes = 0;
+    // single-launch tick of small worlds (dmx_small.hip; the host side is in dmx_joints.cpp)
+    int small_mode = DMX_SMALL_TICK_AUTO;          // dmxBatchSetSmallTick; DMX_SMALL_TICK=0 makes OFF the default
+    int64_t small_stats[DMX_SMALL_TICK_NSTATS] = { 0 };
+    // host-mapped pinned staging (ints, then reals), two buffers used alternately: tick k + 1's tables are filled while tick k's
+    // kernel may still read its own; sm_ev[p] is recorded behind the launch that reads buffer p
+    void *sm_stage[2] = { nullptr, nullptr }, *sm_stage_dev[2] = { nullptr, nullptr };
+    size_t sm_stage_bytes[2] = { 0, 0 };
+    hipEvent_t sm_ev[2] = { nullptr, nullptr }; bool sm_ev_pending[2] = { false, false };
+    int sm_parity = 0;
+    // the mirror: 13 reals per slot (DMX_STATE order), host-mapped pinned, written by small_world_tick.  Valid = it holds the
+    // slab's state once the stream has drained; EVERY other writer of body state clears the flag (dmx_state_written)
+    void *sm_mirror = nullptr, *sm_mirror_dev = nullptr;
+    bool sm_mirror_valid = false;
+    bool sm_lcp_touched = false;                   // dmx_touch_lcp done for this batch (first small dWorldStep tick)
+    bool slab_exposed = false;                     // dmxBatchDevicePtr handed the slab out: writes the batch cannot see -- the mirror is never served
+    StepDiag *sm_diag = nullptr; int sm_diag_cur = 0;      // two device slots used alternately (each launch zeroes the next one's)
+    bool last_small = false;                       // the last dmxBatchStepJoints tick left its diagnostics in sm_diag[sm_diag_cur]
 };
+// called by everything that changes body state in the slab other than the single-launch tick
+inline void dmx_state_written(dmxBatch *b) { b->sm_mirror_valid = false; }
 
 int dmx_ensure_dev(dmxBatch::DevBuf &d, size_t bytes);
 // do the fused kernels make contacts (and so leave contact diagnostics behind)?  The ground plane, or static boxes on the fused path

@@ -11,6 +11,7 @@
 
 #include "dmx_batch_priv.hpp"
 #include "dmx_lcp.hpp"
+#include "dmx_small.hpp"
 
 namespace {
 
@@ -53,6 +54,19 @@ int ensure_pinned(void **p, size_t *have, size_t bytes)
     return DMX_OK;
 }
 
+// the same for host-mapped memory (hipHostMallocMapped) and its device address
+int ensure_mapped(void **p, void **dev, size_t *have, size_t bytes)
+{
+    if (bytes <= *have) return DMX_OK;
+    if (*p) HIP_TRY(hipHostFree(*p));
+    *p = nullptr; *dev = nullptr; *have = 0;
+    size_t want = bytes + bytes / 2 + 4096;
+    HIP_TRY(hipHostMalloc(p, want, hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer(dev, *p, 0));
+    *have = want;
+    return DMX_OK;
+}
+
 template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const dmxContactJoint *joints,
                                      const uint8_t *include, const DevGeometry *geo)
 {
@@ -64,9 +78,6 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         b->sc_island.assign((size_t)n, -1);
         b->sc_last.assign((size_t)n, -1);
     }
-    // previous tick's async copies read the pinned staging buffers: drain before refilling
-    HIP_TRY(hipStreamSynchronize(b->stream));
-
     // ---- canonical joints: body1 is a live dynamic slot, normal points into it -----------------------
     std::unique_ptr<DmxPhase> ph(new DmxPhase(b, 4));
     // (all per-tick work arrays below are members of the batch, reused from tick to tick: tens of MB of fresh
@@ -310,6 +321,20 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     const int n_big = (int)big_list_h.size();
     ph.reset(new DmxPhase(b, 6));
 
+    // ---- the single-launch tick (dmx_small.hip)?  Decided on integers the host has by now; one reason that says no sends the
+    // whole tick down the general path.  The tables built above are what both paths consume.
+    int why = -1;
+    if (b->small_mode != DMX_SMALL_TICK_AUTO) why = DMX_SMALL_TICK_STAT_MODE;
+    else if (ode_order) why = DMX_SMALL_TICK_STAT_ROW_ORDER;
+    else if (include || geo) why = DMX_SMALL_TICK_STAT_SUBSET;
+    else if (nlive > SMALL_MAX_BODIES || n > 8 * SMALL_MAX_BODIES) why = DMX_SMALL_TICK_STAT_BODIES;      // (the mirror and its fill cover the capacity)
+    else if (ni > SMALL_MAX_ISLANDS) why = DMX_SMALL_TICK_STAT_ISLANDS;
+    else if (!exact && big_max_rows > WAVE_ISLAND_ROWS) why = DMX_SMALL_TICK_STAT_SOR_ROWS;            // (the one-wavefront form of solve_island_wg)
+    else if (exact && (!grid_list.empty() || lcp_old_kernel())) why = DMX_SMALL_TICK_STAT_LDS_FIT;
+    const bool small = why < 0;
+    b->small_stats[small ? DMX_SMALL_TICK_STAT_SMALL : DMX_SMALL_TICK_STAT_GENERAL]++;
+    if (!small) b->small_stats[why]++;
+
     // int staging: body_off[ni+1] bodies[nlive] con_off[ni+1] row_off[ni+1] cb1[nc] cb2[nc] cmode[nc] csrc[nc] crow[nc]
     //              big[ni] big_list[n_big] lev_count[n_big] lev_off[..] lev_rows[..]
     const size_t n_int = (size_t)3 * (ni + 1) + (size_t)nlive + (size_t)5 * nc + (size_t)ni + (size_t)2 * n_big +
@@ -317,10 +342,30 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // real staging: cpos[3nc] cnormal[3nc] cdepth cmu cbounce cbounce_vel csoft_erp csoft_cfm [nc each]
     const size_t n_real = (size_t)12 * nc;
     int rc;
-    if ((rc = ensure_pinned(&b->jh_int, &b->jh_int_bytes, n_int * sizeof(int) + 64)) != DMX_OK) return rc;
-    if ((rc = ensure_pinned(&b->jh_real, &b->jh_real_bytes, n_real * sizeof(T) + 64)) != DMX_OK) return rc;
-    int *hi = (int *)b->jh_int;
-    T *hr = (T *)b->jh_real;
+    int *hi; T *hr;
+    const int sp = b->sm_parity;
+    const size_t sm_real_at = ((n_int * sizeof(int) + 64 + 255) / 256) * 256;      // the reals' offset in a small tick's staging buffer
+    if (small) {
+        // host-mapped staging buffer `sp`: last read by the small tick before the previous one
+        if (b->sm_ev_pending[sp]) { HIP_TRY(hipEventSynchronize(b->sm_ev[sp])); b->sm_ev_pending[sp] = false; }
+        if ((rc = ensure_mapped(&b->sm_stage[sp], &b->sm_stage_dev[sp], &b->sm_stage_bytes[sp], sm_real_at + n_real * sizeof(T) + 64)) != DMX_OK) return rc;
+        hi = (int *)b->sm_stage[sp];
+        hr = (T *)((char *)b->sm_stage[sp] + sm_real_at);
+        // the general path's own pinned staging keeps pace with the world (a compare per tick while it is large enough): a tick
+        // that falls back -- one island past a limit -- must not meet its first allocations there, a millisecond of them
+        if (n_int * sizeof(int) + 64 > b->jh_int_bytes || n_real * sizeof(T) + 64 > b->jh_real_bytes) {
+            HIP_TRY(hipStreamSynchronize(b->stream));          // (an earlier general tick's copies may still read the old buffers)
+            if ((rc = ensure_pinned(&b->jh_int, &b->jh_int_bytes, n_int * sizeof(int) + 64)) != DMX_OK) return rc;
+            if ((rc = ensure_pinned(&b->jh_real, &b->jh_real_bytes, n_real * sizeof(T) + 64)) != DMX_OK) return rc;
+        }
+    } else {
+        // previous tick's async copies read the pinned staging buffers: drain before refilling
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if ((rc = ensure_pinned(&b->jh_int, &b->jh_int_bytes, n_int * sizeof(int) + 64)) != DMX_OK) return rc;
+        if ((rc = ensure_pinned(&b->jh_real, &b->jh_real_bytes, n_real * sizeof(T) + 64)) != DMX_OK) return rc;
+        hi = (int *)b->jh_int;
+        hr = (T *)b->jh_real;
+    }
     int *body_off = hi, *bodies = body_off + (ni + 1), *con_off = bodies + nlive, *row_off = con_off + (ni + 1);
     int *cb1 = row_off + (ni + 1), *cb2 = cb1 + nc, *cmode = cb2 + nc, *csrc = cmode + nc, *crow = csrc + nc;
     int *big = crow + nc, *big_list = big + ni, *lev_count = big_list + n_big, *lev_off = lev_count + n_big;
@@ -370,18 +415,20 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // ---- device buffers -----------------------------------------------------------------------------------
     ph.reset(new DmxPhase(b, 7));
     const size_t nrows = (size_t)3 * nc;
+    // (a small tick reads neither of these two, but keeps them sized for the tick that falls back: see the pinned staging above)
     if ((rc = dmx_ensure_dev(b->jd_int, n_int * sizeof(int) + 64)) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->jd_real, n_real * sizeof(T) + 64)) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->jd_rows, (nrows + 1) * ISLAND_ROW_REALS * sizeof(T))) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->jd_rowjb, (nrows + 1) * 2 * sizeof(int))) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->jd_bscr, ((size_t)nlive + 1) * 28 * sizeof(T))) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->jd_local, (size_t)b->stride * sizeof(int))) != DMX_OK) return rc;
-    if (n_int) HIP_TRY(hipMemcpyAsync(b->jd_int.p, hi, n_int * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    if (n_real) HIP_TRY(hipMemcpyAsync(b->jd_real.p, hr, n_real * sizeof(T), hipMemcpyHostToDevice, b->stream));
+    if (!small && n_int) HIP_TRY(hipMemcpyAsync(b->jd_int.p, hi, n_int * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (!small && n_real) HIP_TRY(hipMemcpyAsync(b->jd_real.p, hr, n_real * sizeof(T), hipMemcpyHostToDevice, b->stream));
 
     IslandSet<T> I;
-    int *di = (int *)b->jd_int.p;
-    T *dr = (T *)b->jd_real.p;
+    // (a small tick's kernel reads the tables where the host wrote them: the device address of the mapped staging)
+    int *di = small ? (int *)b->sm_stage_dev[sp] : (int *)b->jd_int.p;
+    T *dr = small ? (T *)((char *)b->sm_stage_dev[sp] + sm_real_at) : (T *)b->jd_real.p;
     I.n_islands = ni;
     I.body_off = di; I.bodies = di + (ni + 1); I.con_off = I.bodies + nlive; I.row_off = I.con_off + (ni + 1);
     I.cb1 = I.row_off + (ni + 1); I.cb2 = I.cb1 + nc; I.cmode = I.cb2 + nc;
@@ -427,6 +474,56 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     }
 
     StepParams<T> P = dmx_make_params<T>(b, h);
+    if (small) {
+        // one launch: islands with rows a workgroup each, free bodies and one-body islands a lane each; the new state goes to
+        // the slab and to the mirror.  Nobody waits here: dmxBatchDownload(DMX_STATE) does, when the caller reads a pose.
+        if (!b->sm_mirror) {
+            HIP_TRY(hipHostMalloc(&b->sm_mirror, (size_t)n * C_MASS * sizeof(T) + 64, hipHostMallocMapped));
+            HIP_TRY(hipHostGetDevicePointer(&b->sm_mirror_dev, b->sm_mirror, 0));
+        }
+        if (exact && !b->sm_lcp_touched) {        // ... and dWorldStep's own code object (dmx_lcp.hip), which dmxBatchCreate does not load
+            (void)dmx_touch_lcp((int)sizeof(T));
+            b->sm_lcp_touched = true;
+        }
+        if (!b->sm_diag) {
+            HIP_TRY(hipMalloc((void **)&b->sm_diag, 2 * sizeof(StepDiag)));
+            HIP_TRY(hipMemsetAsync(b->sm_diag, 0, 2 * sizeof(StepDiag), b->stream));
+        }
+        if (!b->sm_ev[sp]) HIP_TRY(hipEventCreateWithFlags(&b->sm_ev[sp], hipEventDisableTiming));
+        SmallTick<T> K;
+        K.mirror = (T *)b->sm_mirror_dev;
+        const int cur = b->sm_diag_cur ^ 1;                    // (the slot the previous small tick zeroed)
+        K.diag_next = b->sm_diag + (cur ^ 1);
+        K.n_slots = n;
+        K.full = b->sm_mirror_valid ? 0 : 1;
+        K.lds_bodies = 1; K.murty = 0; K.tol_rel = T(0);
+        size_t lds;
+        if (exact) {
+            double tol;
+            lcp_lds_knobs((int)sizeof(T), &K.murty, &tol);
+            K.tol_rel = (T)tol;
+            lds = lds_need;
+            // (the general exact tick's scratch, kept sized like the staging: not used here)
+            if ((rc = dmx_ensure_dev(b->jd_lcp, (size_t)(b->sc_lcp_off[(size_t)n_big] + 1) * sizeof(T))) != DMX_OK) return rc;
+            if ((rc = dmx_ensure_dev(b->jd_lcp_off, ((size_t)n_big + 1) * sizeof(long long))) != DMX_OK) return rc;
+            if ((rc = dmx_ensure_dev(b->jd_lcp_int, (nrows + 1) * 3 * sizeof(int))) != DMX_OK) return rc;
+        } else {
+            lds = small_tick_sor_lds((int)sizeof(T), big_max_bodies, &K.lds_bodies);
+        }
+        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, exact, lds, b->stream));
+        HIP_TRY(hipEventRecord(b->sm_ev[sp], b->stream));
+        b->sm_ev_pending[sp] = true;
+        b->sm_parity = sp ^ 1;
+        b->sm_diag_cur = cur;
+        b->sm_mirror_valid = true;
+        b->last_small = true;
+        b->last_islands = true;
+        b->ext_pending = false;
+        b->stepped_with_plane = true;     // diagnostics are valid
+        return DMX_OK;
+    }
+    dmx_state_written(b);
+    b->last_small = false;
     HIP_TRY(hipMemsetAsync(b->diag_isl, 0, sizeof(StepDiag), b->stream));
     if (exact) {
         const size_t nbig = (size_t)n_big;

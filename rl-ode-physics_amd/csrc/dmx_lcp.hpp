@@ -47,6 +47,8 @@ hipError_t dmx_touch_lcp(int real_bytes);
 // lcp_lds_fits: does an island of m rows, nbd of them bounded, fit?  (Islands that do not go to the grid solve.)
 bool lcp_lds_fits(int real_bytes, int m, int nbd);
 size_t lcp_lds_need(int real_bytes, int m, int nbd);
+// lcp_island_lds' pivoting mode (DMX_LCP_MURTY) and relative tolerance (DMX_LCP_TOL; default per precision)
+void lcp_lds_knobs(int real_bytes, int *murty_only, double *tol_rel);
 template <class T>
 hipError_t launch_lcp_lds(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
                           size_t lds_bytes, hipStream_t st);

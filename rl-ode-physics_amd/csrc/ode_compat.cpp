@@ -120,13 +120,25 @@ struct dxWorld {
         cap = capacity;
         slots.resize((size_t)cap, nullptr);
         host_dirty = true;
+        pushed_valid = false;          // a new batch has been told nothing yet
+        // One read-back the general way into the buffer to_host() uses, now.  The runtime registers a pageable destination the
+        // first time a device-to-host copy lands in it (8 ms, measured); a world whose ticks run on the single-launch path reads
+        // its poses from the batch's host mirror and would meet that at the first tick that falls back -- a whole 120 Hz frame.
+        buf.assign((size_t)cap * 13, 0);
+        DMX_MUST(dmxBatchDownload(batch, DMX_STATE, buf.data(), 0, cap));
     }
-    void push_params()
+    // what the batch was last told (push_params): a tick pushes the world's parameters only when one has changed since
+    dReal pushed[7] = { 0, 0, 0, 0, 0, 0, 0 }; int pushed_iters = 0, pushed_stepper = -1; bool pushed_valid = false;
+    void push_params(int stepper)
     {
+        const dReal now[7] = { g[0], g[1], g[2], erp, cfm, sor_w, (dReal)0 };
+        if (pushed_valid && memcmp(now, pushed, sizeof(now)) == 0 && pushed_iters == iters && pushed_stepper == stepper) return;
         DMX_MUST(dmxBatchSetGravity(batch, g[0], g[1], g[2]));
         DMX_MUST(dmxBatchSetERP(batch, erp));
         DMX_MUST(dmxBatchSetCFM(batch, cfm));
         DMX_MUST(dmxBatchSetQuickStep(batch, iters, sor_w));
+        DMX_MUST(dmxBatchSetStepper(batch, stepper));
+        memcpy(pushed, now, sizeof(now)); pushed_iters = iters; pushed_stepper = stepper; pushed_valid = true;
     }
     void to_host()
     {
@@ -268,8 +280,7 @@ static int world_step(dWorldID w, dReal h, int stepper)
 {
     if (!w || !(h > 0)) return 0;
     w->to_device();
-    w->push_params();
-    DMX_MUST(dmxBatchSetStepper(w->batch, stepper));
+    w->push_params(stepper);
     w->cj.clear();
     for (const dxJoint *j : w->joints) {
         dmxContactJoint c;
