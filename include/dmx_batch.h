@@ -198,6 +198,16 @@ int dmxBatchSetExactPipeline(dmxBatchID b, int mode);
  * in registers between them: same arithmetic per tick, same results bit for bit, one read and one write of the state
  * per launch instead of per tick.  Default 1 (one launch per tick); 1..64. */
 int dmxBatchSetTicksPerLaunch(dmxBatchID b, int ticks);
+/* Work the contact-free tick (integrate_free) leaves out because the result does not need it; same results bit for bit
+ * with any mask.  DMX_ELIDE_STORES: a launch that runs in place stores a state component of a wavefront's 64 bodies only
+ * if one of them changed its bits (a body dropped at rest under gravity along y keeps lvel.x/z, pos.x/z and, with isotropic
+ * inertia, avel).  DMX_ELIDE_CONSTANTS: while every slot's mass and inertia are the same -- the library follows the uploads
+ * of DMX_MASS / DMX_INERTIA; any dmxBatchDevicePtr call ends it for the batch's lifetime (the address is one into the slab,
+ * through which the caller can write every component unseen) -- they are passed as kernel arguments instead of loaded per
+ * body.  Launches recorded while the batch's stream is being captured into a HIP graph always load them, so that a replay
+ * sees a later upload of mass or inertia like an eager tick does.  Default: both (DMX_ELIDE=<mask> in the environment changes the default); 0: every load and store. */
+enum { DMX_ELIDE_STORES = 1, DMX_ELIDE_CONSTANTS = 2 };
+int dmxBatchSetElision(dmxBatchID b, int mask);
 int dmxBatchCollisionStats(dmxBatchID b, int64_t out[6]);
 /* the same six numbers and [6] AABB pairs met so far that had no collider (always 0 since every class pair has one), [7] exact ticks
  * of the one-workgroup pipeline whose island solve and fused step were enqueued before the host had the tick's counts, and stood

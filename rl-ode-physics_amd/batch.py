@@ -270,6 +270,11 @@ class BatchWorld:
     def set_ticks_per_launch(self, ticks):
         _check(self.lib.dmxBatchSetTicksPerLaunch(self.h, ticks), "dmxBatchSetTicksPerLaunch")
 
+    def set_elision(self, mask):
+        """bit 0: in-place launches of the contact-free tick store only what changed; bit 1: uniform mass / inertia travel as
+        kernel arguments.  Default 3; 0 = every load and store (include/dmx_batch.h).  Same results bit for bit."""
+        _check(self.lib.dmxBatchSetElision(self.h, int(mask)), "dmxBatchSetElision")
+
     def check_zones_on(self, stream_handle, first, count):
         _check(self.lib.dmxBatchCheckZonesOnStream(self.h, stream_handle, first, count), "dmxBatchCheckZonesOnStream")
 

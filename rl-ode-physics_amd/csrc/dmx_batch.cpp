@@ -93,6 +93,10 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
     if (const char *v = getenv("DMX_MIN_WAVES")) b->min_waves = atoi(v);
     if (const char *v = getenv("DMX_NT")) b->nt = atoi(v);
     if (const char *v = getenv("DMX_OOP")) b->oop = atoi(v);
+    {
+        static const int elide_default = [] { const char *e = getenv("DMX_ELIDE"); return e ? atoi(e) & 3 : (DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS); }();
+        b->elide = elide_default;
+    }
     b->prof_on = getenv("DMX_HOST_PROFILE") != nullptr;
     {
         // every translation unit's code object now, not at the first tick that launches one of its kernels (DMX_PRELOAD=0: lazily)
@@ -255,6 +259,9 @@ static int upload_t(dmxBatch *b, int field, const void *host, int64_t first, int
         src = tmp.data();
     }
     dmx_state_written(b);
+    // the one door constants enter the slab through: the trackers see what goes in (dmx_uniform.hpp)
+    if (field == DMX_MASS) b->uni_mass.on_upload(src, first, count, b->n);
+    if (field == DMX_INERTIA) b->uni_inertia.on_upload(src, first, count, b->n);
     HIP_TRY(hipMemcpyAsync(b->stage, src, bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(launch_aos_to_soa<T>((T *)b->slab, b->stride, k_field_comp0[field], k, first, count,
                                  (const T *)b->stage, b->stream));
@@ -374,6 +381,9 @@ extern "C" void *dmxBatchDevicePtr(dmxBatchID b, int field, int component)
     if (!b || field < 0 || field >= DMX_NFIELDS || component < 0 || component >= k_field_k[field]) return nullptr;
     if (dmx_settle(b) != DMX_OK) return nullptr;
     b->slab_exposed = true;       // the caller may write the slab behind the batch's back: the mirror is no longer served
+    // ... and neither are the constants known to be uniform any more: whatever field was asked for, the address is one into
+    // the slab, whose layout the header documents -- components 13..16 can be reached from it
+    b->uni_mass.poison(); b->uni_inertia.poison();
     return (char *)b->slab + (size_t)slab_ix(k_field_comp0[field] + component, 0) * b->rsize;
 }
 
@@ -410,6 +420,7 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
 {
     if (!b || !(h > 0) || nsteps < 0) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_note_capture(b);
     dmx_state_written(b);
     if (b->bp_enabled) return dmx_step_collide(b, h, nsteps);
     SETTLE(b);
@@ -466,6 +477,14 @@ extern "C" int dmxBatchSetSnapshotMode(dmxBatchID b, int mode)
     if (b->flipped) return DMX_EINVAL;          // not inside a chunk that has already advanced
     b->flip_armed = false;
     b->snapshot_mode = mode;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetElision(dmxBatchID b, int mask)
+{
+    if (!b || mask < 0 || mask > (DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS)) return DMX_EINVAL;
+    SETTLE(b);
+    b->elide = mask;
     return DMX_OK;
 }
 
@@ -611,6 +630,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_note_capture(b);
     dmx_state_written(b);
     return dmx_chunk_tick(b, h, check);
 }
@@ -618,6 +638,7 @@ extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_
 {
     if (!b || !(h > 0) || nticks < 0) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_note_capture(b);
     dmx_state_written(b);
     return dmx_chunk_ticks(b, h, nticks, check_first, check_last);
 }
@@ -677,6 +698,7 @@ extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
     if (!b || !(h > 0)) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
+    dmx_note_capture(b);
     dmx_state_written(b);
     return dmx_exact_tick(b, h);
 }
@@ -745,6 +767,7 @@ extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t 
     if (first % 64 != 0) return DMX_EINVAL;      // ranges start on a wave so per-wave diagnostics slots stay disjoint
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
+    dmx_note_capture(b);
     dmx_state_written(b);
     return b->precision == DMX_F32 ? step_t<float>(b, h, 1, first, count, reset_diag != 0)
                                    : step_t<double>(b, h, 1, first, count, reset_diag != 0);

@@ -14,6 +14,7 @@
 
 #include "../../include/dmx_batch.h"
 #include "dmx_internal.hpp"
+#include "dmx_uniform.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -93,6 +94,11 @@ struct dmxBatch {
     int nt = 0;                      // DMX_NT launch-tuning override (see StepParams)
     int oop = 0;                     // DMX_OOP=1: the plain (unchecked) loop writes every tick out of place, alternating slabs (experiment)
     int vec = 0;                     // DMX_VEC launch-tuning override (bodies per lane in integrate_free), 0 = default (1)
+    // integrate_free's removals (dmxBatchSetElision; DMX_ELIDE in the environment sets the default): bit 0 = store elision,
+    // bit 1 = uniform mass / inertia as kernel arguments.  The trackers follow every upload of the two fields (upload_t).
+    int elide = DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS;
+    dmx::UniformTracker<1> uni_mass; dmx::UniformTracker<3> uni_inertia;
+    bool capturing = false;          // the stream was being captured into a HIP graph at the last stepping call (dmx_note_capture)
     bool stepped_with_plane = false;
     // general island path (explicit contact joints)
     uint8_t *bflags = nullptr;                 // device, per-slot BF_* flags
@@ -173,6 +179,17 @@ struct dmxBatch {
     StepDiag *sm_diag = nullptr; int sm_diag_cur = 0;      // two device slots used alternately (each launch zeroes the next one's)
     bool last_small = false;                       // the last dmxBatchStepJoints tick left its diagnostics in sm_diag[sm_diag_cur]
 };
+// A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later
+// upload of another mass while eager ticks use the new one: launches recorded during a capture read the constants from the
+// slab.  Asked once per stepping call of the C ABI (the entry points that can reach integrate_free), and only while the
+// answer matters, not per tick: the exact ticks of small scenes are bound by host latency.
+inline void dmx_note_capture(dmxBatch *b)
+{
+    b->capturing = false;
+    if (!(b->elide & DMX_ELIDE_CONSTANTS) || !b->uni_mass.uniform || !b->uni_inertia.uniform) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    b->capturing = hipStreamIsCapturing(b->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
 // called by everything that changes body state in the slab other than the single-launch tick
 inline void dmx_state_written(dmxBatch *b) { b->sm_mirror_valid = false; }
 
@@ -254,6 +271,13 @@ template <class T> inline StepParams<T> dmx_make_params(dmxBatch *b, double h)
     P.vec = b->vec;
     P.min_waves = b->min_waves;
     P.nt = b->nt;
+    P.elide = b->elide;
+    // (not while the batch's stream is being captured into a HIP graph: dmx_note_capture)
+    P.uni = (b->uni_mass.uniform && b->uni_inertia.uniform && (b->elide & DMX_ELIDE_CONSTANTS) && !b->capturing) ? 1 : 0;
+    if (P.uni) {
+        P.uni_mass = (T)b->uni_mass.v[0];
+        P.uni_inertia = { (T)b->uni_inertia.v[0], (T)b->uni_inertia.v[1], (T)b->uni_inertia.v[2] };
+    }
     { static const int nf = [] { const char *e = getenv("DMX_HULL_FILTER"); return !e ? 0 : atoi(e) == 0 ? 1 : atoi(e) == 2 ? 2 : 0; }(); P.hull_nofilter = nf; }
     P.bp_check = 0;          // set by the collision-aware tick (dmx_general.cpp)
     P.ticks = 1;

@@ -10,7 +10,8 @@ namespace dmx {
 
 // Body slab layout: tiles of SLAB_TILE consecutive bodies; inside a tile the C_COUNT components are stored one
 // after another, SLAB_TILE reals each (array-of-structures-of-arrays).  A wavefront stepping 64 consecutive
-// bodies therefore reads and writes ONE contiguous run of memory (17 x 256 B in, 13 x 256 B out in f32)
+// bodies therefore reads and writes ONE contiguous run of memory (at most 17 x 256 B in, 13 x 256 B out in f32;
+// integrate_free leaves out uniform constants and the components an in-place launch did not change)
 // instead of 30 streams a whole component array apart: on MI355X that lifts the free-flight pass from
 // about 5.6 to about 7.1 TB/s at 1 Mi bodies (scripts/ubench_layout.hip, profiles/r01_layout_ubench.txt).
 // The slab is allocated for `stride` bodies = the body count rounded up to 256; pad bodies are valid,
@@ -128,6 +129,11 @@ template <class T> struct StepParams {
     // a launch enqueued before the host knows whether it should run (careful_tick's speculative tick): the fused kernels
     // return at once unless *gate != 0 (ExactCounts::spec_ok on the device).  Null: no question asked.
     const uint32_t *gate = nullptr;
+    // integrate_free, work the result does not need (dmxBatchSetElision): bit 0 = an in-place launch stores only the components
+    // some body of the wavefront changed; bit 1 = when every slot has the same mass and inertia (uni = 1; dmx_uniform.hpp
+    // keeps track) they travel as arguments, uni_mass / uni_inertia, and the kernel does not load them
+    int elide = 0, uni = 0;
+    T uni_mass = T(1); V3<T> uni_inertia = { T(1), T(1), T(1) };
 };
 // contact buffer of the static fused path: SC_MAXC contacts of SC_REALS reals per body, field f of contact k of body i at
 // sbuf[sc_ix(k, f, i)] -- tiles of 64 bodies, so a wavefront's access to one field of one contact is one contiguous run

@@ -12,8 +12,9 @@
 // A lane owns V consecutive bodies (V divides the tile).
 //
 // No MFMA: there is no dense contraction on this path.  integrate_free is
-// HBM-bound (30 reals per body-step); step_plane is VALU/latency bound
-// (20 SOR sweeps over <= 12 rows held in registers).
+// HBM-bound (at most 30 reals per body-step, 19 on a dropped unit-mass scene:
+// see the kernel's header); step_plane is VALU/latency bound (20 SOR sweeps
+// over <= 12 rows held in registers).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "dmx_internal.hpp"
@@ -54,28 +55,58 @@ __device__ __forceinline__ void stv_nt(T *base, int64_t stride, int comp, int64_
 }
 
 // ---------------------------------------------------------------------------------------------
-// integrate_free: contact-free tick (BASELINE config 2/4).  Algorithmic traffic per body-step:
+// integrate_free: contact-free tick (BASELINE config 2/4).  Algorithmic traffic per body-step, at most:
 // read 13 state + 4 constant reals, write 13 state reals = 30 reals (120 B f32 / 240 B f64).
+// OPT (StepParams::elide, dmxBatchSetElision) takes out what the result does not need:
+//   OPT_ELIDE  an IN-PLACE launch (So == S) stores component k of a wavefront's 64 bodies only if some lane's new
+//              value differs in its BITS from the one loaded (-0.0 -> +0.0 and NaN payloads count as changes): the
+//              store would have put back what is there.  One ballot and one scalar branch per component; a run that
+//              is stored is stored whole, for all 64 lanes.  An out-of-place launch (the first of a collision-proof
+//              chunk) stores all 13, as OPT = 0 does.
+//   OPT_UNI    mass and inertia are the same for every slot (dmx_uniform.hpp keeps track, host side): they arrive
+//              as kernel arguments (StepParams::uni_mass / uni_inertia) and components 13..16 are not loaded.
+// A dropped scene of unit-mass bodies under gravity along y (the reference's AddBody + dWorldSetGravity) then moves
+// 13 reals in and 6 out (pos.y, quat, lvel.y) = 19 per body-step; any other scene moves what it changes, up to the 30.
+// Same values into the same free_body_step either way: same bits.  OPT != 0 exists for V = 1 and the default launch
+// bound only; the DMX_VEC / DMX_MIN_WAVES tuning experiments run the OPT = 0 instantiations (all loads, all stores).
 // ---------------------------------------------------------------------------------------------
-template <class T, int V, bool EXT, int MINW, bool MULTI>
+enum : int { OPT_ELIDE = 1, OPT_UNI = 2 };
+template <class T> struct BitsOf;
+template <> struct BitsOf<float> { using type = uint32_t; };
+template <> struct BitsOf<double> { using type = uint64_t; };
+template <class T> __device__ __forceinline__ bool bits_differ(T a, T b)
+{
+    using U = typename BitsOf<T>::type;
+    return __builtin_bit_cast(U, a) != __builtin_bit_cast(U, b);
+}
+
+template <class T, int V, bool EXT, int MINW, bool MULTI, int OPT = 0>
 __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t stride, int64_t nvec,
                                                       StepParams<T> P)
 {
+    constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
+    constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
     // So = where the new state goes: S itself (in place) or the batch's other slab (the first launch of a
     // collision-proof chunk, which thereby leaves the chunk's start state behind as the rollback snapshot)
     if (P.gate != nullptr && *P.gate == 0u) return;
     const int nticks = MULTI ? P.ticks : 1;         // MULTI = false: the one-tick kernel, no loop
+    const bool in_place = ELIDE && So == S;         // wave-uniform: two kernel arguments
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nvec;
          t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = t * V;
         if (V == 1 && P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
-        Pack<T, V> c[C_SIDES];
+        Pack<T, V> c[NLOAD];
         if (P.nt & 2) {
 #pragma unroll
-            for (int k = 0; k < C_SIDES; k++) c[k] = ldv_nt<T, V>(S, stride, k, i);
+            for (int k = 0; k < NLOAD; k++) c[k] = ldv_nt<T, V>(S, stride, k, i);
         } else {
 #pragma unroll
-            for (int k = 0; k < C_SIDES; k++) c[k] = ldv<T, V>(S, stride, k, i);
+            for (int k = 0; k < NLOAD; k++) c[k] = ldv<T, V>(S, stride, k, i);
+        }
+        Pack<T, V> was[ELIDE ? C_MASS : 1];          // the state as loaded, to tell which components the launch changed
+        if constexpr (ELIDE) {
+#pragma unroll
+            for (int k = 0; k < C_MASS; k++) was[k] = c[k];
         }
         Pack<T, V> bx, bz, bs;
         if (P.bp_check) {
@@ -109,13 +140,16 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
                 Q4<T> q = { c[C_QUAT].v[b], c[C_QUAT + 1].v[b], c[C_QUAT + 2].v[b], c[C_QUAT + 3].v[b] };
                 V3<T> v = { c[C_LVEL].v[b], c[C_LVEL + 1].v[b], c[C_LVEL + 2].v[b] };
                 V3<T> w = { c[C_AVEL].v[b], c[C_AVEL + 1].v[b], c[C_AVEL + 2].v[b] };
-                const V3<T> Ib = { c[C_INERTIA].v[b], c[C_INERTIA + 1].v[b], c[C_INERTIA + 2].v[b] };
+                T mass;
+                V3<T> Ib;
+                if constexpr (UNI) { mass = P.uni_mass; Ib = P.uni_inertia; }
+                else { mass = c[C_MASS].v[b]; Ib = { c[C_INERTIA].v[b], c[C_INERTIA + 1].v[b], c[C_INERTIA + 2].v[b] }; }
                 V3<T> facc = { T(0), T(0), T(0) }, tacc = { T(0), T(0), T(0) };
                 if (EXT && s == 0) {                       // the accumulators act in the first tick and are cleared by it
                     facc = { f[0].v[b], f[1].v[b], f[2].v[b] };
                     tacc = { f[3].v[b], f[4].v[b], f[5].v[b] };
                 }
-                free_body_step(x, q, v, w, c[C_MASS].v[b], Ib, facc, tacc, P.g, P.h, P.gyro);
+                free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
                 if (s == nticks - 1) pack_boundary(P, i + b, x, q, v, w);
                 c[C_POS].v[b] = x.x; c[C_POS + 1].v[b] = x.y; c[C_POS + 2].v[b] = x.z;
                 c[C_QUAT].v[b] = q.w; c[C_QUAT + 1].v[b] = q.x; c[C_QUAT + 2].v[b] = q.y; c[C_QUAT + 3].v[b] = q.z;
@@ -123,12 +157,16 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
                 c[C_AVEL].v[b] = w.x; c[C_AVEL + 1].v[b] = w.y; c[C_AVEL + 2].v[b] = w.z;
             }
         }
-        if (P.nt & 1) {
 #pragma unroll
-            for (int k = 0; k < C_MASS; k++) stv_nt<T, V>(So, stride, k, i, c[k]);
-        } else {
+        for (int k = 0; k < C_MASS; k++) {
+            if constexpr (ELIDE) if (in_place) {
+                bool changed = false;
 #pragma unroll
-            for (int k = 0; k < C_MASS; k++) stv<T, V>(So, stride, k, i, c[k]);
+                for (int b = 0; b < V; b++) changed |= bits_differ(c[k].v[b], was[k].v[b]);
+                if (__ballot(changed) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
+            }
+            if (P.nt & 1) stv_nt<T, V>(So, stride, k, i, c[k]);
+            else          stv<T, V>(So, stride, k, i, c[k]);
         }
         if (EXT) {
             Pack<T, V> z;
@@ -697,9 +735,10 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         }
     } else if (!P.plane_on) {
         constexpr int VMAX = 16 / sizeof(T);
-        // default: one body per lane.  On the tiled slab a wave's 17 loads already cover one contiguous run, so wider
-        // per-lane loads buy nothing, and V = 1 keeps the kernel at 67 VGPRs (7 waves/SIMD): measured 21.1 / 22.2 / 22.4 us
-        // per tick for V = 1 / 2 / 4 at 1 Mi f32 bodies (profiles/r01_integrate_free_tiled_sweep.txt).
+        // default: one body per lane.  On the tiled slab a wave's loads (17, or 13 when the constants are arguments) already
+        // cover one contiguous run, so wider per-lane loads buy nothing, and V = 1 keeps the f32 kernel at 7 waves/SIMD (71 VGPRs
+        // with every load and store, 72 in the default instantiation below): measured, on the kernel moving all 30 reals,
+        // 21.1 / 22.2 / 22.4 us per tick for V = 1 / 2 / 4 at 1 Mi f32 bodies (profiles/r01_integrate_free_tiled_sweep.txt).
         const int VDEF = 1;
         const int V = P.skip != nullptr ? 1 : (P.vec == 1 || P.vec == 2 || P.vec == VMAX) ? P.vec : VDEF;
         const int64_t nvec = (n + V - 1) / V;     // pad bodies up to `stride` are valid memory
@@ -720,16 +759,30 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
             hipLaunchKernelGGL((integrate_free_wide<T>), dim3(blocks_for(ntiles, 4)), dim3(256), 0, st, S, So, ntiles, P);
             return hipGetLastError();
         }
-#define DMX_LAUNCH_FREE(VV, MW)                                                                                      \
+#define DMX_LAUNCH_FREE(VV, MW, OO, MWX)                                                                               \
     do {                                                                                                             \
-        if (P.ticks > 1) hipLaunchKernelGGL((integrate_free<T, VV, false, MW, true>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);   \
-        else if (ext) hipLaunchKernelGGL((integrate_free<T, VV, true, MW, false>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);  \
-        else     hipLaunchKernelGGL((integrate_free<T, VV, false, MW, false>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P); \
+        if (P.ticks > 1) hipLaunchKernelGGL((integrate_free<T, VV, false, MWX, true, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);   \
+        else if (ext) hipLaunchKernelGGL((integrate_free<T, VV, true, MWX, false, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);  \
+        else     hipLaunchKernelGGL((integrate_free<T, VV, false, MW, false, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P); \
     } while (0)
         const int mw = P.min_waves;   // launch tuning: minimum waves per SIMD the register allocator must leave room for
-        if (V == 1) { if (mw == 8) DMX_LAUNCH_FREE(1, 8); else if (mw == 6) DMX_LAUNCH_FREE(1, 6); else DMX_LAUNCH_FREE(1, 1); }
-        else if (V == 2) { if (mw == 4) DMX_LAUNCH_FREE(2, 4); else if (mw == 5) DMX_LAUNCH_FREE(2, 5); else if (mw == 6) DMX_LAUNCH_FREE(2, 6); else DMX_LAUNCH_FREE(2, 1); }
-        else { if (mw == 4) DMX_LAUNCH_FREE(VMAX, 4); else if (mw == 3) DMX_LAUNCH_FREE(VMAX, 3); else DMX_LAUNCH_FREE(VMAX, 1); }
+        // what the result does not need (the kernel's header): store elision, and constants as arguments when the batch's are uniform.
+        // The constants' scalars cost the f32 one-tick kernel three registers (71 -> 74 VGPRs = 6 waves per SIMD): a launch bound
+        // of 7 waves (MWU) makes the allocator fit them into the 72 that 7 waves allow, without scratch; the kernels with force
+        // accumulators or many ticks would spill under that bound and keep the default one (MWX).  The many-ticks-per-launch
+        // kernel (VALU-bound, one store per `ticks` ticks) keeps its unconditional stores: the copy of the loaded state would
+        // cost it a wave per SIMD (84 -> 97 VGPRs) for a store it rarely issues, while the constants alone free registers
+        // (84 -> 79); a build with the elision in it measured the same within the spread at 32 ticks per launch
+        // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
+        constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
+        int opt = (V == 1 && mw != 8 && mw != 6) ? ((P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0)) : 0;
+        if (P.ticks > 1) opt &= OPT_UNI;
+        if (opt == 3) DMX_LAUNCH_FREE(1, MWU, 3, 1);
+        else if (opt == 2) DMX_LAUNCH_FREE(1, MWU, 2, 1);
+        else if (opt == 1) DMX_LAUNCH_FREE(1, 1, 1, 1);
+        else if (V == 1) { if (mw == 8) DMX_LAUNCH_FREE(1, 8, 0, 8); else if (mw == 6) DMX_LAUNCH_FREE(1, 6, 0, 6); else DMX_LAUNCH_FREE(1, 1, 0, 1); }
+        else if (V == 2) { if (mw == 4) DMX_LAUNCH_FREE(2, 4, 0, 4); else if (mw == 5) DMX_LAUNCH_FREE(2, 5, 0, 5); else if (mw == 6) DMX_LAUNCH_FREE(2, 6, 0, 6); else DMX_LAUNCH_FREE(2, 1, 0, 1); }
+        else { if (mw == 4) DMX_LAUNCH_FREE(VMAX, 4, 0, 4); else if (mw == 3) DMX_LAUNCH_FREE(VMAX, 3, 0, 3); else DMX_LAUNCH_FREE(VMAX, 1, 0, 1); }
 #undef DMX_LAUNCH_FREE
     } else {
         const unsigned grid = blocks_for(n, 256);
@@ -865,6 +918,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
     auto touch = [&](const void *k) { const hipError_t r = hipFuncGetAttributes(&a, k); if (r != hipSuccess) e = r; };
     if (real_bytes == 4) {
         touch((const void *)&integrate_free<float, 1, false, 1, false>);
+        touch((const void *)&integrate_free<float, 1, false, 7, false, 3>);
         touch((const void *)&step_plane<float, false, 1, 4>);
         touch((const void *)&step_plane<float, false, 2, 4>);
         touch((const void *)&step_contacts<float, false, 1, 8, true>);
@@ -872,6 +926,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
         touch((const void *)&copy_components<float>);
     } else {
         touch((const void *)&integrate_free<double, 1, false, 1, false>);
+        touch((const void *)&integrate_free<double, 1, false, 1, false, 3>);
         touch((const void *)&step_plane<double, false, 1, 4>);
         touch((const void *)&step_plane<double, false, 2, 4>);
         touch((const void *)&step_contacts<double, false, 1, 8, true>);
