@@ -261,6 +261,37 @@ int dmxBatchFindPairs(dmxBatchID b, const int32_t **pairs, int64_t *n_pairs, con
  * (rl-ode-physics_amd/shard.py) before the exact tick, which would otherwise return DMX_ECROSS.  At most 256 are listed. */
 int dmxBatchCrossPairs(dmxBatchID b, const int32_t **pairs, int64_t *n_pairs);
 
+/* ---- ray casts: the scene query ODE answers with a ray geom (dCreateRay + dCollide), in batch form.  Each ray is the segment
+ * origin + t * dir, 0 <= t <= length, dir normalised in the batch's precision (7 reals: origin3 dir3 length); it reports the
+ * FIRST geom whose surface it crosses: a body slot, the ground plane (dmxBatchSetPlane) or a static box (dmxBatchSetStaticBoxes).
+ *   ids[i]   the body's slot (>= 0), DMX_RAY_MISS, DMX_RAY_PLANE, or DMX_RAY_STATIC_BOX(k) = -3 - k for static box k
+ *   hits[i]  7 reals in dContactGeom's order: pos3, normal3, depth = t.  The normal is the surface's outward unit normal at the
+ *            hit, negated when the origin lies inside the solid: dot(normal, dir) <= 0 (what ODE's ray colliders return).  A
+ *            miss gives the segment's end point, a zero normal and depth = length; a ray whose direction has zero or non-finite
+ *            norm, or whose length is non-finite or <= 0, gives DMX_RAY_MISS and seven zeros.
+ * Equal t: the plane wins, then static boxes in order, then bodies by slot -- the answer never depends on the search order.
+ * Visible: every slot of [0, body count), ghost slots included, whose class is not DMX_GEOM_NONE, whose flags have
+ * DMX_BODY_ALIVE and whose class bit is in `mask`.  Convex bodies are seen through the hull's faces
+ * (dmxBatchSetConvexHullFaces): without faces a convex body is invisible to rays, as it collides with the ground plane only.
+ * Rays see the state after every tick enqueued so far: a cast first settles the chunk dmxBatchStep may have left open, like every
+ * call that observes the batch.  Beyond that it changes nothing a later tick can tell: the same states with and without casts
+ * between the ticks, and the same statistics as with a dmxBatchSynchronize in each cast's place.
+ * dmxBatchRayCast takes and fills host arrays and returns when they are filled.  dmxBatchRayCastDevice takes device pointers
+ * and is enqueued on the batch's stream; it waits for the device only when the column grid the rays walk has to be rebuilt,
+ * which happens at the first cast after the state, the extents, the classes or the flags changed (many casts between two
+ * ticks share one build; a batch whose slab address was handed out by dmxBatchDevicePtr rebuilds at every cast).
+ * Three forms of the same computation, same results bit for bit: a lane per ray walking the hashed (x,z) column grid (above
+ * 4 096 rays), a wavefront per ray (up to 4 096 rays: one pick ray into a crowded pen), and a brute-force form that tests
+ * every slot (never chosen automatically; the cross-check).  dmxBatchSetRayForm, or DMX_RAY_FORM=lane|wave|brute in the
+ * environment (the setter wins), forces one. */
+enum { DMX_RAY_MISS = -1, DMX_RAY_PLANE = -2 };
+#define DMX_RAY_STATIC_BOX(k) (-3 - (k))
+enum { DMX_RAY_SPHERES = 1, DMX_RAY_BOXES = 2, DMX_RAY_CONVEX = 4, DMX_RAY_STATIC = 8, DMX_RAY_PLANE_BIT = 16, DMX_RAY_ALL = 31 };
+enum { DMX_RAY_FORM_AUTO = 0, DMX_RAY_FORM_LANE = 1, DMX_RAY_FORM_WAVE = 2, DMX_RAY_FORM_BRUTE = 3 };
+int dmxBatchRayCast(dmxBatchID b, int64_t n_rays, const void *rays_aos, int32_t *ids, void *hits_aos, uint32_t mask);
+int dmxBatchRayCastDevice(dmxBatchID b, int64_t n_rays, const void *rays_dev, int32_t *ids_dev, void *hits_dev, uint32_t mask);
+int dmxBatchSetRayForm(dmxBatchID b, int form);
+
 /* ---- explicit contact joints: the callback form of the tick.  The reference's near callback makes one
  * dJointCreateContact + dJointAttach per contact (main.c:683-692) and then calls dWorldStep (main.c:213);
  * this entry takes the whole tick's contact joints at once, groups them into dynamics islands, and steps

@@ -86,7 +86,7 @@ typedef struct dMass {
     dMatrix3 I;
 } dMass;
 
-enum { dSphereClass = 0, dBoxClass = 1, dPlaneClass = 4 };
+enum { dSphereClass = 0, dBoxClass = 1, dPlaneClass = 4, dRayClass = 5 };
 
 /* ---- library lifecycle ---------------------------------------------------- */
 void dInitODE(void);                                             /* main.c:94  */
@@ -169,6 +169,19 @@ void dGeomPlaneGetParams(dGeomID plane, dVector4 result);
 
 /* flags: low 16 bits = max contacts; skip = byte stride between dContactGeoms (main.c:678) */
 int dCollide(dGeomID o1, dGeomID o2, int flags, dContactGeom *contact, int skip);
+
+/* Rays: a bounded slice of ODE's ray geom.  dCreateRay supports space == 0 only -- a ray here does not take part in
+ * dSpaceCollide (no near callback is ever called with one), so putting it into a space would promise what is not there: a
+ * non-null space prints to stderr and returns 0.  The ray starts at its position and runs along the normalised direction for
+ * `length`; dCollide(ray, g) and dCollide(g, ray) against a box, a sphere or a plane return at most one contact, g1 = the ray,
+ * whichever order the geoms were given in: pos = the first crossing of g's surface, depth = its distance from the start, normal
+ * = the surface's outward unit normal there, negated when the start lies inside g (what ODE's ray colliders return).  Runs
+ * on the host, through the same primitives as dmxBatchRayCast (include/dmx_batch.h), the batch form of the query. */
+dGeomID dCreateRay(dSpaceID space, dReal length);
+void dGeomRaySet(dGeomID ray, dReal px, dReal py, dReal pz, dReal dx, dReal dy, dReal dz);
+void dGeomRayGet(dGeomID ray, dVector3 start, dVector3 dir);
+void dGeomRaySetLength(dGeomID ray, dReal length);
+dReal dGeomRayGetLength(dGeomID ray);
 
 /* ---- contact joints ------------------------------------------------------- */
 dJointGroupID dJointGroupCreate(int max_size);                   /* main.c:98  */

@@ -25,6 +25,7 @@ BATCH_SYMBOLS = [
     "dmxBatchChunkCommit", "dmxBatchChunkRollback", "dmxBatchExactTick", "dmxBatchRefreshGhostsOnStream", "dmxBatchSetConvexHull", "dmxBatchChunkTicks", "dmxBatchSetTicksPerLaunch",
     "dmxBatchSetSnapshotMode", "dmxBatchSetStaticBoxes", "dmxBatchSetStepper", "dmxBatchSetConvexHullFaces",
     "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision",
+    "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -127,5 +128,8 @@ def load():
     sig("dmxBatchFindPairs", I, P, C.POINTER(P), C.POINTER(L), C.POINTER(P), C.POINTER(L))
     sig("dmxBatchCrossPairs", I, P, C.POINTER(P), C.POINTER(L))
     sig("dmxBatchSetRowOrder", I, P, I, C.c_uint32)
+    sig("dmxBatchRayCast", I, P, L, P, P, P, C.c_uint32)
+    sig("dmxBatchRayCastDevice", I, P, L, P, P, P, C.c_uint32)
+    sig("dmxBatchSetRayForm", I, P, I)
     _lib = lib
     return lib

@@ -35,6 +35,10 @@ LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", 
 # that path, step_joints ticks on the general path, then one count per reason a tick was not eligible
 SMALL_TICK_OFF, SMALL_TICK_AUTO = 0, 1
 SMALL_TICK_STATS = ("small", "general", "mode", "row_order", "subset", "bodies", "islands", "sor_rows", "lds_fit")
+# ray casts (dmxBatchRayCast): result ids below zero, the visibility mask's bits, the forms
+RAY_MISS, RAY_PLANE = -1, -2           # static box k: -3 - k
+RAY_SPHERES, RAY_BOXES, RAY_CONVEX, RAY_STATIC, RAY_PLANE_BIT, RAY_ALL = 1, 2, 4, 8, 16, 31
+RAY_FORM_AUTO, RAY_FORM_LANE, RAY_FORM_WAVE, RAY_FORM_BRUTE = 0, 1, 2, 3
 
 
 class DmxError(RuntimeError):
@@ -305,6 +309,31 @@ class BatchWorld:
         _check(self.lib.dmxBatchCrossPairs(self.h, C.byref(cp), C.byref(nc)), "dmxBatchCrossPairs")
         grab = lambda p, n: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=(n,)).copy() if n else np.zeros(0, np.int32)
         return (grab(pp, 2 * npairs.value).reshape(-1, 2), grab(ip, ninv.value), grab(cp, 2 * nc.value).reshape(-1, 2))
+
+    # -- ray casts (include/dmx_batch.h) ----------------------------------------------------------------------------
+    def ray_cast(self, origins, dirs, lengths, mask=RAY_ALL):
+        """n rays (origins n x 3, dirs n x 3, lengths n) -> (ids int32 [n], hits [n, 7] = pos3 normal3 depth): per ray the first
+        geom its segment crosses -- a body slot, RAY_PLANE, -3 - k for static box k, or RAY_MISS"""
+        o = np.asarray(origins, dtype=self.dtype).reshape(-1, 3)
+        n = o.shape[0]
+        rays = np.empty((n, 7), self.dtype)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = np.asarray(dirs, dtype=self.dtype).reshape(n, 3)
+        rays[:, 6] = np.broadcast_to(np.asarray(lengths, dtype=self.dtype), (n,))
+        ids = np.empty(n, np.int32)
+        hits = np.empty((n, 7), self.dtype)
+        _check(self.lib.dmxBatchRayCast(self.h, n, rays.ctypes.data if n else None, ids.ctypes.data if n else None,
+                                        hits.ctypes.data if n else None, int(mask)), "dmxBatchRayCast")
+        return ids, hits
+
+    def ray_cast_device(self, rays_ptr, n, ids_ptr, hits_ptr, mask=RAY_ALL):
+        """the same on device memory (n x 7 reals in, n int32 and n x 7 reals out; e.g. torch tensors' data_ptr()), enqueued on
+        the batch's stream"""
+        _check(self.lib.dmxBatchRayCastDevice(self.h, int(n), rays_ptr, ids_ptr, hits_ptr, int(mask)), "dmxBatchRayCastDevice")
+
+    def set_ray_form(self, form):
+        """RAY_FORM_AUTO (default: by the ray count) / RAY_FORM_LANE / RAY_FORM_WAVE / RAY_FORM_BRUTE; same results either way"""
+        _check(self.lib.dmxBatchSetRayForm(self.h, int(form)), "dmxBatchSetRayForm")
 
     def set_active_count(self, n_active):
         _check(self.lib.dmxBatchSetActiveCount(self.h, n_active), "dmxBatchSetActiveCount")

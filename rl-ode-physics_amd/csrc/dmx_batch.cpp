@@ -105,6 +105,7 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
             const int rb = b->precision == DMX_F32 ? 4 : 8;
             (void)dmx::dmx_touch_kernels(rb); (void)dmx::dmx_touch_islands(rb); (void)dmx::dmx_touch_broadphase(rb);
             (void)dmx::dmx_touch_narrow(rb); (void)dmx::dmx_touch_exact(rb); (void)dmx::dmx_touch_small(rb);
+            (void)dmx::dmx_touch_raycast(rb);
         }
     }
     if (const char *v = getenv("DMX_LAZY_CHUNKS")) b->lazy_chunks = atoi(v) != 0;
@@ -187,7 +188,8 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
                                 &b->jd_lcp_int, &b->jd_order })
         if (d->p) (void)hipFree(d->p);
     for (dmxBatch::DevBuf *d : { &b->bp_count, &b->bp_items, &b->bp_flags, &b->bp_inpair, &b->bp_snapshot, &b->hull, &b->cbuf, &b->ccount,
-                                &b->ex_arena, &b->ex_body, &b->ex_last, &b->ex_aabb, &b->sbox, &b->hull_planes })
+                                &b->ex_arena, &b->ex_body, &b->ex_last, &b->ex_aabb, &b->sbox, &b->hull_planes, &b->rc_count, &b->rc_items, &b->rc_misc,
+                                &b->rc_rays, &b->rc_ids, &b->rc_hits })
         if (d->p) (void)hipFree(d->p);
     if (b->bp_flags_host) (void)hipHostFree(b->bp_flags_host);
     if (b->ex_counts_host) (void)hipHostFree(b->ex_counts_host);
@@ -349,6 +351,7 @@ extern "C" int dmxBatchUploadGeomType(dmxBatchID b, const uint8_t *types, int64_
         HIP_TRY(hipMemsetAsync((int *)b->scount.p + first, 0, (size_t)count * sizeof(int), b->stream));
     b->has_simple = b->n_simple > 0;
     b->bp_rmax = 0; b->bp_valid = false;
+    b->state_version++;         // what rays can see has changed
     HIP_TRY(hipStreamSynchronize(b->stream));
     return DMX_OK;
 }
@@ -360,6 +363,7 @@ extern "C" int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
     for (int64_t i = 0; i < count; i++) b->h_bflags[(size_t)(first + i)] = flags[i];
+    b->state_version++;         // what rays can see has changed
     HIP_TRY(hipMemcpyAsync(b->bflags + first, b->h_bflags.data() + first, (size_t)count, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return DMX_OK;
@@ -712,6 +716,42 @@ extern "C" int dmxBatchFindPairs(dmxBatchID b, const int32_t **pairs, int64_t *n
     if (rc != DMX_OK) return rc;
     *pairs = b->fp_pairs.data(); *n_pairs = (int64_t)(b->fp_pairs.size() / 2);
     *involved = b->fp_inv.data(); *n_involved = (int64_t)b->fp_inv.size();
+    return DMX_OK;
+}
+
+// ---- ray casts (dmx_general.cpp "ray casts", dmx_raycast.hip) -----------------------------------------------------------------
+extern "C" int dmxBatchRayCastDevice(dmxBatchID b, int64_t n_rays, const void *rays_dev, int32_t *ids_dev, void *hits_dev, uint32_t mask)
+{
+    if (!b || n_rays < 0 || (n_rays > 0 && (!rays_dev || !ids_dev || !hits_dev))) return DMX_EINVAL;
+    SETTLE(b);
+    if (n_rays == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    return dmx_ray_cast(b, n_rays, rays_dev, ids_dev, hits_dev, mask);
+}
+
+extern "C" int dmxBatchRayCast(dmxBatchID b, int64_t n_rays, const void *rays_aos, int32_t *ids, void *hits_aos, uint32_t mask)
+{
+    if (!b || n_rays < 0 || (n_rays > 0 && (!rays_aos || !ids || !hits_aos))) return DMX_EINVAL;
+    SETTLE(b);
+    if (n_rays == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t rbytes = (size_t)n_rays * 7 * b->rsize, ibytes = (size_t)n_rays * sizeof(int32_t);
+    int rc;
+    if ((rc = dmx_ensure_dev(b->rc_rays, rbytes)) != DMX_OK || (rc = dmx_ensure_dev(b->rc_hits, rbytes)) != DMX_OK ||
+        (rc = dmx_ensure_dev(b->rc_ids, ibytes)) != DMX_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(b->rc_rays.p, rays_aos, rbytes, hipMemcpyHostToDevice, b->stream));
+    if ((rc = dmx_ray_cast(b, n_rays, b->rc_rays.p, (int32_t *)b->rc_ids.p, b->rc_hits.p, mask)) != DMX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ids, b->rc_ids.p, ibytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(hits_aos, b->rc_hits.p, rbytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetRayForm(dmxBatchID b, int form)
+{
+    if (!b || form < DMX_RAY_FORM_AUTO || form > DMX_RAY_FORM_BRUTE) return DMX_EINVAL;
+    b->ray_form = form;
     return DMX_OK;
 }
 

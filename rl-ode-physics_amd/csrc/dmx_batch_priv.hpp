@@ -178,6 +178,17 @@ struct dmxBatch {
     bool slab_exposed = false;                     // dmxBatchDevicePtr handed the slab out: writes the batch cannot see -- the mirror is never served
     StepDiag *sm_diag = nullptr; int sm_diag_cur = 0;      // two device slots used alternately (each launch zeroes the next one's)
     bool last_small = false;                       // the last dmxBatchStepJoints tick left its diagnostics in sm_diag[sm_diag_cur]
+    // ray casts (dmx_general.cpp "ray casts", dmx_raycast.hip).  The column grid rays walk is a table of the ray cast's own --
+    // same size and hashing as the broadphase's, its own bucket capacity and torus / scrambled choice -- so that a cast leaves
+    // nothing behind that a tick could meet: not a grown bucket, not a cleared flag.  It is rebuilt when state_version has
+    // moved on from the build's (every writer of poses, extents, classes or flags bumps it), or always once the slab's address
+    // has been handed out (slab_exposed).
+    uint64_t state_version = 1, rc_version = 0;
+    int rc_cap = 8, rc_xbits = -1;                 // -1: not chosen yet
+    double rc_rmax = 0;                            // the bounding radius the built grid's cell width came from
+    int ray_form = 0;                              // dmxBatchSetRayForm; DMX_RAY_FORM in the environment sets the default
+    DevBuf rc_count, rc_items, rc_misc;            // rc_misc: BPF_COUNT flag words, then the rectangle's four keys at byte 64
+    DevBuf rc_rays, rc_ids, rc_hits;               // device staging of dmxBatchRayCast's host arrays
 };
 // A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later
 // upload of another mass while eager ticks use the new one: launches recorded during a capture read the constants from the
@@ -191,7 +202,7 @@ inline void dmx_note_capture(dmxBatch *b)
     b->capturing = hipStreamIsCapturing(b->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 // called by everything that changes body state in the slab other than the single-launch tick
-inline void dmx_state_written(dmxBatch *b) { b->sm_mirror_valid = false; }
+inline void dmx_state_written(dmxBatch *b) { b->sm_mirror_valid = false; b->state_version++; }
 
 int dmx_ensure_dev(dmxBatch::DevBuf &d, size_t bytes);
 // do the fused kernels make contacts (and so leave contact diagnostics behind)?  The ground plane, or static boxes on the fused path
@@ -240,6 +251,8 @@ int dmx_chunk_commit(dmxBatch *b, int ticks, int refresh_zones);
 int dmx_chunk_rollback(dmxBatch *b);
 int dmx_exact_tick(dmxBatch *b, double h);
 int dmx_find_pairs(dmxBatch *b);           // -> b->fp_pairs / b->fp_inv
+// rays_dev / ids_dev / hits_dev on the device; enqueued on the batch's stream (synchronises only to build the grid)
+int dmx_ray_cast(dmxBatch *b, int64_t n_rays, const void *rays_dev, int32_t *ids_dev, void *hits_dev, uint32_t mask);
 
 
 template <class T> inline void dmx_normalize_plane(const double in[4], T out[4])

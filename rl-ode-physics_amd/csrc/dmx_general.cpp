@@ -920,7 +920,103 @@ template <class T> int find_pairs_t(dmxBatch *b)
     HIP_TRY(hipStreamSynchronize(b->stream));
     return DMX_OK;
 }
+
+// ---- ray casts (dmxBatchRayCast; kernels in dmx_raycast.hip) ----------------------------------------------------------------------
+// The grid rays walk: the broadphase's hashing, bucket layout and insert kernel over a table of the ray cast's own (see
+// dmxBatch::rc_*), filled from the current slab -- every slot of [0, n), ghost slots included -- and kept until the state,
+// the extents, the classes or the flags change.  The build is the one place a cast waits for the device: it needs the
+// bucket-overflow flag.  bp_insert rewrites C_BPR with the value it has whenever zones exist; both slabs get it.
+static_assert(DMX_RAY_MISS == DMX_RAYID_MISS && DMX_RAY_PLANE == DMX_RAYID_PLANE, "ray result ids");
+static_assert((DMX_RAY_SPHERES | DMX_RAY_BOXES | DMX_RAY_CONVEX) == (int)DMX_RAYMASK_BODIES && DMX_RAY_SPHERES == 1 << (GEOM_SPHERE - 1) &&
+              DMX_RAY_BOXES == 1 << (GEOM_BOX - 1) && DMX_RAY_CONVEX == 1 << (GEOM_CONVEX - 1) &&
+              DMX_RAY_STATIC == (int)DMX_RAYMASK_STATIC && DMX_RAY_PLANE_BIT == (int)DMX_RAYMASK_PLANE, "ray mask bits");
+static_assert(DMX_RAY_FORM_AUTO == RAY_FORM_AUTO && DMX_RAY_FORM_LANE == RAY_FORM_LANE && DMX_RAY_FORM_WAVE == RAY_FORM_WAVE &&
+              DMX_RAY_FORM_BRUTE == RAY_FORM_BRUTE, "ray forms");
+constexpr size_t kRayRectOffset = 64;          // rc_misc: flags, then the rectangle
+constexpr int64_t kRayWaveMax = 4096;          // up to this many rays, a wavefront each: fewer waves than the chip has slots for
+
+template <class T> int ray_build(dmxBatch *b)
+{
+    double r = 0;
+    for (int64_t i = 0; i < b->n; i++) {
+        const double *s = &b->h_sides[(size_t)3 * i];
+        const uint8_t g = b->h_gtype[(size_t)i];
+        r = std::max(r, (g == GEOM_SPHERE || g == GEOM_CONVEX) ? s[0] : g == GEOM_BOX ? 0.5 * std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]) : 0.0);
+    }
+    b->rc_rmax = r > 0 ? r : 1.0;
+    uint32_t tbl = 1024;
+    while ((int64_t)tbl < 2 * b->n) tbl <<= 1;
+    if (b->rc_xbits < 0) {
+        int bits = 0;
+        while ((1u << bits) < tbl) bits++;
+        b->rc_xbits = (bits + 1) / 2;
+        b->rc_cap = kBucketCap;
+    }
+    int rc;
+    if ((rc = dmx_ensure_dev(b->rc_count, (size_t)tbl * sizeof(uint32_t))) != DMX_OK) return rc;
+    if ((rc = dmx_ensure_dev(b->rc_misc, 128)) != DMX_OK) return rc;
+    for (;;) {
+        if ((rc = dmx_ensure_dev(b->rc_items, (size_t)tbl * (size_t)b->rc_cap * sizeof(int32_t))) != DMX_OK) return rc;
+        GridParams<T> G = grid_of<T>(b);
+        G.r_max = (T)b->rc_rmax; G.cell = (T)(2.0 * kSkin * b->rc_rmax); G.inv_cell = T(1) / G.cell;
+        G.mask = tbl - 1; G.xbits = b->rc_xbits; G.cap = b->rc_cap;
+        G.count = (uint32_t *)b->rc_count.p; G.items = (int32_t *)b->rc_items.p; G.flags = (uint32_t *)b->rc_misc.p;
+        G.rec = nullptr;
+        HIP_TRY(launch_bp_clear(G.count, (size_t)tbl, G.flags, nullptr, 0, nullptr, 0, b->stream));
+        HIP_TRY(launch_bp_insert<T>((T *)b->slab, b->gtype, b->stride, b->n, G, b->stream));
+        uint32_t overflow = 0;
+        HIP_TRY(hipMemcpyAsync(&overflow, G.flags + BPF_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if (!overflow) break;
+        if (b->rc_xbits > 0) { b->rc_xbits = 0; continue; }           // as grow_buckets: scramble first, then double the buckets
+        if (b->rc_cap >= 1024) {
+            fprintf(stderr, "libode_mi355: ray cast bucket overflow (> %d bodies in one (x,z) column)\n", b->rc_cap);
+            return DMX_ECAPACITY;
+        }
+        b->rc_cap *= 2;
+    }
+    HIP_TRY(launch_ray_bounds<T>((const T *)b->slab, b->gtype, b->bflags, b->n,
+                                 (unsigned long long *)((char *)b->rc_misc.p + kRayRectOffset), b->stream));
+    HIP_TRY(launch_copy_components<T>((const T *)b->slab, (T *)b->slab_alt, C_BPR, 1, 0, b->n, b->stream));
+    b->rc_version = b->state_version;
+    return DMX_OK;
+}
+
+template <class T> int ray_cast_t(dmxBatch *b, int64_t n_rays, const void *rays, int32_t *ids, void *hits, uint32_t mask)
+{
+    static const int env_form = [] {
+        const char *e = getenv("DMX_RAY_FORM");
+        return !e ? RAY_FORM_AUTO : !strcmp(e, "lane") ? RAY_FORM_LANE : !strcmp(e, "wave") ? RAY_FORM_WAVE : !strcmp(e, "brute") ? RAY_FORM_BRUTE : RAY_FORM_AUTO;
+    }();
+    int form = b->ray_form != RAY_FORM_AUTO ? b->ray_form : env_form;
+    if (form == RAY_FORM_AUTO) form = n_rays <= kRayWaveMax ? RAY_FORM_WAVE : RAY_FORM_LANE;      // by the ray count alone
+    int rc;
+    if (form != RAY_FORM_BRUTE && (b->rc_version != b->state_version || b->slab_exposed || !b->rc_count.p) && (rc = ray_build<T>(b)) != DMX_OK)
+        return rc;
+    RaySceneParams<T> Sc;
+    Sc.S = (const T *)b->slab; Sc.gtype = b->gtype; Sc.bflags = b->bflags; Sc.n = b->n;
+    Sc.hull_planes = (const T *)b->hull_planes.p; Sc.hull_nf = b->hull_planes.p ? b->hull_nf : 0;
+    Sc.sbox = (const T *)b->sbox.p; Sc.n_static = b->sbox.p ? b->n_static : 0;
+    T pl[4];
+    dmx_normalize_plane<T>(b->plane, pl);
+    Sc.plane_on = b->plane_on; Sc.pn = { pl[0], pl[1], pl[2] }; Sc.pd = pl[3];
+    Sc.mask = mask;
+    Sc.cell = (T)(2.0 * kSkin * b->rc_rmax); Sc.inv_cell = T(1) / Sc.cell;
+    uint32_t tbl = 1024;
+    while ((int64_t)tbl < 2 * b->n) tbl <<= 1;
+    Sc.gmask = tbl - 1; Sc.xbits = b->rc_xbits > 0 ? b->rc_xbits : 0; Sc.cap = b->rc_cap;
+    Sc.count = (const uint32_t *)b->rc_count.p; Sc.items = (const int32_t *)b->rc_items.p;
+    Sc.rect = (const unsigned long long *)((const char *)b->rc_misc.p + kRayRectOffset);
+    HIP_TRY(launch_ray_cast<T>(form, Sc, n_rays, (const T *)rays, ids, (T *)hits, b->stream));
+    return DMX_OK;
+}
 }  // namespace
+
+int dmx_ray_cast(dmxBatch *b, int64_t n_rays, const void *rays_dev, int32_t *ids_dev, void *hits_dev, uint32_t mask)
+{
+    return b->precision == DMX_F32 ? ray_cast_t<float>(b, n_rays, rays_dev, ids_dev, hits_dev, mask)
+                                   : ray_cast_t<double>(b, n_rays, rays_dev, ids_dev, hits_dev, mask);
+}
 
 int dmx_find_pairs(dmxBatch *b)
 {

@@ -11,7 +11,7 @@ namespace dmx {
 // adjacent in space looks up adjacent entries (a handful of cache lines instead of one per lookup); cells a whole
 // torus period apart share a bucket, which callers tell apart by the bodies' true cells.  Scenes far longer than
 // wide wrap too often for that; they use the scrambled form (xbits = 0).
-__device__ __forceinline__ uint32_t cell_hash(int ix, int iz, uint32_t mask, int xbits)
+__host__ __device__ __forceinline__ uint32_t cell_hash(int ix, int iz, uint32_t mask, int xbits)
 {
     if (xbits > 0) return ((((uint32_t)iz) << xbits) | ((uint32_t)ix & ((1u << xbits) - 1u))) & mask;
     return ((uint32_t)ix * 73856093u ^ (uint32_t)iz * 19349663u) & mask;

@@ -183,6 +183,25 @@ template <class T> struct GridParams {
     uint32_t class_pairs;          // which geometry classes collide with which (classes_collide)
 };
 
+// ray casts (dmx_raycast.hip).  Result ids below zero, the visibility mask's bits (bit gt - 1 for a body of class gt) and the forms
+// are the values of include/dmx_batch.h (DMX_RAY_*); dmx_general.cpp holds the static_asserts.
+enum : int { DMX_RAYID_MISS = -1, DMX_RAYID_PLANE = -2 };       // static box k: -3 - k
+enum : uint32_t { DMX_RAYMASK_BODIES = 7u, DMX_RAYMASK_STATIC = 8u, DMX_RAYMASK_PLANE = 16u };
+enum : int { RAY_FORM_AUTO = 0, RAY_FORM_LANE = 1, RAY_FORM_WAVE = 2, RAY_FORM_BRUTE = 3 };
+template <class T> struct RaySceneParams {
+    const T *S; const uint8_t *gtype; const uint8_t *bflags; int64_t n;     // every slot of [0, n) can be seen, ghost slots too
+    const T *hull_planes; int hull_nf;
+    const T *sbox; int n_static;
+    int plane_on; V3<T> pn; T pd;
+    uint32_t mask;
+    // the ray cast's own column grid (same hashing and bucket layout as GridParams) and the visible bodies' (x,z) rectangle
+    // (xmin, xmax, zmin, zmax as ordered keys: dmx_raycast.hip)
+    T cell, inv_cell;
+    uint32_t gmask; int xbits, cap;
+    const uint32_t *count; const int32_t *items;
+    const unsigned long long *rect;
+};
+
 struct StepDiag {
     unsigned long long contacts;
     double residual;
@@ -248,6 +267,14 @@ hipError_t launch_aos_to_soa(T *S, int64_t stride, int comp0, int k, int64_t fir
 template <class T>
 hipError_t launch_soa_to_aos(const T *S, int64_t stride, int comp0, int k, int64_t first, int64_t count, T *aos,
                              hipStream_t st);
+
+// the (x,z) bounding rectangle of the centres of the slots a ray can see (class set, alive) -> rect[4]
+template <class T>
+hipError_t launch_ray_bounds(const T *S, const uint8_t *gtype, const uint8_t *bflags, int64_t n, unsigned long long *rect, hipStream_t st);
+// n_rays rays (7 reals each: origin, direction, length) -> ids, hits (7 reals each: pos, normal, depth); form = RAY_FORM_LANE / WAVE / BRUTE
+template <class T>
+hipError_t launch_ray_cast(int form, const RaySceneParams<T> &Sc, int64_t n_rays, const T *rays, int32_t *ids, T *hits, hipStream_t st);
+hipError_t dmx_touch_raycast(int real_bytes);
 
 // one per translation unit with device code: forces the unit's code object to load (see dmx_kernels.hip)
 hipError_t dmx_touch_kernels(int real_bytes); hipError_t dmx_touch_islands(int real_bytes); hipError_t dmx_touch_broadphase(int real_bytes);

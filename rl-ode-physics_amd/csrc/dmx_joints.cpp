@@ -516,6 +516,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         b->sm_parity = sp ^ 1;
         b->sm_diag_cur = cur;
         b->sm_mirror_valid = true;
+        b->state_version++;               // (this tick wrote body state too: what rays see has moved on)
         b->last_small = true;
         b->last_islands = true;
         b->ext_pending = false;

@@ -17,6 +17,7 @@
 #include "../../include/ode/ode.h"
 #include "../../include/dmx_batch.h"
 #include "dmx_collide.hpp"
+#include "dmx_ray.hpp"
 #include "dmx_math.hpp"
 
 using dmx::M3;
@@ -451,6 +452,35 @@ extern "C" dGeomID dCreatePlane(dSpaceID space, dReal a, dReal b, dReal c, dReal
     g->plane[0] = a; g->plane[1] = b; g->plane[2] = c; g->plane[3] = d;
     return g;
 }
+// ---- rays (include/ode/ode.h): position = the start, side[0] = the length, plane[0..2] = the unit direction
+extern "C" dGeomID dCreateRay(dSpaceID space, dReal length)
+{
+    if (space) {
+        fprintf(stderr, "libode_mi355: dCreateRay: rays do not take part in dSpaceCollide; only space == 0 is supported\n");
+        return nullptr;
+    }
+    dxGeom *g = new_geom(nullptr, dRayClass);
+    g->side[0] = length;
+    g->plane[0] = 0; g->plane[1] = 0; g->plane[2] = 1; g->plane[3] = 0;       // ODE's ray points along +z until set
+    return g;
+}
+extern "C" void dGeomRaySet(dGeomID g, dReal px, dReal py, dReal pz, dReal dx, dReal dy, dReal dz)
+{
+    if (!g || g->cls != dRayClass) return;
+    g->pos[0] = px; g->pos[1] = py; g->pos[2] = pz;
+    const dReal l = dmx::tsqrt<dReal>(dx * dx + dy * dy + dz * dz);
+    if (l > 0) { dx /= l; dy /= l; dz /= l; }
+    g->plane[0] = dx; g->plane[1] = dy; g->plane[2] = dz;
+}
+extern "C" void dGeomRayGet(dGeomID g, dVector3 start, dVector3 dir)
+{
+    if (!g || g->cls != dRayClass) return;
+    for (int i = 0; i < 3; i++) { start[i] = g->pos[i]; dir[i] = g->plane[i]; }
+    start[3] = 0; dir[3] = 0;
+}
+extern "C" void dGeomRaySetLength(dGeomID g, dReal length) { if (g && g->cls == dRayClass) g->side[0] = length; }
+extern "C" dReal dGeomRayGetLength(dGeomID g) { return g && g->cls == dRayClass ? g->side[0] : (dReal)0; }
+
 extern "C" void dGeomDestroy(dGeomID g)
 {
     if (!g) return;
@@ -536,9 +566,38 @@ bool collide_ordered(const dxGeom *a, const dxGeom *b, int maxc, Hit *out, int *
 
 }  // namespace
 
+namespace {
+// dCollide with a ray on either side: one contact at most, g1 = the ray
+int collide_ray(dxGeom *ray, dxGeom *g, dContactGeom *c)
+{
+    if (g->cls == dRayClass) return 0;
+    sync_geom(g);
+    dmx::Ray<dReal> r;
+    if (!dmx::ray_make<dReal>(ray->pos[0], ray->pos[1], ray->pos[2], ray->plane[0], ray->plane[1], ray->plane[2], ray->side[0], r)) return 0;
+    dmx::RayHit<dReal> h;
+    bool hit = false;
+    if (g->cls == dPlaneClass) hit = dmx::ray_plane<dReal>(r, V3<dReal>{ g->plane[0], g->plane[1], g->plane[2] }, g->plane[3], h);
+    else {
+        const dReal *p = geom_pos(g);
+        const V3<dReal> x = { p[0], p[1], p[2] };
+        if (g->cls == dSphereClass) hit = dmx::ray_sphere<dReal>(r, x, g->side[0], h);
+        else if (g->cls == dBoxClass) hit = dmx::ray_box<dReal>(r, x, to_m3(geom_R(g)), V3<dReal>{ g->side[0], g->side[1], g->side[2] }, h);
+    }
+    if (!hit) return 0;
+    c->pos[0] = r.o.x + h.t * r.d.x; c->pos[1] = r.o.y + h.t * r.d.y; c->pos[2] = r.o.z + h.t * r.d.z; c->pos[3] = 0;
+    c->normal[0] = h.n.x; c->normal[1] = h.n.y; c->normal[2] = h.n.z; c->normal[3] = 0;
+    c->depth = h.t;
+    c->g1 = ray; c->g2 = g;
+    c->side1 = -1; c->side2 = -1;
+    return 1;
+}
+}  // namespace
+
 extern "C" int dCollide(dGeomID o1, dGeomID o2, int flags, dContactGeom *contact, int skip)
 {
     if (!o1 || !o2 || !contact || o1 == o2) return 0;
+    if (o1->cls == dRayClass) return collide_ray(o1, o2, contact);
+    if (o2->cls == dRayClass) return collide_ray(o2, o1, contact);
     if (o1->body && o1->body == o2->body) return 0;
     int maxc = flags & 0xffff;
     if (maxc < 1) maxc = 1;
