@@ -351,6 +351,40 @@ int dmxBatchSmallTickStats(dmxBatchID b, int64_t out[DMX_SMALL_TICK_NSTATS]);
 enum { DMX_ORDER_CREATION = 0, DMX_ORDER_ODE = 1 };
 int dmxBatchSetRowOrder(dmxBatchID b, int order, uint32_t seed);
 
+/* ---- articulation joints: ball-and-socket and hinge (dJointCreateBall / dJointCreateHinge).  Unlike contact joints, which
+ * live for one tick, the set given to dmxBatchSetJoints persists until it is replaced and takes part in every
+ * dmxBatchStepJoints tick -- both steppers, both precisions, the general path and the single-launch tick of small worlds.
+ * Anchors and axes are stored in the frames of the two bodies (world frame for a side that is -1, the world).
+ *   active       a joint is inactive for a tick when both sides are -1, when both sides are the same slot, or when a side that
+ *                is >= 0 is not alive.  body1 = -1 with a live body2 exchanges the two sides (anchors and axes included).  A
+ *                kinematic body is a side like any other (its inverse mass is zero).
+ *   row order    within an island the active articulation joints come first, in the order of the set, then the tick's contact
+ *                joints in creation order; articulation joints link islands as contact joints between two bodies do.
+ *   rows         x_i, R_i = body i's position and rotation, a_i = R_i anchor_i (a world side: x = anchor, a = 0, no Jacobian
+ *                block); every row has lo = -inf, hi = +inf, cfm = the world's CFM; k = ERP / h.
+ *                ball:  three rows, d = e_x, e_y, e_z:  J = [ d, a_1 x d | -d, -(a_2 x d) ],  c = k ((x_2 + a_2) - (x_1 + a_1)) . d
+ *                hinge: the three ball rows, then with u = R_1 axis1, w = R_2 axis2, (p, q) = dPlaneSpace(u), for r = p, q:
+ *                       J = [ 0, r | 0, -r ],  c = k (u x w) . r
+ * While a non-empty set is present, the ticks that find their own contacts and build islands on the device -- dmxBatchStep,
+ * dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick(s), dmxBatchExactTick -- and QuickStep's dmxBatchStepJoints under DMX_ORDER_ODE
+ * return DMX_EINVAL with one line on stderr: nothing is silently ignored.  (Under DMX_STEPPER_EXACT the row order is never used, so
+ * there is nothing to refuse.)  Everything else is unaffected; dmxBatchLastContactCount goes on counting contact joints only. */
+enum { DMX_JOINT_BALL = 1, DMX_JOINT_HINGE = 2 };
+typedef struct dmxJoint {
+    int32_t kind, body1, body2, reserved;     /* slots; -1 = the world */
+    double anchor1[3], anchor2[3];            /* in the frame of body1 / body2; world frame for a side that is -1 */
+    double axis1[3], axis2[3];                /* hinge: unit axis in each side's frame; ignored for a ball */
+} dmxJoint;
+int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints);   /* copied; replaces the set; n = 0 removes it */
+int64_t dmxBatchJointCount(dmxBatchID b);
+/* a joint from world-frame anchor / axis at the bodies' CURRENT poses (what dJointSetHingeAnchor / Axis mean); axis_w may be
+ * NULL for a ball */
+int dmxBatchJointFromWorld(dmxBatchID b, int kind, int32_t body1, int32_t body2, const double anchor_w[3], const double axis_w[3],
+                           dmxJoint *out);
+/* per joint of the set |p2 - p1| (the anchors' separation) and, for hinges, |u x w| (0 for balls), from the current state,
+ * computed on the device (inactive joints report 0); either array may be NULL; out_max[2] = the two maxima (may be NULL) */
+int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_err, double out_max[2]);
+
 /* per-body flags for the island path: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes */
 enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };
 int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64_t first, int64_t count);

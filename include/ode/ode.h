@@ -190,6 +190,28 @@ void dJointGroupDestroy(dJointGroupID);                          /* main.c:265 *
 dJointID dJointCreateContact(dWorldID, dJointGroupID, const dContact *);   /* main.c:690 */
 void dJointAttach(dJointID, dBodyID body1, dBodyID body2);       /* main.c:691 */
 
+/* ---- articulation joints: ball-and-socket and hinge [ODE-recall objects.h].  Anchors and axes are given in world
+ * coordinates after dJointAttach and kept in the bodies' frames at their poses of that moment; a body of 0 is the world.
+ * dJointAttach(j, 0, body) exchanges the two, as ODE does: dJointGetBody(j, 0) is the body.  dWorldDestroy destroys the joints that
+ * are in no group.  dBodyDestroy detaches the body's joints (both sides: the joint does nothing until it is attached again).  No limits,
+ * motors or angles.  dWorldStep / dWorldQuickStep honour them (include/dmx_batch.h, dmxBatchSetJoints). */
+enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeContact = 4 };
+dJointID dJointCreateBall(dWorldID, dJointGroupID);
+dJointID dJointCreateHinge(dWorldID, dJointGroupID);
+void dJointDestroy(dJointID);
+int dJointGetType(dJointID);
+dBodyID dJointGetBody(dJointID, int index);
+void dJointSetBallAnchor(dJointID, dReal x, dReal y, dReal z);
+void dJointGetBallAnchor(dJointID, dVector3 result);
+void dJointGetBallAnchor2(dJointID, dVector3 result);
+void dJointSetHingeAnchor(dJointID, dReal x, dReal y, dReal z);
+void dJointSetHingeAxis(dJointID, dReal x, dReal y, dReal z);
+void dJointGetHingeAnchor(dJointID, dVector3 result);
+void dJointGetHingeAnchor2(dJointID, dVector3 result);
+void dJointGetHingeAxis(dJointID, dVector3 result);
+int dAreConnected(dBodyID, dBodyID);
+int dAreConnectedExcluding(dBodyID body1, dBodyID body2, int joint_type);
+
 /* ---- rotation helpers used when filling dBodySetRotation's argument ------- */
 void dRSetIdentity(dMatrix3 R);
 void dRFromAxisAndAngle(dMatrix3 R, dReal ax, dReal ay, dReal az, dReal angle);

@@ -26,6 +26,7 @@ BATCH_SYMBOLS = [
     "dmxBatchSetSnapshotMode", "dmxBatchSetStaticBoxes", "dmxBatchSetStepper", "dmxBatchSetConvexHullFaces",
     "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision",
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
+    "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -131,5 +132,9 @@ def load():
     sig("dmxBatchRayCast", I, P, L, P, P, P, C.c_uint32)
     sig("dmxBatchRayCastDevice", I, P, L, P, P, P, C.c_uint32)
     sig("dmxBatchSetRayForm", I, P, I)
+    sig("dmxBatchSetJoints", I, P, L, P)
+    sig("dmxBatchJointCount", L, P)
+    sig("dmxBatchJointFromWorld", I, P, I, C.c_int32, C.c_int32, P, P, P)
+    sig("dmxBatchJointErrors", I, P, P, P, P)
     _lib = lib
     return lib

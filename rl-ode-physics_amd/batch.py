@@ -30,6 +30,13 @@ CONTACT_JOINT_DTYPE = np.dtype({
                 np.float64, np.float64, np.float64],
     "offsets": [0, 24, 48, 56, 60, 64, 72, 80, 88, 96, 104],
     "itemsize": 112})
+# dmxJoint (include/dmx_batch.h): an articulation joint -- a ball or a hinge -- of the persistent set (set_joints)
+JOINT_BALL, JOINT_HINGE = 1, 2
+JOINT_DTYPE = np.dtype({
+    "names": ["kind", "body1", "body2", "reserved", "anchor1", "anchor2", "axis1", "axis2"],
+    "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 3), (np.float64, 3), (np.float64, 3), (np.float64, 3)],
+    "offsets": [0, 4, 8, 12, 16, 40, 64, 88],
+    "itemsize": 112})
 LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", "single", "fallback")
 # the single-launch tick of small worlds (dmxBatchSetSmallTick); the counters of dmxBatchSmallTickStats, in its order: ticks on
 # that path, step_joints ticks on the general path, then one count per reason a tick was not eligible
@@ -199,6 +206,34 @@ class BatchWorld:
         j = np.ascontiguousarray(np.asarray(joints).astype(CONTACT_JOINT_DTYPE, copy=False))
         _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
                "dmxBatchStepJoints")
+
+    # -- articulation joints: ball and hinge (dJointCreateBall / dJointCreateHinge), a set that persists between ticks --
+    def set_joints(self, arr):
+        """replace the set of articulation joints (an array of JOINT_DTYPE; empty or None removes it); every later
+        step_joints tick honours them, ahead of the tick's contact joints"""
+        j = np.zeros(0, JOINT_DTYPE) if arr is None else np.ascontiguousarray(np.asarray(arr).astype(JOINT_DTYPE, copy=False)).reshape(-1)
+        _check(self.lib.dmxBatchSetJoints(self.h, j.shape[0], j.ctypes.data if j.shape[0] else None), "dmxBatchSetJoints")
+
+    def joint_count(self):
+        return int(self.lib.dmxBatchJointCount(self.h))
+
+    def joint_from_world(self, kind, body1, body2, anchor, axis=None):
+        """a JOINT_DTYPE record from a world-frame anchor (and axis, for a hinge) at the bodies' current poses; -1 = the world"""
+        out = np.zeros(1, JOINT_DTYPE)
+        a = np.ascontiguousarray(anchor, np.float64).reshape(3)
+        x = None if axis is None else np.ascontiguousarray(axis, np.float64).reshape(3)
+        _check(self.lib.dmxBatchJointFromWorld(self.h, int(kind), int(body1), int(body2), a.ctypes.data,
+                                               None if x is None else x.ctypes.data, out.ctypes.data), "dmxBatchJointFromWorld")
+        return out[0]
+
+    def joint_errors(self):
+        """-> (pos_err [n], axis_err [n], (max pos_err, max axis_err)) of the set at the current state: the anchors' separation
+        and, for hinges, |u x w|, computed on the device"""
+        n = self.joint_count()
+        pe, ae, mx = np.zeros(n), np.zeros(n), np.zeros(2)
+        _check(self.lib.dmxBatchJointErrors(self.h, pe.ctypes.data if n else None, ae.ctypes.data if n else None, mx.ctypes.data),
+               "dmxBatchJointErrors")
+        return pe, ae, (float(mx[0]), float(mx[1]))
 
     def set_stepper(self, stepper):
         """STEPPER_QUICK (dWorldQuickStep, default) / STEPPER_EXACT (dWorldStep) for step_joints"""

@@ -1,0 +1,144 @@
+// dmx_artic.hip -- the articulation joints' entry points of the batch C ABI (include/dmx_batch.h): the persistent set
+// (dmxBatchSetJoints), a joint from world-frame anchor and axis at the bodies' current poses (dmxBatchJointFromWorld), and the
+// joints' position / axis errors from the current state, computed on the device (dmxBatchJointErrors).  The rows themselves are
+// built by joint_unit_rows (dmx_island_rows.hpp) inside the island kernels; the host side of a tick is in dmx_joints.cpp.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <cmath>
+
+#include "dmx_batch_priv.hpp"
+
+namespace dmx {
+
+// One lane per joint: |p2 - p1| with p_i = x_i + R_i anchor_i (a world side: its anchor), and for hinges |u x w| with
+// u = R_1 axis1, w = R_2 axis2 -- the quantities the rows' right-hand sides pull to zero, in the batch's precision.  The two
+// maxima: a wave reduction, then one atomic per wavefront on the values' bit patterns (non-negative doubles order like their bits).
+template <class T>
+__global__ __launch_bounds__(256) void joint_errors(const T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, int64_t n_slots,
+                                                    const dmxJoint *__restrict__ joints, int64_t nj, double *__restrict__ pos_err,
+                                                    double *__restrict__ axis_err, unsigned long long *__restrict__ maxima)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double pe = 0.0, ae = 0.0;
+    if (k < nj) {
+        const dmxJoint j = joints[k];
+        const int s1 = j.body1, s2 = j.body2;
+        auto alive = [&](int s) { return s < n_slots && (bflags[s] & BF_ALIVE) != 0; };
+        const bool active = !(s1 < 0 && s2 < 0) && s1 != s2 && (s1 < 0 || alive(s1)) && (s2 < 0 || alive(s2));
+        if (active) {
+            auto side = [&](int s, const double *anchor, const double *axis, V3<T> &p, V3<T> &u) {
+                const V3<T> a = { (T)anchor[0], (T)anchor[1], (T)anchor[2] }, ax = { (T)axis[0], (T)axis[1], (T)axis[2] };
+                if (s < 0) { p = a; u = ax; return; }
+                const Q4<T> q = { S[slab_ix(C_QUAT + 0, s)], S[slab_ix(C_QUAT + 1, s)], S[slab_ix(C_QUAT + 2, s)], S[slab_ix(C_QUAT + 3, s)] };
+                const M3<T> R = quat_to_R(q);
+                const V3<T> ra = mulv(R, a);
+                p = { S[slab_ix(C_POS + 0, s)] + ra.x, S[slab_ix(C_POS + 1, s)] + ra.y, S[slab_ix(C_POS + 2, s)] + ra.z };
+                u = mulv(R, ax);
+            };
+            V3<T> p1, p2, u, w;
+            side(s1, j.anchor1, j.axis1, p1, u);
+            side(s2, j.anchor2, j.axis2, p2, w);
+            const V3<T> d = { p2.x - p1.x, p2.y - p1.y, p2.z - p1.z };
+            pe = (double)tsqrt<T>(dot(d, d));
+            if (j.kind == DMX_JOINT_HINGE) { const V3<T> c = cross(u, w); ae = (double)tsqrt<T>(dot(c, c)); }
+        }
+        pos_err[k] = pe;
+        axis_err[k] = ae;
+    }
+    double mp = pe, ma = ae;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double a = __shfl_xor(mp, o, 64), c = __shfl_xor(ma, o, 64);
+        mp = a > mp ? a : mp;
+        ma = c > ma ? c : ma;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&maxima[0], (unsigned long long)__double_as_longlong(mp));
+        atomicMax(&maxima[1], (unsigned long long)__double_as_longlong(ma));
+    }
+}
+
+}  // namespace dmx
+
+extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints)
+{
+    if (!b || n < 0 || (n > 0 && !joints)) return DMX_EINVAL;
+    for (int64_t k = 0; k < n; k++)
+        if (joints[k].kind != DMX_JOINT_BALL && joints[k].kind != DMX_JOINT_HINGE) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    b->art.assign(joints, joints + n);
+    return DMX_OK;
+}
+
+extern "C" int64_t dmxBatchJointCount(dmxBatchID b) { return b ? (int64_t)b->art.size() : DMX_EINVAL; }
+
+extern "C" int dmxBatchJointFromWorld(dmxBatchID b, int kind, int32_t body1, int32_t body2, const double anchor_w[3], const double axis_w[3],
+                                      dmxJoint *out)
+{
+    if (!b || !out || !anchor_w || (kind != DMX_JOINT_BALL && kind != DMX_JOINT_HINGE) || (kind == DMX_JOINT_HINGE && !axis_w)) return DMX_EINVAL;
+    if (body1 < -1 || body2 < -1 || body1 >= b->n || body2 >= b->n) return DMX_EINVAL;
+    memset(out, 0, sizeof(*out));
+    out->kind = kind; out->body1 = body1; out->body2 = body2;
+    double ax[3] = { 0, 0, 0 };
+    if (axis_w) {
+        const double l = std::sqrt(axis_w[0] * axis_w[0] + axis_w[1] * axis_w[1] + axis_w[2] * axis_w[2]);
+        if (kind == DMX_JOINT_HINGE && !(l > 0)) return DMX_EINVAL;
+        if (l > 0) for (int k = 0; k < 3; k++) ax[k] = axis_w[k] / l;
+    }
+    auto side = [&](int32_t s, double *anchor, double *axis) -> int {
+        if (s < 0) { for (int k = 0; k < 3; k++) { anchor[k] = anchor_w[k]; axis[k] = ax[k]; } return DMX_OK; }
+        double st[13];
+        if (b->precision == DMX_F32) {
+            float f[13];
+            const int rc = dmxBatchDownload(b, DMX_STATE, f, s, 1);
+            if (rc != DMX_OK) return rc;
+            for (int k = 0; k < 13; k++) st[k] = f[k];
+        } else {
+            const int rc = dmxBatchDownload(b, DMX_STATE, st, s, 1);
+            if (rc != DMX_OK) return rc;
+        }
+        const Q4<double> q = { st[3], st[4], st[5], st[6] };
+        const M3<double> R = quat_to_R(q);
+        const double d[3] = { anchor_w[0] - st[0], anchor_w[1] - st[1], anchor_w[2] - st[2] };
+        for (int k = 0; k < 3; k++) {          // R^T
+            anchor[k] = R.m[0][k] * d[0] + R.m[1][k] * d[1] + R.m[2][k] * d[2];
+            axis[k] = R.m[0][k] * ax[0] + R.m[1][k] * ax[1] + R.m[2][k] * ax[2];
+        }
+        return DMX_OK;
+    };
+    int rc = side(body1, out->anchor1, out->axis1);
+    if (rc == DMX_OK) rc = side(body2, out->anchor2, out->axis2);
+    return rc;
+}
+
+extern "C" int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_err, double out_max[2])
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if (out_max) out_max[0] = out_max[1] = 0.0;
+    const int64_t nj = (int64_t)b->art.size();
+    if (nj == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    int rc;
+    if ((rc = dmx_ensure_dev(b->art_dev, (size_t)nj * sizeof(dmxJoint))) != DMX_OK) return rc;
+    if ((rc = dmx_ensure_dev(b->art_err, ((size_t)2 * nj + 2) * sizeof(double))) != DMX_OK) return rc;
+    double *d_pos = (double *)b->art_err.p + 2, *d_axis = d_pos + nj;
+    unsigned long long *d_max = (unsigned long long *)b->art_err.p;
+    // (the set lives in pageable host memory: plain copies, which have read it when they return)
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->art_dev.p, b->art.data(), (size_t)nj * sizeof(dmxJoint), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_max, 0, 2 * sizeof(double), b->stream));
+    const unsigned grid = (unsigned)((nj + 255) / 256);
+    if (b->precision == DMX_F32)
+        hipLaunchKernelGGL((dmx::joint_errors<float>), dim3(grid), dim3(256), 0, b->stream, (const float *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_axis, d_max);
+    else
+        hipLaunchKernelGGL((dmx::joint_errors<double>), dim3(grid), dim3(256), 0, b->stream, (const double *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_axis, d_max);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (pos_err) HIP_TRY(hipMemcpy(pos_err, d_pos, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
+    if (axis_err) HIP_TRY(hipMemcpy(axis_err, d_axis, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_max) HIP_TRY(hipMemcpy(out_max, d_max, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return DMX_OK;
+}

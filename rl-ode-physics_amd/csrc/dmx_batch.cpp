@@ -189,7 +189,7 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
         if (d->p) (void)hipFree(d->p);
     for (dmxBatch::DevBuf *d : { &b->bp_count, &b->bp_items, &b->bp_flags, &b->bp_inpair, &b->bp_snapshot, &b->hull, &b->cbuf, &b->ccount,
                                 &b->ex_arena, &b->ex_body, &b->ex_last, &b->ex_aabb, &b->sbox, &b->hull_planes, &b->rc_count, &b->rc_items, &b->rc_misc,
-                                &b->rc_rays, &b->rc_ids, &b->rc_hits })
+                                &b->rc_rays, &b->rc_ids, &b->rc_hits, &b->art_dev, &b->art_err })
         if (d->p) (void)hipFree(d->p);
     if (b->bp_flags_host) (void)hipHostFree(b->bp_flags_host);
     if (b->ex_counts_host) (void)hipHostFree(b->ex_counts_host);
@@ -423,6 +423,7 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
 extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
 {
     if (!b || !(h > 0) || nsteps < 0) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchStep")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_written(b);
@@ -633,6 +634,7 @@ extern "C" int dmxBatchChunkBegin(dmxBatchID b, int *exact_only, int *ballistic)
 extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_written(b);
@@ -641,6 +643,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
 extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_first, int check_last)
 {
     if (!b || !(h > 0) || nticks < 0) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_written(b);
@@ -700,6 +703,7 @@ extern "C" int dmxBatchChunkRollback(dmxBatchID b)
 extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchExactTick")) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
@@ -800,6 +804,7 @@ extern "C" int dmxBatchSetActiveCount(dmxBatchID b, int64_t n_active)
 extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t count, int reset_diag)
 {
     if (!b || !(h > 0) || first < 0 || count < 0 || first + count > b->n_active) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchStepRange")) return DMX_EINVAL;
     SETTLE(b);
     // lanes own 16 B packs of consecutive bodies: ranges must start on a pack and end on one (or at the end)
     const int64_t pack = 16 / (int64_t)b->rsize;
@@ -842,6 +847,7 @@ extern "C" int dmxBatchGetStream(dmxBatchID b, void **hip_stream)
 extern "C" int dmxBatchStepTimed(dmxBatchID b, double h, int nsteps, float *ms)
 {
     if (!b || !ms) return DMX_EINVAL;
+    if (dmx_refuse_joints(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     int rc = dmxBatchStep(b, h, nsteps);
@@ -884,7 +890,7 @@ extern "C" int dmxBatchLastContactCount(dmxBatchID b, int64_t *n)
     unsigned long long c; double r;
     int rc = fetch_diag(b, &c, &r);
     if (rc != DMX_OK) return rc;
-    *n = (int64_t)c;
+    *n = (int64_t)c - (b->last_islands ? b->last_units : 0);      // (contact joints only: not the articulation joints' units)
     return DMX_OK;
 }
 

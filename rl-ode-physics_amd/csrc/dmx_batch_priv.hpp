@@ -29,7 +29,9 @@
 using namespace dmx;
 
 // a contact joint in canonical form: body1 a live dynamic slot, normal into it (dmx_joints.cpp)
-struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; };
+// ... or a unit of an articulation joint (unit != 0: j is null, art = its index in the batch's set): at most three rows on the
+// same two bodies, carried beside the contacts -- a ball is one DMX_UNIT_BALL, a hinge a DMX_UNIT_BALL and a DMX_UNIT_HINGE2
+struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; int unit = 0; int art = -1; };
 
 struct dmxBatch {
     int64_t n = 0, stride = 0;
@@ -189,7 +191,19 @@ struct dmxBatch {
     int ray_form = 0;                              // dmxBatchSetRayForm; DMX_RAY_FORM in the environment sets the default
     DevBuf rc_count, rc_items, rc_misc;            // rc_misc: BPF_COUNT flag words, then the rectangle's four keys at byte 64
     DevBuf rc_rays, rc_ids, rc_hits;               // device staging of dmxBatchRayCast's host arrays
+    // articulation joints (dmxBatchSetJoints): the set, and the device staging of dmxBatchJointErrors
+    std::vector<dmxJoint> art;
+    DevBuf art_dev, art_err;
+    int64_t last_units = 0;                        // units the last dmxBatchStepJoints tick carried among its contact entries
 };
+// the ticks that build their own islands on the device do not know articulation joints: they say so instead of ignoring them
+inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
+{
+    if (b->art.empty()) return false;
+    fprintf(stderr, "libode_mi355: %s does not honour articulation joints (dmxBatchSetJoints): %lld are set; use dmxBatchStepJoints\n",
+            what, (long long)b->art.size());
+    return true;
+}
 // A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later
 // upload of another mass while eager ticks use the new one: launches recorded during a capture read the constants from the
 // slab.  Asked once per stepping call of the C ABI (the entry points that can reach integrate_free), and only while the

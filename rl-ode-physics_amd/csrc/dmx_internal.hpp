@@ -89,7 +89,13 @@ template <class T> struct IslandSet {
     int order_stride;      //   row_off[island] + i] at its i-th step; null: rows in creation order (solve_islands only)
     int singles;           // 1: islands of one body with 1..8 contacts are left to solve_singles / solve_singles_lds (one lane each);
                            // whoever builds `big` must then keep such islands out of it
+    // 1: some entries of the contact arrays are units of articulation joints (dmx_island_rows.hpp: joint_unit_rows), marked by
+    // cmu = UNIT_BALL_MU / UNIT_HINGE2_MU; within an island they come before its contacts.  0: contacts only
+    int has_units = 0;
 };
+// a unit's marker in IslandSet::cmu: minus its row count (a contact's mu is never negative there when has_units is set)
+constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2;
+constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0;
 
 template <class T> struct StepParams {
     V3<T> g;            // gravity

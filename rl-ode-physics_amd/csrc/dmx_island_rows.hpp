@@ -1,5 +1,5 @@
 // dmx_island_rows.hpp -- the per-body / per-contact / per-row phase functions of the general island step (gravity and
-// world-frame inertia, the rows of a contact joint, rhs and M^-1 J^T, one SOR row update, the integration of a body).
+// world-frame inertia, the rows of a contact joint and of a ball / hinge joint's units, rhs and M^-1 J^T, one SOR row update, the integration of a body).
 // Shared by the SOR kernels (dmx_islands.hip) and the exact solve of dWorldStep (dmx_lcp.hip): both steppers build the same
 // rows [ODE-recall: dxStepIsland / dxQuickStepIsland share getInfo1/getInfo2], /root/reference/src/main.c:213.
 #pragma once
@@ -18,10 +18,11 @@ static_assert(RW_COUNT >= 29 && RW_COUNT % 4 == 0, "a row is read in 16-byte pie
 // per island-body scratch layout (reals)
 enum : int { BW_INVI = 0, BW_FACC = 9, BW_TACC = 12, BW_INVM = 15, BW_FC = 16, BW_TMP = 22, BW_COUNT = 28 };
 
-template <class T> __device__ __forceinline__ V3<T> ld3(const T *p) { return { p[0], p[1], p[2] }; }
-template <class T> __device__ __forceinline__ void st3(T *p, const V3<T> &v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+// (host too: tests/harness/joint_rows_harness.cpp runs joint_unit_rows on the CPU)
+template <class T> DMX_HD V3<T> ld3(const T *p) { return { p[0], p[1], p[2] }; }
+template <class T> DMX_HD void st3(T *p, const V3<T> &v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 template <class T> __device__ __forceinline__ T dot3p(const T *a, const V3<T> &b) { return fma_(a[2], b.z, fma_(a[1], b.y, a[0] * b.x)); }
-template <class T> __device__ __forceinline__ V3<T> ldS(const T *S, int64_t stride, int c0, int s)
+template <class T> DMX_HD V3<T> ldS(const T *S, int64_t stride, int c0, int s)
 {
     return { S[slab_ix(c0 + 0, s)], S[slab_ix(c0 + 1, s)], S[slab_ix(c0 + 2, s)] };
 }
@@ -62,9 +63,98 @@ __device__ __forceinline__ void stage_body(const T *S, const uint8_t *bflags, in
 }
 
 // per-contact surface arrays are optional: without them every contact carries the batch's surface (StepParams)
+// (an entry that is a unit of an articulation joint carries minus its row count there: UNIT_BALL_MU / UNIT_HINGE2_MU)
 template <class T> __device__ __forceinline__ int contact_rpc(const IslandSet<T> &I, const StepParams<T> &P, int ci)
 {
-    return (I.cmu != nullptr ? I.cmu[ci] : P.mu) > 0 ? 3 : 1;
+    const T mu = I.cmu != nullptr ? I.cmu[ci] : P.mu;
+    if (I.has_units && mu < 0) return mu == T(UNIT_HINGE2_MU) ? 2 : 3;
+    return mu > 0 ? 3 : 1;
+}
+template <class T> __device__ __forceinline__ bool contact_is_unit(const IslandSet<T> &I, int ci)
+{
+    return I.has_units && I.cmu[ci] < 0;
+}
+
+// a + b and its rounding error (Knuth's TwoSum; the library is built without contraction or reassociation)
+template <class T> DMX_HD T two_sum(T a, T b, T &e)
+{
+    const T s = a + b, bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+    return s;
+}
+// (x2 + a2) - (x1 + a1) for terms that nearly cancel
+template <class T> DMX_HD T diff_of_sums(T x2, T a2, T x1, T a1)
+{
+    T e1, e2, e3;
+    const T dx = two_sum(x2, -x1, e1), da = two_sum(a2, -a1, e2);
+    const T r = two_sum(dx, da, e3);
+    return r + ((e1 + e2) + e3);
+}
+
+// ---- rows of a unit of an articulation joint (dmxBatchSetJoints), written at island-relative row m ---------------------------
+// The unit's six reals travel in the contact arrays: cpos = the first side's anchor (ball unit) or axis (hinge unit) in the
+// frame of body 1, cnormal = the second side's in the frame of body 2 -- or in the world frame when there is no body 2.
+//   ball unit, d = e_x, e_y, e_z:  J = [ d, a1 x d | -d, -(a2 x d) ],  c = k ((x2 + a2) - (x1 + a1)) . d,   a_i = R_i anchor_i
+//   hinge unit, r = p, q of plane_space(u), u = R_1 axis1, w = R_2 axis2:  J = [ 0, r | 0, -r ],  c = k (u x w) . r
+// with k = erp / h, cfm = the world's, no bounds.  Returns the unit's row count.
+template <class T>
+DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
+                                               T *rows, int *jb, int ci, int m, T hinv)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
+    const bool hinge2 = I.cmu[ci] == T(UNIT_HINGE2_MU);
+    const V3<T> f1 = ld3(I.cpos + 3 * (size_t)ci), f2 = ld3(I.cnormal + 3 * (size_t)ci);
+    const Q4<T> q1 = { S[slab_ix(C_QUAT + 0, s1)], S[slab_ix(C_QUAT + 1, s1)], S[slab_ix(C_QUAT + 2, s1)], S[slab_ix(C_QUAT + 3, s1)] };
+    const V3<T> w1 = mulv(quat_to_R(q1), f1);              // a1 (ball unit) / u (hinge unit)
+    V3<T> w2 = f2;                                         // a world side: the anchor / axis as given
+    if (s2 >= 0) {
+        const Q4<T> q2 = { S[slab_ix(C_QUAT + 0, s2)], S[slab_ix(C_QUAT + 1, s2)], S[slab_ix(C_QUAT + 2, s2)], S[slab_ix(C_QUAT + 3, s2)] };
+        w2 = mulv(quat_to_R(q2), f2);
+    }
+    const T k = hinv * P.erp;
+    V3<T> dir[3], err;
+    int n;
+    if (hinge2) {
+        n = 2;
+        plane_space(w1, dir[0], dir[1]);
+        dir[2] = { T(0), T(0), T(0) };
+        err = cross(w1, w2);
+    } else {
+        n = 3;
+        dir[0] = { T(1), T(0), T(0) }; dir[1] = { T(0), T(1), T(0) }; dir[2] = { T(0), T(0), T(1) };
+        const V3<T> x1 = ldS(S, stride, C_POS, s1);
+        // (x2 + a2) - (x1 + a1); a world side's point is its anchor (x = anchor, a = 0).  The four terms cancel to the joint's
+        // error, which ERP / h carries straight into the velocities: summed plainly, the rounding of x + a -- an ulp of the
+        // POSITIONS -- would come out as 12 ulp(x) of velocity noise at h = 1/60.  (x2 - x1) + (a2 - a1) with the sums' rounding
+        // errors carried along (two_sum) is exact to an ulp of the error itself.
+        V3<T> x2 = w2, a2 = { T(0), T(0), T(0) };
+        if (s2 >= 0) { x2 = ldS(S, stride, C_POS, s2); a2 = w2; }
+        err = { diff_of_sums(x2.x, a2.x, x1.x, w1.x), diff_of_sums(x2.y, a2.y, x1.y, w1.y), diff_of_sums(x2.z, a2.z, x1.z, w1.z) };
+    }
+    for (int dnum = 0; dnum < n; dnum++) {
+        T *row = rows + (size_t)(m + dnum) * RW_COUNT;
+        jb[2 * (m + dnum)] = l1; jb[2 * (m + dnum) + 1] = l2;
+        T *J = row + RW_J;
+        const V3<T> d = dir[dnum];
+        const V3<T> zero = { T(0), T(0), T(0) };
+        const V3<T> lin = hinge2 ? zero : d;
+        const V3<T> ang1 = hinge2 ? d : cross(w1, d);
+        st3(J, lin);
+        st3(J + 3, ang1);
+        if (s2 >= 0) {
+            const V3<T> ang2 = hinge2 ? d : cross(w2, d);
+            J[6] = -lin.x; J[7] = -lin.y; J[8] = -lin.z;
+            J[9] = -ang2.x; J[10] = -ang2.y; J[11] = -ang2.z;
+        } else {
+            for (int j = 6; j < 12; j++) J[j] = T(0);
+        }
+        row[RW_LO] = -Limits<T>::inf(); row[RW_HI] = Limits<T>::inf();
+        row[RW_RHS] = k * dot(err, d);      // c for now
+        row[RW_AD] = P.cfm;                 // cfm for now
+        row[RW_LAM] = T(0);
+    }
+    return n;
 }
 
 // ---- rows of contact ci (normal + 2 friction when mu > 0), written at island-relative row m -----------------
@@ -74,6 +164,7 @@ template <class T, int RPCK = 0>
 __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                              T *rows, int *jb, int ci, int m, T hinv)
 {
+    if (RPCK == 0 && contact_is_unit(I, ci)) { (void)joint_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv); return; }
     const int s1 = I.cb1[ci], s2 = I.cb2[ci];
     const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
     const bool ind = I.csrc != nullptr;

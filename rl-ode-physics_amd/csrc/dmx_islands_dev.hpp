@@ -24,7 +24,8 @@ constexpr int SINGLE_MAXC_LDS = 8;      // rows in LDS (solve_singles_lds): a co
 template <class T> __device__ __forceinline__ bool island_is_single(const IslandSet<T> &I, int isl)
 {
     const int nb = I.body_off[isl + 1] - I.body_off[isl], nc = I.con_off[isl + 1] - I.con_off[isl];
-    return nb == 1 && nc >= 1 && nc <= SINGLE_MAXC_LDS;
+    // (an island's articulation units come first: one body on a joint to the world is not the one-body forms' island)
+    return nb == 1 && nc >= 1 && nc <= SINGLE_MAXC_LDS && !contact_is_unit(I, I.con_off[isl]);
 }
 
 template <class T> struct RowS { T J[6], iMJ[6], rhs, ad, lam; };

@@ -88,6 +88,29 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     cj.reserve((size_t)nj_in);
     // `include` (optional) restricts the tick to a subset of bodies: the rest is stepped by the fused kernels
     auto live = [&](int s) { return s >= 0 && s < n && (b->h_bflags[(size_t)s] & BF_ALIVE) && (!include || include[s]); };
+    // the active articulation joints first, as units of at most three rows (a ball: one unit; a hinge: its ball unit and the two
+    // angular rows), in the order of the set: the stable sort by island below keeps them ahead of the island's contacts
+    if (!b->art.empty() && (include || geo)) {          // (every caller that steps a subset is refused before it gets here)
+        fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour articulation joints (dmxBatchSetJoints)\n");
+        return DMX_EINVAL;
+    }
+    if (!b->art.empty()) {
+        for (size_t a = 0; a < b->art.size(); a++) {
+            const dmxJoint &j = b->art[a];
+            int b1 = j.body1, b2 = j.body2;
+            if ((b1 < 0 && b2 < 0) || b1 == b2) continue;
+            if ((b1 >= 0 && !live(b1)) || (b2 >= 0 && !live(b2))) continue;
+            const bool rev = b1 < 0;
+            if (rev) { b1 = b2; b2 = -1; }
+            DmxCanonicalJoint u; u.b1 = b1; u.b2 = b2; u.j = nullptr; u.rev = rev; u.unit = UNIT_BALL; u.art = (int)a;
+            cj.push_back(u);
+            if (j.kind == DMX_JOINT_HINGE) { u.unit = UNIT_HINGE2; cj.push_back(u); }
+        }
+    }
+    const int n_units = (int)cj.size();
+    // rows of an entry, and how many of them can clamp
+    auto rpc_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_HINGE2 ? 2 : 3) : (c.j->mu > 0 ? 3 : 1); };
+    auto nbd_rows_of = [](const CJ &c) { return c.unit ? 0 : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
     for (int64_t k = 0; k < nj_in; k++) {
         const dmxContactJoint &j = joints[k];
         int b1 = live(j.body1) ? j.body1 : -1, b2 = live(j.body2) ? j.body2 : -1;
@@ -95,7 +118,8 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         if (b1 < 0 && b2 >= 0) { b1 = b2; b2 = -1; rev = true; }   // dJointAttach(c, 0, body): swap + reverse
         if (b1 < 0) continue;                                       // static-static: the stepper ignores it
         if (b1 == b2) continue;
-        cj.push_back({ b1, b2, &j, rev });
+        DmxCanonicalJoint c; c.b1 = b1; c.b2 = b2; c.j = &j; c.rev = rev;
+        cj.push_back(c);
     }
     const int nc = (int)cj.size();
 
@@ -201,9 +225,9 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 int m = 0, nbd = 0;
                 for (int d = con_start[(size_t)i]; d < con_start[(size_t)i + 1]; d++) {
                     crow_h[(size_t)d] = m;
-                    const double mu = cj[(size_t)con_sorted[(size_t)d]].j->mu;
-                    m += mu > 0 ? 3 : 1;
-                    nbd += (mu > 0 && mu < __builtin_huge_val()) ? 3 : 1;
+                    const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
+                    m += rpc_of(c);
+                    nbd += nbd_rows_of(c);
                 }
                 m_of[(size_t)i] = m;
                 nbd_of[(size_t)i] = nbd;
@@ -228,7 +252,9 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             if (ode_order) break;                     // shuffled sweeps are sequential: every island takes solve_islands
             if (m_of[(size_t)i] < (exact ? 1 : big_island_rows())) continue;
             // one body with 1..8 contacts: solve_singles' / solve_singles_lds' island (one lane), never a workgroup's
-            if (!exact && island_bodies[(size_t)i] == 1 && con_start[(size_t)i + 1] - con_start[(size_t)i] <= 8) continue;
+            // (not with an articulation unit -- a body on a joint to the world: those forms know contacts only; units come first)
+            if (!exact && island_bodies[(size_t)i] == 1 && con_start[(size_t)i + 1] - con_start[(size_t)i] <= 8 &&
+                !cj[(size_t)con_sorted[(size_t)con_start[(size_t)i]]].unit) continue;
             // dWorldStep, an island of hundreds of rows or more: the grid-wide solve (dmx_lcp.hip), not one workgroup
             // (small and medium ones: one workgroup, the whole solve in LDS, while it fits)
             if (exact && !lcp_old_kernel() && !lcp_lds_fits((int)sizeof(T), m_of[(size_t)i], nbd_of[(size_t)i])) { grid_list.push_back(i); continue; }
@@ -270,7 +296,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 int nlev = 0, r = 0;
                 for (int d = con_start[(size_t)i]; d < con_start[(size_t)i + 1]; d++) {
                     const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
-                    const int rpc = c.j->mu > 0 ? 3 : 1;
+                    const int rpc = rpc_of(c);
                     for (int q = 0; q < rpc; q++, r++) {
                         int lv = last[(size_t)c.b1];
                         if (c.b2 >= 0 && last[(size_t)c.b2] > lv) lv = last[(size_t)c.b2];
@@ -396,6 +422,18 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         dmx_parallel_for(nc, 8192, [&](int64_t lo, int64_t hi, int) {
             for (int64_t d = lo; d < hi; d++) {
                 const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
+                if (c.unit) {
+                    // a unit's six reals ride in the contact arrays: the first side's anchor (axis) where a contact has its
+                    // position, the second side's where it has its normal; cmu says which unit it is
+                    const dmxJoint &a = b->art[(size_t)c.art];
+                    const double *f1 = c.unit == UNIT_BALL ? (c.rev ? a.anchor2 : a.anchor1) : (c.rev ? a.axis2 : a.axis1);
+                    const double *f2 = c.unit == UNIT_BALL ? (c.rev ? a.anchor1 : a.anchor2) : (c.rev ? a.axis1 : a.axis2);
+                    cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = 0; csrc[d] = 0;
+                    for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)f1[k]; cnormal[3 * (size_t)d + k] = (T)f2[k]; }
+                    cdepth[d] = T(0); cmu[d] = (T)(c.unit == UNIT_BALL ? UNIT_BALL_MU : UNIT_HINGE2_MU);
+                    cbounce[d] = T(0); cbv[d] = T(0); cserp[d] = T(0); cscfm[d] = T(0);
+                    continue;
+                }
                 const dmxContactJoint &j = *c.j;
                 cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = j.mode;
                 csrc[d] = geo ? geo->src[(size_t)(c.j - joints)] : 0;
@@ -406,6 +444,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 }
                 cdepth[d] = (T)j.depth; cmu[d] = (T)j.mu; cbounce[d] = (T)j.bounce; cbv[d] = (T)j.bounce_vel;
                 cserp[d] = (T)j.soft_erp; cscfm[d] = (T)j.soft_cfm;
+                if (n_units && j.mu < 0) cmu[d] = T(0);      // (what the kernels make of it anyway; below zero marks a unit)
             }
         });
     }
@@ -445,6 +484,8 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     I.cbounce = I.cmu + nc; I.cbounce_vel = I.cbounce + nc; I.csoft_erp = I.cbounce_vel + nc; I.csoft_cfm = I.csoft_erp + nc;
     I.rows = (T *)b->jd_rows.p; I.rowjb = (int *)b->jd_rowjb.p; I.bscr = (T *)b->jd_bscr.p; I.local = (int *)b->jd_local.p;
     I.singles = (exact || ode_order) ? 0 : 1;
+    I.has_units = n_units > 0 ? 1 : 0;
+    b->last_units = n_units;               // (the kernels count an island's entries: dmxBatchLastContactCount takes these off)
     I.order = nullptr; I.order_stride = 0;
     if (ode_order) {
         // the shuffled row orders, one per 8 sweeps, islands in ODE's processing order (the LCG is global and sequential)
@@ -558,12 +599,12 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     if (e > 0 && ord[e].first != ord[e - 1].first) run = e;
                     const int d = ord[e].second;
                     const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
-                    const int r = crow_h[(size_t)d], rpc = c.j->mu > 0 ? 3 : 1;
+                    const int r = crow_h[(size_t)d], rpc = rpc_of(c);
                     const uint64_t base = ((uint64_t)(uint32_t)(c.b1 + 1) << 38) | ((uint64_t)((uint32_t)(c.b2 + 1) & 0xffffffu) << 14) |
                                           ((uint64_t)((e - run) & 0xfffu) << 2);
                     for (int q = 0; q < rpc; q++) {
                         R.key[(size_t)(r + q)] = base | (uint64_t)q;
-                        R.unbounded[(size_t)(r + q)] = (q > 0 && !(c.j->mu < __builtin_huge_val())) ? 1 : 0;
+                        R.unbounded[(size_t)(r + q)] = (c.unit || (q > 0 && !(c.j->mu < __builtin_huge_val()))) ? 1 : 0;
                     }
                 }
                 // every body's rows (creation order): counting sort over the island's contacts; local index = position among the
@@ -574,7 +615,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 R.boff.assign((size_t)inb + 1, 0);
                 for (int d = d0; d < d1; d++) {
                     const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
-                    const int rpc = c.j->mu > 0 ? 3 : 1;
+                    const int rpc = rpc_of(c);
                     R.boff[(size_t)loc[(size_t)c.b1] + 1] += rpc;
                     if (c.b2 >= 0) R.boff[(size_t)loc[(size_t)c.b2] + 1] += rpc;
                 }
@@ -585,7 +626,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     fill.assign(R.boff.begin(), R.boff.end() - 1);
                     for (int d = d0; d < d1; d++) {
                         const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
-                        const int r = crow_h[(size_t)d], rpc = c.j->mu > 0 ? 3 : 1;
+                        const int r = crow_h[(size_t)d], rpc = rpc_of(c);
                         for (int q = 0; q < rpc; q++) {
                             R.bodyrows[(size_t)fill[(size_t)loc[(size_t)c.b1]]++] = 2 * (r + q);
                             if (c.b2 >= 0) R.bodyrows[(size_t)fill[(size_t)loc[(size_t)c.b2]]++] = 2 * (r + q) + 1;
@@ -622,5 +663,10 @@ extern "C" int dmxBatchStepJoints(dmxBatchID b, double h, int64_t n_joints, cons
     if (!b || !(h > 0) || n_joints < 0 || (n_joints > 0 && !joints)) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if (b->row_order_ode && !b->stepper_exact && !b->art.empty()) {      // (dWorldStep never uses the order)
+        fprintf(stderr, "libode_mi355: dmxBatchStepJoints under DMX_ORDER_ODE does not honour articulation joints (dmxBatchSetJoints): "
+                        "%lld are set\n", (long long)b->art.size());
+        return DMX_EINVAL;
+    }
     return dmx_step_joints(b, h, n_joints, joints, nullptr, nullptr);
 }

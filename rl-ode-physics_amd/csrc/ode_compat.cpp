@@ -87,6 +87,9 @@ struct dxJoint {
     dxJointGroup *group = nullptr;
     dContact contact;
     dxBody *b1 = nullptr, *b2 = nullptr;
+    int type = dJointTypeContact;
+    // a ball or a hinge: anchors and axes in the frames of the two bodies (world frame for a side without a body)
+    double anchor1[3] = { 0, 0, 0 }, anchor2[3] = { 0, 0, 0 }, axis1[3] = { 1, 0, 0 }, axis2[3] = { 1, 0, 0 };
 };
 
 struct dxJointGroup {
@@ -98,6 +101,9 @@ struct dxWorld {
     int cap = 0;
     std::vector<dxBody *> slots;       // slot -> body (nullptr = free)
     std::vector<dxJoint *> joints;     // contact joints of the current tick, creation order
+    std::vector<dxJoint *> arts;       // ball and hinge joints, creation order: they persist (dmxBatchSetJoints)
+    bool art_dirty = false;            // ... and changed since the batch last saw them
+    std::vector<dmxJoint> aj;
     dReal g[3] = { 0, 0, 0 };
     dReal erp = (dReal)0.2, cfm = kDefaultCFM, sor_w = (dReal)1.3;
     int iters = 20;
@@ -122,6 +128,7 @@ struct dxWorld {
         slots.resize((size_t)cap, nullptr);
         host_dirty = true;
         pushed_valid = false;          // a new batch has been told nothing yet
+        art_dirty = !arts.empty();
         // One read-back the general way into the buffer to_host() uses, now.  The runtime registers a pageable destination the
         // first time a device-to-host copy lands in it (8 ms, measured); a world whose ticks run on the single-launch path reads
         // its poses from the batch's host mirror and would meet that at the first tick that falls back -- a whole 120 Hz frame.
@@ -263,6 +270,8 @@ extern "C" void dWorldDestroy(dWorldID w)
         delete b;
     }
     for (dxJoint *j : w->joints) j->world = nullptr;
+    // ball and hinge joints outside a group go with the world; those in a group are the group's to delete [ODE-recall dWorldDestroy]
+    for (dxJoint *j : w->arts) { if (j->group) j->world = nullptr; else delete j; }
     if (w->batch) dmxBatchDestroy(w->batch);
     delete w;
 }
@@ -282,6 +291,20 @@ static int world_step(dWorldID w, dReal h, int stepper)
     if (!w || !(h > 0)) return 0;
     w->to_device();
     w->push_params(stepper);
+    if (w->art_dirty) {                // the articulation joints go to the batch only when they changed
+        w->aj.clear();
+        for (const dxJoint *j : w->arts) {
+            dmxJoint a;
+            memset(&a, 0, sizeof a);
+            a.kind = j->type == dJointTypeHinge ? DMX_JOINT_HINGE : DMX_JOINT_BALL;
+            a.body1 = j->b1 ? j->b1->slot : -1;
+            a.body2 = j->b2 ? j->b2->slot : -1;
+            for (int k = 0; k < 3; k++) { a.anchor1[k] = j->anchor1[k]; a.anchor2[k] = j->anchor2[k]; a.axis1[k] = j->axis1[k]; a.axis2[k] = j->axis2[k]; }
+            w->aj.push_back(a);
+        }
+        DMX_MUST(dmxBatchSetJoints(w->batch, (int64_t)w->aj.size(), w->aj.data()));
+        w->art_dirty = false;
+    }
     w->cj.clear();
     for (const dxJoint *j : w->joints) {
         dmxContactJoint c;
@@ -295,7 +318,12 @@ static int world_step(dWorldID w, dReal h, int stepper)
         c.soft_erp = ct.surface.soft_erp; c.soft_cfm = ct.surface.soft_cfm;
         w->cj.push_back(c);
     }
-    DMX_MUST(dmxBatchStepJoints(w->batch, h, (int64_t)w->cj.size(), w->cj.data()));
+    {
+        const int rc = dmxBatchStepJoints(w->batch, h, (int64_t)w->cj.size(), w->cj.data());
+        // ball / hinge joints under DMX_ROW_ORDER=ode with QuickStep: the batch has said so on stderr; the step fails, the process lives
+        if (rc == DMX_EINVAL && !w->arts.empty()) return 0;
+        if (rc != DMX_OK) fatal("dmxBatchStepJoints", rc);
+    }
     w->dev_newer = true;
     return 1;
 }
@@ -359,6 +387,8 @@ extern "C" void dBodyDestroy(dBodyID b)
     w->to_host();
     for (dxGeom *g : b->geoms) g->body = nullptr;
     for (dxJoint *j : w->joints) { if (j->b1 == b) j->b1 = nullptr; if (j->b2 == b) j->b2 = nullptr; }
+    // its articulation joints are detached on both sides, ODE's limbo: inactive until attached again
+    for (dxJoint *j : w->arts) if (j->b1 == b || j->b2 == b) { j->b1 = j->b2 = nullptr; w->art_dirty = true; }
     w->slots[(size_t)b->slot] = nullptr;
     w->host_dirty = true;
     delete b;
@@ -787,7 +817,11 @@ extern "C" void dJointGroupEmpty(dJointGroupID g)
 {
     if (!g) return;
     for (dxJoint *j : g->joints) {
-        if (j->world) { auto &v = j->world->joints; v.erase(std::remove(v.begin(), v.end(), j), v.end()); }
+        if (j->world) {
+            auto &v = j->type == dJointTypeContact ? j->world->joints : j->world->arts;
+            v.erase(std::remove(v.begin(), v.end(), j), v.end());
+            if (j->type != dJointTypeContact) j->world->art_dirty = true;
+        }
         delete j;
     }
     g->joints.clear();
@@ -808,7 +842,109 @@ extern "C" void dJointAttach(dJointID j, dBodyID b1, dBodyID b2)
 {
     if (!j) return;
     j->b1 = b1; j->b2 = b2;
+    if (j->type != dJointTypeContact) {
+        // a ball or a hinge attached as (0, body): ODE exchanges the two, so that body 1 is the body [ODE-recall dJointAttach, dJOINT_REVERSE]
+        if (!j->b1 && j->b2) { j->b1 = j->b2; j->b2 = nullptr; }
+        if (j->world) j->world->art_dirty = true;
+    }
 }
+
+// ================================================================================ ball and hinge joints
+namespace {
+
+dJointID create_art(dWorldID w, dJointGroupID g, int type)
+{
+    if (!w) return nullptr;
+    dxJoint *j = new dxJoint();
+    j->world = w;
+    j->group = g;
+    j->type = type;
+    w->arts.push_back(j);
+    if (g) g->joints.push_back(j);
+    w->art_dirty = true;
+    return j;
+}
+// a world-frame point / direction into the frame of body b at its current pose, and back (b = 0: the world frame itself)
+void to_body(const dxBody *b, const double in[3], bool point, double out[3])
+{
+    if (!b) { for (int k = 0; k < 3; k++) out[k] = in[k]; return; }
+    double d[3];
+    for (int k = 0; k < 3; k++) d[k] = in[k] - (point ? (double)b->pos[k] : 0.0);
+    for (int k = 0; k < 3; k++) out[k] = (double)b->R[k] * d[0] + (double)b->R[4 + k] * d[1] + (double)b->R[8 + k] * d[2];      // R^T d
+}
+void to_world(const dxBody *b, const double in[3], bool point, dReal out[4])
+{
+    for (int k = 0; k < 3; k++)
+        out[k] = b ? (dReal)((double)b->R[4 * k] * in[0] + (double)b->R[4 * k + 1] * in[1] + (double)b->R[4 * k + 2] * in[2] + (point ? (double)b->pos[k] : 0.0))
+                   : (dReal)in[k];
+}
+void set_anchor(dJointID j, dReal x, dReal y, dReal z)
+{
+    if (!j || j->type == dJointTypeContact) return;
+    if (j->world) j->world->to_host();
+    const double p[3] = { (double)x, (double)y, (double)z };
+    to_body(j->b1, p, true, j->anchor1);
+    to_body(j->b2, p, true, j->anchor2);
+    if (j->world) j->world->art_dirty = true;
+}
+void get_anchor(dJointID j, int side, dVector3 out)
+{
+    if (!j) return;
+    if (j->world) j->world->to_host();
+    to_world(side ? j->b2 : j->b1, side ? j->anchor2 : j->anchor1, true, out);
+}
+
+}  // namespace
+
+extern "C" dJointID dJointCreateBall(dWorldID w, dJointGroupID g) { return create_art(w, g, dJointTypeBall); }
+extern "C" dJointID dJointCreateHinge(dWorldID w, dJointGroupID g) { return create_art(w, g, dJointTypeHinge); }
+extern "C" void dJointDestroy(dJointID j)
+{
+    if (!j) return;
+    if (j->world) {
+        auto &v = j->type == dJointTypeContact ? j->world->joints : j->world->arts;
+        v.erase(std::remove(v.begin(), v.end(), j), v.end());
+        if (j->type != dJointTypeContact) j->world->art_dirty = true;
+    }
+    if (j->group) { auto &v = j->group->joints; v.erase(std::remove(v.begin(), v.end(), j), v.end()); }
+    delete j;
+}
+extern "C" int dJointGetType(dJointID j) { return j ? j->type : dJointTypeNone; }
+extern "C" dBodyID dJointGetBody(dJointID j, int index) { return !j ? nullptr : index == 0 ? j->b1 : index == 1 ? j->b2 : nullptr; }
+extern "C" void dJointSetBallAnchor(dJointID j, dReal x, dReal y, dReal z) { if (j && j->type == dJointTypeBall) set_anchor(j, x, y, z); }
+extern "C" void dJointGetBallAnchor(dJointID j, dVector3 r) { get_anchor(j, 0, r); }
+extern "C" void dJointGetBallAnchor2(dJointID j, dVector3 r) { get_anchor(j, 1, r); }
+extern "C" void dJointSetHingeAnchor(dJointID j, dReal x, dReal y, dReal z) { if (j && j->type == dJointTypeHinge) set_anchor(j, x, y, z); }
+extern "C" void dJointGetHingeAnchor(dJointID j, dVector3 r) { get_anchor(j, 0, r); }
+extern "C" void dJointGetHingeAnchor2(dJointID j, dVector3 r) { get_anchor(j, 1, r); }
+extern "C" void dJointSetHingeAxis(dJointID j, dReal x, dReal y, dReal z)
+{
+    if (!j || j->type != dJointTypeHinge) return;
+    const double l = sqrt((double)x * x + (double)y * y + (double)z * z);
+    if (!(l > 0)) return;
+    if (j->world) j->world->to_host();
+    const double a[3] = { x / l, y / l, z / l };
+    to_body(j->b1, a, false, j->axis1);
+    to_body(j->b2, a, false, j->axis2);
+    if (j->world) j->world->art_dirty = true;
+}
+extern "C" void dJointGetHingeAxis(dJointID j, dVector3 r)
+{
+    if (!j) return;
+    if (j->world) j->world->to_host();
+    to_world(j->b1, j->axis1, false, r);
+}
+// is there a joint between the two bodies (dAreConnectedExcluding: one whose type is not joint_type)?
+extern "C" int dAreConnectedExcluding(dBodyID b1, dBodyID b2, int joint_type)
+{
+    if (!b1 || !b2 || b1->world != b2->world) return 0;
+    const dxWorld *w = b1->world;
+    for (const std::vector<dxJoint *> *v : { &w->arts, &w->joints })
+        for (const dxJoint *j : *v)
+            if (j->type != joint_type && ((j->b1 == b1 && j->b2 == b2) || (j->b1 == b2 && j->b2 == b1))) return 1;
+    return 0;
+}
+extern "C" int dAreConnected(dBodyID b1, dBodyID b2) { return dAreConnectedExcluding(b1, b2, dJointTypeNone); }
 
 // ================================================================================ rotation helpers
 extern "C" void dRSetIdentity(dMatrix3 R) { set_identity(R); }
