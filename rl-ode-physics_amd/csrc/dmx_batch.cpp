@@ -85,14 +85,6 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
     b->device = device;
     b->rsize = precision == DMX_F32 ? 4 : 8;
     b->cfm = precision == DMX_F32 ? 1e-5 : 1e-10;      // dWorldCreate default per precision [ODE]
-    if (const char *v = getenv("DMX_VEC")) b->vec = atoi(v);
-    if (const char *v = getenv("DMX_WIDE")) {            // 1: integrate_free_wide; 2: integrate_free_dma (DMX_WIDE_BLOCKS per CU, default 4)
-        if (atoi(v) == 1) b->vec = -16;
-        if (atoi(v) == 2) { const char *k = getenv("DMX_WIDE_BLOCKS"); const int pc = k ? atoi(k) : 4; b->vec = -(32 + (pc > 0 && pc < 32 ? pc : 4)); }
-    }
-    if (const char *v = getenv("DMX_MIN_WAVES")) b->min_waves = atoi(v);
-    if (const char *v = getenv("DMX_NT")) b->nt = atoi(v);
-    if (const char *v = getenv("DMX_OOP")) b->oop = atoi(v);
     {
         static const int elide_default = [] { const char *e = getenv("DMX_ELIDE"); return e ? atoi(e) & 3 : (DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS); }();
         b->elide = elide_default;
@@ -184,8 +176,7 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
     if (b->slab_alt) (void)hipFree(b->slab_alt);
     if (b->gtype) (void)hipFree(b->gtype);
     if (b->bflags) (void)hipFree(b->bflags);
-    for (dmxBatch::DevBuf *d : { &b->jd_int, &b->jd_real, &b->jd_rows, &b->jd_rowjb, &b->jd_bscr, &b->jd_local, &b->jd_lcp, &b->jd_lcp_off,
-                                &b->jd_lcp_int, &b->jd_order })
+    for (dmxBatch::DevBuf *d : { &b->jd_int, &b->jd_real, &b->jd_rows, &b->jd_rowjb, &b->jd_bscr, &b->jd_local, &b->jd_order })
         if (d->p) (void)hipFree(d->p);
     for (dmxBatch::DevBuf *d : { &b->bp_count, &b->bp_items, &b->bp_flags, &b->bp_inpair, &b->bp_snapshot, &b->hull, &b->cbuf, &b->ccount,
                                 &b->ex_arena, &b->ex_body, &b->ex_last, &b->ex_aabb, &b->sbox, &b->hull_planes, &b->rc_count, &b->rc_items, &b->rc_misc,
@@ -406,13 +397,7 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
         const bool ext = b->ext_pending && s == 0;
         P.ticks = ext ? 1 : std::min(per, nsteps - s);
         T *S = (T *)b->slab + slab_ix(0, first);
-        if (b->oop && first == 0 && count == b->n && !ext) {
-            // experiment (DMX_OOP): read one slab, write the other, swap -- every tick
-            HIP_TRY(launch_step<T>(S, (T *)b->slab_alt, b->gtype, b->stride, count, P, false, b->diag, b->stream));
-            std::swap(b->slab, b->slab_alt);
-        } else {
-            HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream));
-        }
+        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream));
         s += P.ticks;
     }
     b->stepped_with_plane = dmx_fused_contacts(b);

@@ -92,10 +92,6 @@ struct dmxBatch {
     // host-side phase timers of the exact tick (seconds), printed at destroy when DMX_HOST_PROFILE is set
     double prof[12] = { 0 }; bool prof_on = false;
     int ticks_per_launch = 1;        // contact-free ticks fused into one integrate_free launch (dmxBatchSetTicksPerLaunch)
-    int min_waves = 0;               // DMX_MIN_WAVES launch-tuning override (see StepParams)
-    int nt = 0;                      // DMX_NT launch-tuning override (see StepParams)
-    int oop = 0;                     // DMX_OOP=1: the plain (unchecked) loop writes every tick out of place, alternating slabs (experiment)
-    int vec = 0;                     // DMX_VEC launch-tuning override (bodies per lane in integrate_free), 0 = default (1)
     // integrate_free's removals (dmxBatchSetElision; DMX_ELIDE in the environment sets the default): bit 0 = store elision,
     // bit 1 = uniform mass / inertia as kernel arguments.  The trackers follow every upload of the two fields (upload_t).
     int elide = DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS;
@@ -107,8 +103,6 @@ struct dmxBatch {
     std::vector<uint8_t> h_bflags;             // host mirror
     struct DevBuf { void *p = nullptr; size_t bytes = 0; };
     DevBuf jd_int, jd_real, jd_rows, jd_rowjb, jd_bscr, jd_local;   // device staging / scratch
-    DevBuf jd_lcp, jd_lcp_off, jd_lcp_int;     // dWorldStep's exact island solve: A, factor, vectors per island; offsets; pivoting state
-    std::vector<long long> sc_lcp_off;
     std::vector<int> sc_nbd_of, sc_grid_list; std::vector<std::pair<uint64_t, int>> sc_pair_ord;
     void *lcp_grid = nullptr;                  // dWorldStep's grid-wide solve of large islands (dmx_lcp.hip): buffers, remembered active sets
     double exs_acc[64] = { 0 }; long exs_ticks = 0;      // DMX_EXS_TIMING: stage times of the small-scene exact tick, summed
@@ -295,9 +289,6 @@ template <class T> inline StepParams<T> dmx_make_params(dmxBatch *b, double h)
     P.surf_mode = b->surf_mode;
     P.mu = (T)b->mu; P.bounce = (T)b->bounce; P.bounce_vel = (T)b->bounce_vel;
     P.max_contacts = b->max_contacts;
-    P.vec = b->vec;
-    P.min_waves = b->min_waves;
-    P.nt = b->nt;
     P.elide = b->elide;
     // (not while the batch's stream is being captured into a HIP graph: dmx_note_capture)
     P.uni = (b->uni_mass.uniform && b->uni_inertia.uniform && (b->elide & DMX_ELIDE_CONSTANTS) && !b->capturing) ? 1 : 0;

@@ -107,9 +107,6 @@ template <class T> struct StepParams {
     V3<T> pn; T pd;     // plane n.x = d
     int surf_mode; T mu, bounce, bounce_vel;   // contact surface (NearCallback, main.c:684-687)
     int max_contacts;
-    int vec;            // launch tuning (env DMX_VEC): bodies per lane in integrate_free (0 = default, one)
-    int min_waves;      // launch tuning (env DMX_MIN_WAVES): waves per SIMD the register allocator must leave room for, 0 = default
-    int nt;             // launch tuning (env DMX_NT): bit 0 = non-temporal state stores, bit 1 = non-temporal loads (integrate_free)
     int hull_nofilter;  // DMX_HULL_FILTER=0: the hull colliders' conservative filter lets every point through (A/B, diagnosis)
     int bp_check;       // safe-zone test of every body's pre-step position (BPC_* bits; any bit = "this tick" for one-tick kernels)
     int ticks;          // integrate_free: ticks taken by one launch with the state held in registers (>= 1)
@@ -222,11 +219,10 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
 template <class T>
 hipError_t launch_islands(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                           StepDiag *diag, hipStream_t st);
-// dWorldStep: every island with rows is solved exactly (boxed LCP, block principal pivoting) by one workgroup;
-// scratch = per island 2 m^2 + 3 m reals at scratch_off[k] (k = index in I.big_list), iscratch = 9 ints per reserved row
+// dWorldStep: solve_islands for the islands without rows only (those with rows: launch_lcp_lds / lcp_grid_solve, dmx_lcp.hpp)
 template <class T>
-hipError_t launch_islands_exact(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
-                                StepDiag *diag, T *scratch, const long long *scratch_off, int *iscratch, int max_rows, hipStream_t st);
+hipError_t launch_islands_without_rows(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
+                                       StepDiag *diag, hipStream_t st);
 // bucket counts and flags to zero, and two optional small records (each at most 256 words) with them
 hipError_t launch_bp_clear(uint32_t *count, size_t n_count, uint32_t *flags, void *rec_a, size_t bytes_a, void *rec_b, size_t bytes_b,
                            hipStream_t st);

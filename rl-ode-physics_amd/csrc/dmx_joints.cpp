@@ -21,13 +21,6 @@ namespace {
 // off with a wavefront: 500-body reference scene 5.2 / 3.3 / 2.4 / 1.7 / 1.3 / 1.1 / 0.8 ms per tick at 384 / 128 / 64 / 32 / 16 /
 // 8 / 4 rows (profiles/r01_big_island_threshold.txt), 0.90 -> 0.67 from 4 to 1 with the one-body islands on solve_singles
 // (profiles/r02_island_threshold.txt).
-// DMX_LCP_OLD=1: dWorldStep's islands below the grid threshold go to round 2's one-workgroup kernel (lcp_island_wg) -- for A/B runs
-bool lcp_old_kernel()
-{
-    static const bool v = [] { const char *e = getenv("DMX_LCP_OLD"); return e && atoi(e) != 0; }();
-    return v;
-}
-
 int big_island_rows()
 {
     static const int v = [] { const char *e = getenv("DMX_BIG_ISLAND_ROWS"); return e ? atoi(e) : 1; }();
@@ -257,7 +250,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 !cj[(size_t)con_sorted[(size_t)con_start[(size_t)i]]].unit) continue;
             // dWorldStep, an island of hundreds of rows or more: the grid-wide solve (dmx_lcp.hip), not one workgroup
             // (small and medium ones: one workgroup, the whole solve in LDS, while it fits)
-            if (exact && !lcp_old_kernel() && !lcp_lds_fits((int)sizeof(T), m_of[(size_t)i], nbd_of[(size_t)i])) { grid_list.push_back(i); continue; }
+            if (exact && !lcp_lds_fits((int)sizeof(T), m_of[(size_t)i], nbd_of[(size_t)i])) { grid_list.push_back(i); continue; }
             if (exact && m_of[(size_t)i] >= lcp_grid_threshold()) { grid_list.push_back(i); continue; }
             if (exact) lds_need = std::max(lds_need, lcp_lds_need((int)sizeof(T), m_of[(size_t)i], nbd_of[(size_t)i]));
             big_list_h.push_back(i);
@@ -268,15 +261,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         }
         const int nbig = (int)big_list_h.size();
         if (exact) {
-            // no level schedules: the exact solve is not a sweep.  Per-island scratch offsets instead (2 m^2 + 3 m reals).
-            b->sc_lcp_off.resize((size_t)nbig + 1);
-            long long at = 0;
-            for (int k = 0; k < nbig; k++) {
-                b->sc_lcp_off[(size_t)k] = at;
-                const long long m = m_of[(size_t)big_list_h[(size_t)k]];
-                at += 2 * m * m + 3 * m;
-            }
-            b->sc_lcp_off[(size_t)nbig] = at;
+            // no level schedules: the exact solve is not a sweep
             lev_count_h.assign((size_t)nbig, 0);
             for (int k = 0; k < nbig; k++) big_h[(size_t)big_list_h[(size_t)k]] = 0;
             for (int i : grid_list) big_h[(size_t)i] = 0;         // (not the lane-per-island kernel's either)
@@ -356,7 +341,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     else if (nlive > SMALL_MAX_BODIES || n > 8 * SMALL_MAX_BODIES) why = DMX_SMALL_TICK_STAT_BODIES;      // (the mirror and its fill cover the capacity)
     else if (ni > SMALL_MAX_ISLANDS) why = DMX_SMALL_TICK_STAT_ISLANDS;
     else if (!exact && big_max_rows > WAVE_ISLAND_ROWS) why = DMX_SMALL_TICK_STAT_SOR_ROWS;            // (the one-wavefront form of solve_island_wg)
-    else if (exact && (!grid_list.empty() || lcp_old_kernel())) why = DMX_SMALL_TICK_STAT_LDS_FIT;
+    else if (exact && !grid_list.empty()) why = DMX_SMALL_TICK_STAT_LDS_FIT;
     const bool small = why < 0;
     b->small_stats[small ? DMX_SMALL_TICK_STAT_SMALL : DMX_SMALL_TICK_STAT_GENERAL]++;
     if (!small) b->small_stats[why]++;
@@ -544,10 +529,6 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             lcp_lds_knobs((int)sizeof(T), &K.murty, &tol);
             K.tol_rel = (T)tol;
             lds = lds_need;
-            // (the general exact tick's scratch, kept sized like the staging: not used here)
-            if ((rc = dmx_ensure_dev(b->jd_lcp, (size_t)(b->sc_lcp_off[(size_t)n_big] + 1) * sizeof(T))) != DMX_OK) return rc;
-            if ((rc = dmx_ensure_dev(b->jd_lcp_off, ((size_t)n_big + 1) * sizeof(long long))) != DMX_OK) return rc;
-            if ((rc = dmx_ensure_dev(b->jd_lcp_int, (nrows + 1) * 3 * sizeof(int))) != DMX_OK) return rc;
         } else {
             lds = small_tick_sor_lds((int)sizeof(T), big_max_bodies, &K.lds_bodies);
         }
@@ -568,17 +549,12 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     b->last_small = false;
     HIP_TRY(hipMemsetAsync(b->diag_isl, 0, sizeof(StepDiag), b->stream));
     if (exact) {
-        const size_t nbig = (size_t)n_big;
-        if ((rc = dmx_ensure_dev(b->jd_lcp, (size_t)(b->sc_lcp_off[nbig] + 1) * sizeof(T))) != DMX_OK) return rc;
-        if ((rc = dmx_ensure_dev(b->jd_lcp_off, (nbig + 1) * sizeof(long long))) != DMX_OK) return rc;
-        if ((rc = dmx_ensure_dev(b->jd_lcp_int, (nrows + 1) * 3 * sizeof(int))) != DMX_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(b->jd_lcp_off.p, b->sc_lcp_off.data(), (nbig + 1) * sizeof(long long), hipMemcpyHostToDevice, b->stream));
-        int max_rows = 0;
-        for (int k = 0; k < n_big; k++) max_rows = std::max(max_rows, b->sc_iv[10][(size_t)big_list_h[(size_t)k]]);
-        HIP_TRY(launch_islands_exact<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, (T *)b->jd_lcp.p,
-                                        (const long long *)b->jd_lcp_off.p, (int *)b->jd_lcp_int.p, lcp_old_kernel() ? max_rows : -1, b->stream));
-        if (!lcp_old_kernel()) HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));      // sc_lcp_off is pageable host memory: the copy must have read it before the next tick rewrites it
+        HIP_TRY(launch_islands_without_rows<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream));
+        HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream));
+        // Written for a copy from pageable host memory that is gone; but the grid solves' host loop below and the next tick's
+        // rewrite of the host staging have run behind this wait ever since, and no test tells a missing wait from a present one.
+        // Taking it out is a change of speed, to be made and measured on its own.
+        HIP_TRY(hipStreamSynchronize(b->stream));
         if (!grid_list.empty()) {
             // the large islands, one after the other: per row whether it can ever clamp, and the key its active-set state is
             // remembered under -- (body pair, ordinal of the contact within the pair this tick, row of the contact)

@@ -9,7 +9,7 @@
 // Data layout: one slab `S` of `real` in tiles of 64 bodies x 30 components
 // (dmx_internal.hpp: component c of body i at S[slab_ix(c, i)]), so that a
 // wavefront's 30 component accesses fall in one contiguous 7.5 KiB (f32) run.
-// A lane owns V consecutive bodies (V divides the tile).
+// A lane owns one body.
 //
 // No MFMA: there is no dense contraction on this path.  integrate_free is
 // HBM-bound (at most 30 reals per body-step, 19 on a dropped unit-mass scene:
@@ -24,36 +24,6 @@
 
 namespace dmx {
 
-template <class T, int V> struct alignas(sizeof(T) * V) Pack { T v[V]; };
-
-template <class T, int V>
-__device__ __forceinline__ Pack<T, V> ldv(const T *__restrict__ base, int64_t stride, int comp, int64_t i)
-{
-    return *reinterpret_cast<const Pack<T, V> *>(base + slab_ix(comp, i));
-}
-template <class T, int V>
-__device__ __forceinline__ void stv(T *__restrict__ base, int64_t stride, int comp, int64_t i, const Pack<T, V> &p)
-{
-    *reinterpret_cast<Pack<T, V> *>(base + slab_ix(comp, i)) = p;
-}
-// the same with the non-temporal hint (streamed once: do not keep the line in cache); launch tuning, StepParams::nt
-template <class T, int V>
-__device__ __forceinline__ Pack<T, V> ldv_nt(const T *base, int64_t stride, int comp, int64_t i)
-{
-    Pack<T, V> p;
-    const T *a = base + slab_ix(comp, i);
-#pragma unroll
-    for (int b = 0; b < V; b++) p.v[b] = __builtin_nontemporal_load(a + b);
-    return p;
-}
-template <class T, int V>
-__device__ __forceinline__ void stv_nt(T *base, int64_t stride, int comp, int64_t i, const Pack<T, V> &p)
-{
-    T *a = base + slab_ix(comp, i);
-#pragma unroll
-    for (int b = 0; b < V; b++) __builtin_nontemporal_store(p.v[b], a + b);
-}
-
 // ---------------------------------------------------------------------------------------------
 // integrate_free: contact-free tick (BASELINE config 2/4).  Algorithmic traffic per body-step, at most:
 // read 13 state + 4 constant reals, write 13 state reals = 30 reals (120 B f32 / 240 B f64).
@@ -67,8 +37,7 @@ __device__ __forceinline__ void stv_nt(T *base, int64_t stride, int comp, int64_
 //              as kernel arguments (StepParams::uni_mass / uni_inertia) and components 13..16 are not loaded.
 // A dropped scene of unit-mass bodies under gravity along y (the reference's AddBody + dWorldSetGravity) then moves
 // 13 reals in and 6 out (pos.y, quat, lvel.y) = 19 per body-step; any other scene moves what it changes, up to the 30.
-// Same values into the same free_body_step either way: same bits.  OPT != 0 exists for V = 1 and the default launch
-// bound only; the DMX_VEC / DMX_MIN_WAVES tuning experiments run the OPT = 0 instantiations (all loads, all stores).
+// Same values into the same free_body_step either way: same bits.
 // ---------------------------------------------------------------------------------------------
 enum : int { OPT_ELIDE = 1, OPT_UNI = 2 };
 template <class T> struct BitsOf;
@@ -80,9 +49,8 @@ template <class T> __device__ __forceinline__ bool bits_differ(T a, T b)
     return __builtin_bit_cast(U, a) != __builtin_bit_cast(U, b);
 }
 
-template <class T, int V, bool EXT, int MINW, bool MULTI, int OPT = 0>
-__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t stride, int64_t nvec,
-                                                      StepParams<T> P)
+template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0>
+__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P)
 {
     constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
     constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
@@ -91,244 +59,69 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
     if (P.gate != nullptr && *P.gate == 0u) return;
     const int nticks = MULTI ? P.ticks : 1;         // MULTI = false: the one-tick kernel, no loop
     const bool in_place = ELIDE && So == S;         // wave-uniform: two kernel arguments
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nvec;
-         t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = t * V;
-        if (V == 1 && P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
-        Pack<T, V> c[NLOAD];
-        if (P.nt & 2) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
+        T c[NLOAD];
 #pragma unroll
-            for (int k = 0; k < NLOAD; k++) c[k] = ldv_nt<T, V>(S, stride, k, i);
-        } else {
-#pragma unroll
-            for (int k = 0; k < NLOAD; k++) c[k] = ldv<T, V>(S, stride, k, i);
-        }
-        Pack<T, V> was[ELIDE ? C_MASS : 1];          // the state as loaded, to tell which components the launch changed
+        for (int k = 0; k < NLOAD; k++) c[k] = S[slab_ix(k, i)];
+        T was[ELIDE ? C_MASS : 1];          // the state as loaded, to tell which components the launch changed
         if constexpr (ELIDE) {
 #pragma unroll
             for (int k = 0; k < C_MASS; k++) was[k] = c[k];
         }
-        Pack<T, V> bx, bz, bs;
-        if (P.bp_check) {
-            bx = ldv<T, V>(S, stride, C_BPX, i); bz = ldv<T, V>(S, stride, C_BPZ, i); bs = ldv<T, V>(S, stride, C_BPSAFE, i);
-        }
-        Pack<T, V> f[6];
+        T bx, bz, bs;
+        if (P.bp_check) { bx = S[slab_ix(C_BPX, i)]; bz = S[slab_ix(C_BPZ, i)]; bs = S[slab_ix(C_BPSAFE, i)]; }
+        T f[6];
         if (EXT) {
 #pragma unroll
-            for (int k = 0; k < 6; k++) f[k] = ldv<T, V>(S, stride, C_FORCE + k, i);
+            for (int k = 0; k < 6; k++) f[k] = S[slab_ix(C_FORCE + k, i)];
         }
         // P.ticks ticks with the state in registers: one read and one write of the state per launch, not per tick
         for (int s = 0; s < nticks; s++) {
             if (P.bp_check && ((P.bp_check & BPC_ALL) || (s == 0 && (P.bp_check & BPC_FIRST)) ||
                                (s == nticks - 1 && (P.bp_check & BPC_LAST)))) {
                 // dSpaceCollide for body-body pairs, by proof: a body inside its safe zone cannot touch any other
-                int zs = 0;
-#pragma unroll
-                for (int b = 0; b < V; b++) {
-                    int z = zone_state(c[C_POS].v[b] - bx.v[b], c[C_POS + 2].v[b] - bz.v[b], bs.v[b]);
-                    if (P.n_static > 0) {
-                        const int z2 = static_state(P, c[C_POS].v[b], c[C_POS + 1].v[b], c[C_POS + 2].v[b], S[slab_ix(C_BPR, i + b)]);
-                        z = z2 > z ? z2 : z;
-                    }
-                    zs = z > zs ? z : zs;
+                int z = zone_state(c[C_POS] - bx, c[C_POS + 2] - bz, bs);
+                if (P.n_static > 0) {
+                    const int z2 = static_state(P, c[C_POS], c[C_POS + 1], c[C_POS + 2], S[slab_ix(C_BPR, i)]);
+                    z = z2 > z ? z2 : z;
                 }
-                report_zone(zs, P.bp_flags);
+                report_zone(z, P.bp_flags);
             }
-#pragma unroll
-            for (int b = 0; b < V; b++) {
-                V3<T> x = { c[C_POS].v[b], c[C_POS + 1].v[b], c[C_POS + 2].v[b] };
-                Q4<T> q = { c[C_QUAT].v[b], c[C_QUAT + 1].v[b], c[C_QUAT + 2].v[b], c[C_QUAT + 3].v[b] };
-                V3<T> v = { c[C_LVEL].v[b], c[C_LVEL + 1].v[b], c[C_LVEL + 2].v[b] };
-                V3<T> w = { c[C_AVEL].v[b], c[C_AVEL + 1].v[b], c[C_AVEL + 2].v[b] };
-                T mass;
-                V3<T> Ib;
-                if constexpr (UNI) { mass = P.uni_mass; Ib = P.uni_inertia; }
-                else { mass = c[C_MASS].v[b]; Ib = { c[C_INERTIA].v[b], c[C_INERTIA + 1].v[b], c[C_INERTIA + 2].v[b] }; }
-                V3<T> facc = { T(0), T(0), T(0) }, tacc = { T(0), T(0), T(0) };
-                if (EXT && s == 0) {                       // the accumulators act in the first tick and are cleared by it
-                    facc = { f[0].v[b], f[1].v[b], f[2].v[b] };
-                    tacc = { f[3].v[b], f[4].v[b], f[5].v[b] };
-                }
-                free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
-                if (s == nticks - 1) pack_boundary(P, i + b, x, q, v, w);
-                c[C_POS].v[b] = x.x; c[C_POS + 1].v[b] = x.y; c[C_POS + 2].v[b] = x.z;
-                c[C_QUAT].v[b] = q.w; c[C_QUAT + 1].v[b] = q.x; c[C_QUAT + 2].v[b] = q.y; c[C_QUAT + 3].v[b] = q.z;
-                c[C_LVEL].v[b] = v.x; c[C_LVEL + 1].v[b] = v.y; c[C_LVEL + 2].v[b] = v.z;
-                c[C_AVEL].v[b] = w.x; c[C_AVEL + 1].v[b] = w.y; c[C_AVEL + 2].v[b] = w.z;
+            V3<T> x = { c[C_POS], c[C_POS + 1], c[C_POS + 2] };
+            Q4<T> q = { c[C_QUAT], c[C_QUAT + 1], c[C_QUAT + 2], c[C_QUAT + 3] };
+            V3<T> v = { c[C_LVEL], c[C_LVEL + 1], c[C_LVEL + 2] };
+            V3<T> w = { c[C_AVEL], c[C_AVEL + 1], c[C_AVEL + 2] };
+            T mass;
+            V3<T> Ib;
+            if constexpr (UNI) { mass = P.uni_mass; Ib = P.uni_inertia; }
+            else { mass = c[C_MASS]; Ib = { c[C_INERTIA], c[C_INERTIA + 1], c[C_INERTIA + 2] }; }
+            V3<T> facc = { T(0), T(0), T(0) }, tacc = { T(0), T(0), T(0) };
+            if (EXT && s == 0) {                       // the accumulators act in the first tick and are cleared by it
+                facc = { f[0], f[1], f[2] };
+                tacc = { f[3], f[4], f[5] };
             }
+            free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
+            if (s == nticks - 1) pack_boundary(P, i, x, q, v, w);
+            c[C_POS] = x.x; c[C_POS + 1] = x.y; c[C_POS + 2] = x.z;
+            c[C_QUAT] = q.w; c[C_QUAT + 1] = q.x; c[C_QUAT + 2] = q.y; c[C_QUAT + 3] = q.z;
+            c[C_LVEL] = v.x; c[C_LVEL + 1] = v.y; c[C_LVEL + 2] = v.z;
+            c[C_AVEL] = w.x; c[C_AVEL + 1] = w.y; c[C_AVEL + 2] = w.z;
         }
 #pragma unroll
         for (int k = 0; k < C_MASS; k++) {
             if constexpr (ELIDE) if (in_place) {
-                bool changed = false;
-#pragma unroll
-                for (int b = 0; b < V; b++) changed |= bits_differ(c[k].v[b], was[k].v[b]);
-                if (__ballot(changed) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
+                if (__ballot(bits_differ(c[k], was[k])) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
             }
-            if (P.nt & 1) stv_nt<T, V>(So, stride, k, i, c[k]);
-            else          stv<T, V>(So, stride, k, i, c[k]);
+            So[slab_ix(k, i)] = c[k];
         }
         if (EXT) {
-            Pack<T, V> z;
 #pragma unroll
-            for (int b = 0; b < V; b++) z.v[b] = T(0);
-#pragma unroll
-            for (int k = 0; k < 6; k++) stv<T, V>(S, stride, C_FORCE + k, i, z);
+            for (int k = 0; k < 6; k++) S[slab_ix(C_FORCE + k, i)] = T(0);
         }
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// integrate_free_wide: the same contact-free tick with the tile moved in 16-byte pieces.  integrate_free's lanes load and store
-// one real each (a wavefront's request is 256 B); here a wavefront streams its tile's 17 input components as ONE flat run in
-// dwordx4 pieces (1 KiB per request) into LDS, every lane picks its body's components out of LDS, steps it, and the 13 new
-// state components go back through LDS and out as dwordx4 stores.  Same arithmetic (free_body_step), same bits; an experiment
-// on the memory system's request granularity (DMX_WIDE=1; DESIGN.md section 4, HBM-resident sizes).
-// ---------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void integrate_free_wide(T *S, T *So, int64_t ntiles, StepParams<T> P)
-{
-    constexpr int W16 = 16 / sizeof(T);                       // reals per 16-byte piece
-    constexpr int IN = C_SIDES * SLAB_TILE, OUT = C_MASS * SLAB_TILE;      // reals in, reals out per tile
-    __shared__ __align__(16) T stage[4][IN];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    const bool live = tile < ntiles;
-    T *ls = stage[wv];
-    const int64_t base = tile * (int64_t)(C_COUNT * SLAB_TILE);
-    if (live) {
-#pragma unroll
-        for (int k = 0; k * 64 * W16 < IN; k++) {
-            const int f = (k * 64 + lane) * W16;
-            if (f < IN) *reinterpret_cast<Pack<T, W16> *>(ls + f) = *reinterpret_cast<const Pack<T, W16> *>(S + base + f);
-        }
-    }
-    __syncthreads();
-    T c[C_SIDES];
-#pragma unroll
-    for (int k = 0; k < C_SIDES; k++) c[k] = ls[k * SLAB_TILE + lane];
-    __syncthreads();
-    const int64_t i = tile * SLAB_TILE + lane;
-    if (live) {
-        if (P.bp_check) {
-            int z = zone_state(c[C_POS] - S[slab_ix(C_BPX, i)], c[C_POS + 2] - S[slab_ix(C_BPZ, i)], S[slab_ix(C_BPSAFE, i)]);
-            if (P.n_static > 0) {
-                const int z2 = static_state(P, c[C_POS], c[C_POS + 1], c[C_POS + 2], S[slab_ix(C_BPR, i)]);
-                z = z2 > z ? z2 : z;
-            }
-            report_zone(z, P.bp_flags);
-        }
-        V3<T> x = { c[C_POS], c[C_POS + 1], c[C_POS + 2] };
-        Q4<T> q = { c[C_QUAT], c[C_QUAT + 1], c[C_QUAT + 2], c[C_QUAT + 3] };
-        V3<T> v = { c[C_LVEL], c[C_LVEL + 1], c[C_LVEL + 2] };
-        V3<T> w = { c[C_AVEL], c[C_AVEL + 1], c[C_AVEL + 2] };
-        const V3<T> Ib = { c[C_INERTIA], c[C_INERTIA + 1], c[C_INERTIA + 2] };
-        free_body_step(x, q, v, w, c[C_MASS], Ib, V3<T>{ T(0), T(0), T(0) }, V3<T>{ T(0), T(0), T(0) }, P.g, P.h, P.gyro);
-        pack_boundary(P, i, x, q, v, w);
-        ls[(C_POS + 0) * SLAB_TILE + lane] = x.x; ls[(C_POS + 1) * SLAB_TILE + lane] = x.y; ls[(C_POS + 2) * SLAB_TILE + lane] = x.z;
-        ls[(C_QUAT + 0) * SLAB_TILE + lane] = q.w; ls[(C_QUAT + 1) * SLAB_TILE + lane] = q.x;
-        ls[(C_QUAT + 2) * SLAB_TILE + lane] = q.y; ls[(C_QUAT + 3) * SLAB_TILE + lane] = q.z;
-        ls[(C_LVEL + 0) * SLAB_TILE + lane] = v.x; ls[(C_LVEL + 1) * SLAB_TILE + lane] = v.y; ls[(C_LVEL + 2) * SLAB_TILE + lane] = v.z;
-        ls[(C_AVEL + 0) * SLAB_TILE + lane] = w.x; ls[(C_AVEL + 1) * SLAB_TILE + lane] = w.y; ls[(C_AVEL + 2) * SLAB_TILE + lane] = w.z;
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll
-        for (int k = 0; k * 64 * W16 < OUT; k++) {
-            const int f = (k * 64 + lane) * W16;
-            if (f < OUT) *reinterpret_cast<Pack<T, W16> *>(So + base + f) = *reinterpret_cast<const Pack<T, W16> *>(ls + f);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// integrate_free_dma: the contact-free tick with its READS taken off the register path.  A persistent grid; every wavefront walks
-// tiles, and a tile's 17 input components -- one flat run of the slab -- arrive by LDS-DMA (global_load_lds_dwordx4: 1 KiB per
-// request, no VGPR held while in flight) into one of the wave's two LDS buffers while the wave steps the tile before it: two
-// tiles of reads in flight per wave.  The counters behind this (profiles/r03_tcc_counters_16Mi.txt): at HBM-resident sizes the
-// pass is bound by how many read requests a compute unit keeps in flight (about 110-125 of 128 B through the vector L1), not by
-// DRAM credits or by request size.  Same arithmetic (free_body_step), same bits (DMX_WIDE=2).
-// ---------------------------------------------------------------------------------------------
-template <class T> __device__ __forceinline__ void dma_tile_in(const T *src, T *lds, int lane)
-{
-    constexpr int BYTES = C_SIDES * SLAB_TILE * (int)sizeof(T), FULL = BYTES / 1024, REM4 = (BYTES - FULL * 1024) / 256;
-    const char *g = reinterpret_cast<const char *>(src);
-    char *l = reinterpret_cast<char *>(lds);
-#pragma unroll
-    for (int k = 0; k < FULL; k++)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + k * 1024 + lane * 16),
-                                         (__attribute__((address_space(3))) void *)(l + k * 1024), 16, 0, 0);
-#pragma unroll
-    for (int k = 0; k < REM4; k++)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + FULL * 1024 + k * 256 + lane * 4),
-                                         (__attribute__((address_space(3))) void *)(l + FULL * 1024 + k * 256), 4, 0, 0);
-}
-template <class T> constexpr int dma_loads_per_tile()
-{
-    return (C_SIDES * SLAB_TILE * (int)sizeof(T)) / 1024 + ((C_SIDES * SLAB_TILE * (int)sizeof(T)) % 1024) / 256;
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void integrate_free_dma(T *S, T *So, int64_t ntiles, StepParams<T> P)
-{
-    constexpr int IN = C_SIDES * SLAB_TILE;
-    extern __shared__ __align__(16) unsigned char dma_raw[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T *buf0 = reinterpret_cast<T *>(dma_raw) + (size_t)(2 * wv) * IN, *buf1 = buf0 + IN;
-    const int64_t step = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    if (tile >= ntiles) return;
-    constexpr int TILE_REALS = C_COUNT * SLAB_TILE;
-    // counted waits need every vector-memory operation between two waits to be known: the 13 state stores and the next tile's
-    // loads.  Ticks that also test zones or pack boundary rows (chunk ends, exchange ticks) wait for everything instead.
-    const bool counted = !P.bp_check && P.pack_out == nullptr;
-    dma_tile_in<T>(S + tile * TILE_REALS, buf0, lane);
-    int cur = 0;
-    bool first = true;
-    for (; tile < ntiles; tile += step, cur ^= 1) {
-        T *ls = cur ? buf1 : buf0;
-        const int64_t next = tile + step;
-        if (next < ntiles) dma_tile_in<T>(S + next * TILE_REALS, cur ? buf0 : buf1, lane);
-        // this tile's loads are older than: the tile before's 13 stores and the next tile's loads (vmcnt counts them all, in order)
-        // (the wave's first tile has no stores before it)
-        if (!counted) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (first) {
-            if (next >= ntiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (sizeof(T) == 4) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        } else if (next < ntiles) {
-            if (sizeof(T) == 4) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");      // 13 + 5
-            else                asm volatile("s_waitcnt vmcnt(23)" ::: "memory");      // 13 + 10
-        } else asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-        first = false;
-        T c[C_SIDES];
-#pragma unroll
-        for (int k = 0; k < C_SIDES; k++) c[k] = ls[k * SLAB_TILE + lane];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // in registers before the buffer is handed to the tile after next
-        const int64_t i = tile * SLAB_TILE + lane;
-        if (P.bp_check) {
-            int z = zone_state(c[C_POS] - S[slab_ix(C_BPX, i)], c[C_POS + 2] - S[slab_ix(C_BPZ, i)], S[slab_ix(C_BPSAFE, i)]);
-            if (P.n_static > 0) {
-                const int z2 = static_state(P, c[C_POS], c[C_POS + 1], c[C_POS + 2], S[slab_ix(C_BPR, i)]);
-                z = z2 > z ? z2 : z;
-            }
-            report_zone(z, P.bp_flags);
-        }
-        V3<T> x = { c[C_POS], c[C_POS + 1], c[C_POS + 2] };
-        Q4<T> q = { c[C_QUAT], c[C_QUAT + 1], c[C_QUAT + 2], c[C_QUAT + 3] };
-        V3<T> v = { c[C_LVEL], c[C_LVEL + 1], c[C_LVEL + 2] };
-        V3<T> w = { c[C_AVEL], c[C_AVEL + 1], c[C_AVEL + 2] };
-        const V3<T> Ib = { c[C_INERTIA], c[C_INERTIA + 1], c[C_INERTIA + 2] };
-        free_body_step(x, q, v, w, c[C_MASS], Ib, V3<T>{ T(0), T(0), T(0) }, V3<T>{ T(0), T(0), T(0) }, P.g, P.h, P.gyro);
-        pack_boundary(P, i, x, q, v, w);
-        So[slab_ix(C_POS + 0, i)] = x.x; So[slab_ix(C_POS + 1, i)] = x.y; So[slab_ix(C_POS + 2, i)] = x.z;
-        So[slab_ix(C_QUAT + 0, i)] = q.w; So[slab_ix(C_QUAT + 1, i)] = q.x;
-        So[slab_ix(C_QUAT + 2, i)] = q.y; So[slab_ix(C_QUAT + 3, i)] = q.z;
-        So[slab_ix(C_LVEL + 0, i)] = v.x; So[slab_ix(C_LVEL + 1, i)] = v.y; So[slab_ix(C_LVEL + 2, i)] = v.z;
-        So[slab_ix(C_AVEL + 0, i)] = w.x; So[slab_ix(C_AVEL + 1, i)] = w.y; So[slab_ix(C_AVEL + 2, i)] = w.z;
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // step_plane: fused tick for single-body islands resting on / falling onto the ground plane
@@ -734,79 +527,50 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
             else     hipLaunchKernelGGL((step_contacts<T, false, 1, 8>), dim3(grid), dim3(256), 0, st, S, So, n, P, diag);
         }
     } else if (!P.plane_on) {
-        constexpr int VMAX = 16 / sizeof(T);
-        // default: one body per lane.  On the tiled slab a wave's loads (17, or 13 when the constants are arguments) already
-        // cover one contiguous run, so wider per-lane loads buy nothing, and V = 1 keeps the f32 kernel at 7 waves/SIMD (71 VGPRs
+        // One body per lane.  On the tiled slab a wave's loads (17, or 13 when the constants are arguments) already cover one
+        // contiguous run, so wider per-lane loads buy nothing, and one body keeps the f32 kernel at 7 waves/SIMD (71 VGPRs
         // with every load and store, 72 in the default instantiation below): measured, on the kernel moving all 30 reals,
-        // 21.1 / 22.2 / 22.4 us per tick for V = 1 / 2 / 4 at 1 Mi f32 bodies (profiles/r01_integrate_free_tiled_sweep.txt).
-        const int VDEF = 1;
-        const int V = P.skip != nullptr ? 1 : (P.vec == 1 || P.vec == 2 || P.vec == VMAX) ? P.vec : VDEF;
-        const int64_t nvec = (n + V - 1) / V;     // pad bodies up to `stride` are valid memory
-        const unsigned grid = blocks_for(nvec, 256);
-        if (P.vec <= -32 && P.ticks == 1 && !ext && P.skip == nullptr) {      // DMX_WIDE=2[:blocks per CU]: reads by LDS-DMA, persistent grid
-            const int64_t ntiles = (n + SLAB_TILE - 1) / SLAB_TILE;
-            const int per_cu = (-P.vec) / 32 > 0 ? ((-P.vec) % 32 == 0 ? 4 : (-P.vec) % 32) : 4;
-            const size_t lds = (size_t)4 * 2 * C_SIDES * SLAB_TILE * sizeof(T);
-            const hipError_t ea = hipFuncSetAttribute((const void *)integrate_free_dma<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (ea != hipSuccess) return ea;
-            int64_t blocks = (ntiles + 3) / 4;
-            if (blocks > (int64_t)256 * per_cu) blocks = (int64_t)256 * per_cu;
-            hipLaunchKernelGGL((integrate_free_dma<T>), dim3((unsigned)blocks), dim3(256), lds, st, S, So, ntiles, P);
-            return hipGetLastError();
-        }
-        if (P.vec == -16 && P.ticks == 1 && !ext && P.skip == nullptr) {      // DMX_WIDE=1: the tile in 16-byte pieces through LDS
-            const int64_t ntiles = (n + SLAB_TILE - 1) / SLAB_TILE;
-            hipLaunchKernelGGL((integrate_free_wide<T>), dim3(blocks_for(ntiles, 4)), dim3(256), 0, st, S, So, ntiles, P);
-            return hipGetLastError();
-        }
-#define DMX_LAUNCH_FREE(VV, MW, OO, MWX)                                                                               \
-    do {                                                                                                             \
-        if (P.ticks > 1) hipLaunchKernelGGL((integrate_free<T, VV, false, MWX, true, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);   \
-        else if (ext) hipLaunchKernelGGL((integrate_free<T, VV, true, MWX, false, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P);  \
-        else     hipLaunchKernelGGL((integrate_free<T, VV, false, MW, false, OO>), dim3(grid), dim3(256), 0, st, S, So, stride, nvec, P); \
-    } while (0)
-        const int mw = P.min_waves;   // launch tuning: minimum waves per SIMD the register allocator must leave room for
+        // 21.1 / 22.2 / 22.4 us per tick for 1 / 2 / 4 bodies per lane at 1 Mi f32 bodies
+        // (profiles/r01_integrate_free_tiled_sweep.txt).  Pad bodies up to `stride` are valid memory.
+        const unsigned grid = blocks_for(n, 256);
         // what the result does not need (the kernel's header): store elision, and constants as arguments when the batch's are uniform.
         // The constants' scalars cost the f32 one-tick kernel three registers (71 -> 74 VGPRs = 6 waves per SIMD): a launch bound
         // of 7 waves (MWU) makes the allocator fit them into the 72 that 7 waves allow, without scratch; the kernels with force
-        // accumulators or many ticks would spill under that bound and keep the default one (MWX).  The many-ticks-per-launch
+        // accumulators or many ticks would spill under that bound and keep the default one.  The many-ticks-per-launch
         // kernel (VALU-bound, one store per `ticks` ticks) keeps its unconditional stores: the copy of the loaded state would
-        // cost it a wave per SIMD (84 -> 97 VGPRs) for a store it rarely issues, while the constants alone free registers
-        // (84 -> 79); a build with the elision in it measured the same within the spread at 32 ticks per launch
+        // cost it a wave per SIMD (78 -> 91 VGPRs, 6 -> 5 waves) for a store it rarely issues, while the constants as arguments
+        // cost it none (78 -> 79); a build with the elision in it measured the same within the spread at 32 ticks per launch
         // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
         constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
-        int opt = (V == 1 && mw != 8 && mw != 6) ? ((P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0)) : 0;
-        if (P.ticks > 1) opt &= OPT_UNI;
-        if (opt == 3) DMX_LAUNCH_FREE(1, MWU, 3, 1);
-        else if (opt == 2) DMX_LAUNCH_FREE(1, MWU, 2, 1);
-        else if (opt == 1) DMX_LAUNCH_FREE(1, 1, 1, 1);
-        else if (V == 1) { if (mw == 8) DMX_LAUNCH_FREE(1, 8, 0, 8); else if (mw == 6) DMX_LAUNCH_FREE(1, 6, 0, 6); else DMX_LAUNCH_FREE(1, 1, 0, 1); }
-        else if (V == 2) { if (mw == 4) DMX_LAUNCH_FREE(2, 4, 0, 4); else if (mw == 5) DMX_LAUNCH_FREE(2, 5, 0, 5); else if (mw == 6) DMX_LAUNCH_FREE(2, 6, 0, 6); else DMX_LAUNCH_FREE(2, 1, 0, 1); }
-        else { if (mw == 4) DMX_LAUNCH_FREE(VMAX, 4, 0, 4); else if (mw == 3) DMX_LAUNCH_FREE(VMAX, 3, 0, 3); else DMX_LAUNCH_FREE(VMAX, 1, 0, 1); }
-#undef DMX_LAUNCH_FREE
+        const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P); };
+        if (P.ticks > 1) {
+            if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
+            else launch(integrate_free<T, false, 1, true, 0>);
+        } else if (ext) {
+            if (opt == 3) launch(integrate_free<T, true, 1, false, 3>);
+            else if (opt == 2) launch(integrate_free<T, true, 1, false, 2>);
+            else if (opt == 1) launch(integrate_free<T, true, 1, false, 1>);
+            else launch(integrate_free<T, true, 1, false, 0>);
+        } else {
+            if (opt == 3) launch(integrate_free<T, false, MWU, false, 3>);
+            else if (opt == 2) launch(integrate_free<T, false, MWU, false, 2>);
+            else if (opt == 1) launch(integrate_free<T, false, 1, false, 1>);
+            else launch(integrate_free<T, false, 1, false, 0>);
+        }
     } else {
         const unsigned grid = blocks_for(n, 256);
-#define DMX_LAUNCH_PLANE(MW)                                                                                           \
-    do {                                                                                                                   \
-        if (convex) {                                                                                                      \
-            if (ext) hipLaunchKernelGGL((step_plane<T, true, 1, CONVEX_MAXC>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);  \
-            else     hipLaunchKernelGGL((step_plane<T, false, 1, CONVEX_MAXC>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag); \
-        } else if (ext) hipLaunchKernelGGL((step_plane<T, true, MW, 4>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);  \
-        else     hipLaunchKernelGGL((step_plane<T, false, MW, 4>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag); \
-    } while (0)
         // convex bodies: their plane contacts first (one wavefront per body), then the fused step with 8 contact slots
-        const bool convex = P.hull_n > 0 && P.cbuf != nullptr;
-        if (convex) {
+        if (P.hull_n > 0 && P.cbuf != nullptr) {
             const hipError_t e = launch_np_convex_plane<T>(S, gtype, n, P, st);
             if (e != hipSuccess) return e;
+            if (ext) hipLaunchKernelGGL((step_plane<T, true, 1, CONVEX_MAXC>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);
+            else     hipLaunchKernelGGL((step_plane<T, false, 1, CONVEX_MAXC>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);
+        } else {
+            constexpr int MW = sizeof(T) == 4 ? 2 : 1;
+            if (ext) hipLaunchKernelGGL((step_plane<T, true, MW, 4>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);
+            else     hipLaunchKernelGGL((step_plane<T, false, MW, 4>), dim3(grid), dim3(256), 0, st, S, So, gtype, stride, n, P, diag);
         }
-        switch (P.min_waves) {
-        case 1: DMX_LAUNCH_PLANE(1); break;
-        case 2: DMX_LAUNCH_PLANE(2); break;
-        default:
-            if (sizeof(T) == 4) DMX_LAUNCH_PLANE(2); else DMX_LAUNCH_PLANE(1);
-        }
-#undef DMX_LAUNCH_PLANE
     }
     return hipGetLastError();
 }
@@ -917,18 +681,16 @@ hipError_t dmx_touch_kernels(int real_bytes)
     hipError_t e = hipSuccess;
     auto touch = [&](const void *k) { const hipError_t r = hipFuncGetAttributes(&a, k); if (r != hipSuccess) e = r; };
     if (real_bytes == 4) {
-        touch((const void *)&integrate_free<float, 1, false, 1, false>);
-        touch((const void *)&integrate_free<float, 1, false, 7, false, 3>);
-        touch((const void *)&step_plane<float, false, 1, 4>);
+        touch((const void *)&integrate_free<float, false, 1, false>);
+        touch((const void *)&integrate_free<float, false, 7, false, 3>);
         touch((const void *)&step_plane<float, false, 2, 4>);
         touch((const void *)&step_contacts<float, false, 1, 8, true>);
         touch((const void *)&check_zones<float>);
         touch((const void *)&copy_components<float>);
     } else {
-        touch((const void *)&integrate_free<double, 1, false, 1, false>);
-        touch((const void *)&integrate_free<double, 1, false, 1, false, 3>);
+        touch((const void *)&integrate_free<double, false, 1, false>);
+        touch((const void *)&integrate_free<double, false, 1, false, 3>);
         touch((const void *)&step_plane<double, false, 1, 4>);
-        touch((const void *)&step_plane<double, false, 2, 4>);
         touch((const void *)&step_contacts<double, false, 1, 8, true>);
         touch((const void *)&check_zones<double>);
         touch((const void *)&copy_components<double>);

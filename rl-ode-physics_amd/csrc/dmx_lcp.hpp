@@ -1,6 +1,6 @@
 // dmx_lcp.hpp -- dWorldStep's exact island solve for LARGE islands, spread over the whole chip (dmx_lcp.hip).
 // The reference calls dWorldStep at 120 Hz with up to 512 bodies that pile into ONE island of 2 000 - 2 600 constraint rows
-// (/root/reference/src/main.c:208,213, /root/reference/inc/body.h:6): one workgroup per island (lcp_island_wg) is the wrong
+// (/root/reference/src/main.c:208,213, /root/reference/inc/body.h:6): one workgroup per island (lcp_island_lds) is the wrong
 // shape for that.  See the header of dmx_lcp.hip for the method.
 #pragma once
 
@@ -11,7 +11,7 @@
 
 namespace dmx {
 
-// rows at or above which an island's exact solve leaves lcp_island_wg (one workgroup) for the grid solve (DMX_LCP_GRID_ROWS)
+// rows at or above which an island's exact solve leaves lcp_island_lds (one workgroup) for the grid solve (DMX_LCP_GRID_ROWS)
 int lcp_grid_threshold();
 // islands above this many rows are not solved exactly at all: the tick falls back to QuickStep's SOR with a warning (DMX_MAX_EXACT_ROWS)
 int lcp_max_exact_rows();
