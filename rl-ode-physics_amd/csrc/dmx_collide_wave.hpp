@@ -311,8 +311,8 @@ __device__ __forceinline__ int wave_sphere_convex(const V3<T> &cs, T radius, con
 }
 
 // ---- convex hull A (geom 1) against convex hull B (geom 2), both the batch's one hull shape: (1) B's vertices inside A, in
-// array order, each along A's face it is nearest to, normal into A; (2) A's vertices inside B, along B's nearest face.  Lane l
-// transforms vertex 64 j + l; the few that survive the culls are then tested one after the other, each by the whole wave.
+// array order, each along A's face it is nearest to, normal into A; (2) A's vertices inside B, along B's nearest face.  A thread
+// transforms one vertex; the few that survive the culls are then tested one after the other, each by a whole wave (wg_convex_convex).
 // Culling (it decides nothing, it only spares walks): a vertex inside a hull is inside that hull's bounding sphere and inside its
 // world AABB (boxA / boxB: lo3 hi3, the exact AABBs the pair search already holds), both taken with slack far above rounding.  Two
 // teapots that touch overlap in a sliver; nearly every chunk of 64 vertices then has no candidate and costs a dozen instructions.
@@ -350,64 +350,13 @@ __device__ __forceinline__ bool wave_point_in_hull(const V3<T> &rr, const StepPa
     return fbest != 0x7fffffff;
 }
 
-template <class T, class Emit>
-__device__ __forceinline__ int wave_convex_convex(const V3<T> &xa, const M3<T> &Ra, const V3<T> &xb, const M3<T> &Rb, T hull_radius,
-                                                  const T *boxA, const T *boxB, const StepParams<T> &P, int maxc, bool negate, int lane,
-                                                  Emit emit)
-{
-    if (P.hull_nf <= 0) return 0;
-    int contacts = 0;
-    const T slack = hull_radius * T(1e-4);
-    for (int pass = 0; pass < 2; pass++) {
-        const V3<T> &xv = pass == 0 ? xb : xa; const M3<T> &Rv = pass == 0 ? Rb : Ra;      // the hull whose vertices are walked
-        const V3<T> &xh = pass == 0 ? xa : xb; const M3<T> &Rh = pass == 0 ? Ra : Rb;      // the hull they are tested against
-        const T *box = pass == 0 ? boxA : boxB;
-        int fhint = -1;                    // the face that sent the last candidate away (wave-uniform)
-        for (int base = 0; base < P.hull_n && contacts < maxc; base += 64) {
-            const int k = base + lane;
-            V3<T> v = { T(0), T(0), T(0) }, r = { T(0), T(0), T(0) };
-            bool alive = false;
-            if (k < P.hull_n) {
-                v = mulv(Rv, V3<T>{ P.hull[3 * k], P.hull[3 * k + 1], P.hull[3 * k + 2] });
-                v.x += xv.x; v.y += xv.y; v.z += xv.z;
-                r = to_hull_frame(Rh, xh, v);
-                // inside the hull means inside its bounding sphere (slack for rounding): most vertices skip the walk
-                alive = !(r.x * r.x + r.y * r.y + r.z * r.z > hull_radius * hull_radius * T(1.0001)) &&
-                        !(v.x < box[0] - slack || v.x > box[3] + slack || v.y < box[1] - slack || v.y > box[4] + slack ||
-                          v.z < box[2] - slack || v.z > box[5] + slack);
-            }
-            // the candidates of this chunk, in array order; each one's walk over the faces is the WAVE's: lane l tests faces l, l + 64,
-            // ... (a vertex outside the hull leaves at the first group of 64 faces that holds a face it is outside of; before that,
-            // at the face that sent the last candidate away: neighbouring vertices tend to fail the same face)
-            unsigned long long cand = __ballot(alive);
-            while (cand != 0ull && contacts < maxc) {
-                const int l = __builtin_ctzll(cand);
-                cand &= cand - 1ull;
-                const V3<T> rr = { __shfl(r.x, l, 64), __shfl(r.y, l, 64), __shfl(r.z, l, 64) };
-                T dep;
-                int fbest;
-                if (!wave_point_in_hull<T>(rr, P, lane, fhint, dep, fbest)) continue;
-                if (lane == l) {
-                    const T *pl = P.hull_planes + 4 * fbest;
-                    const V3<T> nw = mulv(Rh, V3<T>{ pl[0], pl[1], pl[2] });
-                    const bool flip = (pass == 0) != negate;           // pass 0: against A's outward normal (into A); `negate` flips all
-                    emit(contacts, v, flip ? V3<T>{ -nw.x, -nw.y, -nw.z } : nw, dep);
-                }
-                contacts++;
-            }
-        }
-        if (contacts > maxc) contacts = maxc;
-    }
-    return contacts;
-}
-
-// ---- the same collider by a WORKGROUP of NW wavefronts: one deep pair of hulls is a hundred candidate vertices, each a walk over
-// 2 500 faces by a whole wavefront -- 150-180 us for one wavefront, and the duration of the narrowphase launch whatever the
-// number of pairs.  Here the vertices are taken 64 NW at a time: every thread tests one against the other hull's bounding
+// ---- the collider, by a WORKGROUP of NW wavefronts: one deep pair of hulls is a hundred candidate vertices, each a walk over
+// 2 500 faces by a whole wavefront -- 150-180 us if one wavefront took them all, and the duration of the narrowphase launch
+// whatever the number of pairs.  So the vertices are taken 64 NW at a time: every thread tests one against the other hull's bounding
 // sphere and box, the survivors are listed in array order (ballots + a prefix over the waves), the waves take them in turn
-// (wave w: candidates w, w + NW, ...), and the first maxc that are inside -- in array order, as the one-wavefront walk keeps
-// them -- become contacts.  Same arithmetic per vertex, same contacts, same bits.  Called by every thread of the workgroup;
-// returns the number of contacts on every thread; emit(rank, ...) runs on one thread per contact.
+// (wave w: candidates w, w + NW, ...), and the first maxc that are inside -- in array order, as the oracle's sequential walk keeps
+// them -- become contacts.  Called by every thread of the workgroup; returns the number of contacts on every thread;
+// emit(rank, ...) runs on one thread per contact.
 template <class T, int NW, class Emit>
 __device__ __forceinline__ int wg_convex_convex(const V3<T> &xa, const M3<T> &Ra, const V3<T> &xb, const M3<T> &Rb, T hull_radius,
                                                 const T *boxA, const T *boxB, const StepParams<T> &P, int maxc, bool negate, Emit emit)
@@ -458,7 +407,7 @@ __device__ __forceinline__ int wg_convex_convex(const V3<T> &xa, const M3<T> &Ra
             }
             __syncthreads();
             if (tid == 0) {
-                int n = s_contacts;                                       // (the one-wavefront walk stops at maxc: so does the count)
+                int n = s_contacts;                                       // (the sequential walk stops at maxc: so does the count)
                 for (int c = 0; c < ncand; c++) {
                     const bool take = s_face[c] >= 0 && n < maxc;
                     s_rank[c] = take ? n : -1;

@@ -503,9 +503,9 @@ __global__ __launch_bounds__(256) void ex_narrow_convex(const T *__restrict__ S,
                                                         const int32_t *__restrict__ inv, const int32_t *__restrict__ pairs,
                                                         const GridRec<T> *__restrict__ rec, StepParams<T> P, ExactCaps cap,
                                                         T *__restrict__ gpos, T *__restrict__ gnormal, T *__restrict__ gdepth,
-                                                        uint32_t *__restrict__ cc, ExactCounts *__restrict__ C, int hull_pairs_elsewhere)
+                                                        uint32_t *__restrict__ cc, ExactCounts *__restrict__ C)
 {
-    // hull_pairs_elsewhere: pairs of two hulls are ex_narrow_hull_pairs' (a workgroup each), not this kernel's
+    // (pairs of two hulls are ex_narrow_hull_pairs' -- a workgroup each -- not this kernel's: it leaves their cc entries alone)
     const uint32_t ninv = C->overflow ? 0u : C->ninv, np = C->overflow ? 0u : C->npairs;
     const uint32_t ne = cap.entries(), e_pairs = cap.pair_entry0();
     const int lane = threadIdx.x & 63;
@@ -552,14 +552,7 @@ __global__ __launch_bounds__(256) void ex_narrow_convex(const T *__restrict__ S,
                     nc = wave_box_convex<T>(Bx.x, Bx.R, Bx.side, H.x, H.R, H.side[0], P, maxc, gi != GEOM_BOX, lane,
                                             [&](int rank, const V3<T> &pp, const V3<T> &nn, T dep) { put_c(gpos, gnormal, gdepth, slot0 + rank, pp, nn, dep); }, P.hull);
             } else if (gi == GEOM_CONVEX && gj == GEOM_CONVEX) {
-                if (hull_pairs_elsewhere) continue;
-                // hull i (geom 1, created first) against hull j: vertices of each inside the other, normals into i
-                const BodyGeomX<T> A = geom_of<T>(S, gtype, i), Bh = geom_of<T>(S, gtype, j);
-                const size_t slot0 = cap.pair_slot0() + (size_t)8 * p;
-                const T boxA[6] = { rec[i].lo[0], rec[i].lo[1], rec[i].lo[2], rec[i].hi[0], rec[i].hi[1], rec[i].hi[2] };
-                const T boxB[6] = { rec[j].lo[0], rec[j].lo[1], rec[j].lo[2], rec[j].hi[0], rec[j].hi[1], rec[j].hi[2] };
-                nc = wave_convex_convex<T>(A.x, A.R, Bh.x, Bh.R, A.side[0], boxA, boxB, P, maxc, false, lane,
-                                           [&](int rank, const V3<T> &pp, const V3<T> &nn, T dep) { put_c(gpos, gnormal, gdepth, slot0 + rank, pp, nn, dep); });
+                continue;                                           // ex_narrow_hull_pairs' entry
             } else if (gi == GEOM_SPHERE || gj == GEOM_SPHERE) {
                 // (sphere i, hull j): the collider's own order, normal into the sphere.  (hull i, sphere j): dCollide swaps and flips.
                 const BodyGeomX<T> Sp = geom_of<T>(S, gtype, gi == GEOM_SPHERE ? i : j);
@@ -1332,7 +1325,7 @@ hipError_t launch_exact_group(const T *S, const uint8_t *gtype, int64_t n_active
                        B.gpos, B.gnormal, B.gdepth, B.cc, B.counts, SortKeyArgs{ B.pc, B.inc, B.root, B.rinc, B.keys, B.vals });
     if (P.hull_n > 0) {
         hipLaunchKernelGGL((ex_narrow_convex<T>), dim3((unsigned)std::min<size_t>((ne + 3) / 4, 65535)), dim3(256), 0, st, S, gtype, B.inv,
-                           B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts, 1);
+                           B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts);
         hipLaunchKernelGGL((ex_narrow_hull_pairs<T>), dim3((unsigned)std::min<size_t>(std::max<size_t>(cap.pairs, 1), 4096)), dim3(256), 0, st, S, gtype,
                            B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts);
     }
@@ -1434,7 +1427,7 @@ hipError_t launch_exact_small_group(const T *S, const uint8_t *gtype, const Grid
                        B.gpos, B.gnormal, B.gdepth, B.cc, B.counts, SortKeyArgs{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr });
     if (P.hull_n > 0) {
         hipLaunchKernelGGL((ex_narrow_convex<T>), dim3((unsigned)std::min<size_t>((ne + 3) / 4, 65535)), dim3(256), 0, st, S, gtype, B.inv,
-                           B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts, 1);
+                           B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts);
         hipLaunchKernelGGL((ex_narrow_hull_pairs<T>), dim3((unsigned)std::min<size_t>(std::max<size_t>(cap.pairs, 1), 4096)), dim3(256), 0, st, S, gtype,
                            B.pairs, G.rec, P, cap, B.gpos, B.gnormal, B.gdepth, B.cc, B.counts);
     }

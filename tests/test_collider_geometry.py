@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 from oracle.orc_ctypes import Oracle
+from pair_population import _boxbox_cases, _rand_rot, _small_rot          # shared with the pair populations: the same draws
 
 N_BOXBOX = 120_000
 N_OTHER = 100_000
@@ -37,27 +38,6 @@ def orc():
 
 
 # ------------------------------------------------------------------------------------------------------------ helpers
-def _rand_rot(rng, n):
-    q = rng.normal(size=(n, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    w, x, y, z = q.T
-    R = np.empty((n, 3, 3))
-    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - w * z); R[:, 0, 2] = 2 * (x * z + w * y)
-    R[:, 1, 0] = 2 * (x * y + w * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - w * x)
-    R[:, 2, 0] = 2 * (x * z - w * y); R[:, 2, 1] = 2 * (y * z + w * x); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
-    return R
-
-
-def _small_rot(rng, n, angle):
-    """rotations by `angle` radians (scalar or per-pair) about random axes: boxes with near-parallel edges"""
-    ax = rng.normal(size=(n, 3))
-    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
-    a = np.broadcast_to(np.asarray(angle, float), (n,))
-    K = np.zeros((n, 3, 3))
-    K[:, 0, 1] = -ax[:, 2]; K[:, 0, 2] = ax[:, 1]; K[:, 1, 0] = ax[:, 2]; K[:, 1, 2] = -ax[:, 0]; K[:, 2, 0] = -ax[:, 1]; K[:, 2, 1] = ax[:, 0]
-    return np.eye(3)[None] + np.sin(a)[:, None, None] * K + (1 - np.cos(a))[:, None, None] * (K @ K)
-
-
 def _pose(p, R):
     """position + 3x4 row-major rotation, the oracle's geom layout"""
     n = len(p)
@@ -128,28 +108,6 @@ def _sat_by_projection(p1, R1, s1, p2, R2, s2):
             ov[:, k] += 1e-5 * others / np.where(ok[:, k], ln[:, k], 1.0)
             k += 1
     return ov, axes, ok
-
-
-def _boxbox_cases(rng, n):
-    """three regimes: generic pairs near contact; near-parallel edges (tiny relative rotation); a floor-sized box under a small one"""
-    n1, n2 = n // 2, n // 4
-    n3 = n - n1 - n2
-    s1 = rng.uniform(0.2, 1.0, (n, 3)); s2 = rng.uniform(0.2, 1.0, (n, 3))
-    R1 = _rand_rot(rng, n); R2 = _rand_rot(rng, n)
-    R2[n1:n1 + n2] = _small_rot(rng, n2, 10.0 ** rng.uniform(-9, -2, n2)) @ R1[n1:n1 + n2]
-    p1 = rng.uniform(-1, 1, (n, 3))
-    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
-    reach = 0.5 * (np.linalg.norm(s1, axis=1) + np.linalg.norm(s2, axis=1))
-    p2 = p1 + d * (rng.uniform(0.15, 1.0, n) * reach)[:, None]
-    # the reference's floor (main.c:115): 100 x 1 x 100, a spawned box resting on / sunk into / hovering over its top
-    a = n1 + n2
-    s2[a:] = [100.0, 1.0, 100.0]
-    R2[a:] = np.eye(3)
-    R1[a:] = _small_rot(rng, n3, rng.choice([0.0, 1e-7, 1e-3, 0.3], n3)) @ np.eye(3)
-    p2[a:] = 0.0
-    p1[a:, 0] = rng.uniform(-40, 40, n3); p1[a:, 2] = rng.uniform(-40, 40, n3)
-    p1[a:, 1] = 0.5 + 0.5 * s1[a:, 1] + rng.uniform(-0.05, 0.02, n3)
-    return p1, R1, s1, p2, R2, s2
 
 
 # ------------------------------------------------------------------------------------------------------------ box - box
