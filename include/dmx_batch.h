@@ -361,7 +361,8 @@ int dmxBatchSetRowOrder(dmxBatchID b, int order, uint32_t seed);
  *   row order    within an island the active articulation joints come first, in the order of the set, then the tick's contact
  *                joints in creation order; articulation joints link islands as contact joints between two bodies do.
  *   rows         x_i, R_i = body i's position and rotation, a_i = R_i anchor_i (a world side: x = anchor, a = 0, no Jacobian
- *                block); every row has lo = -inf, hi = +inf, cfm = the world's CFM; k = ERP / h.
+ *                block); every row has lo = -inf, hi = +inf, cfm = the world's CFM; k = ERP / h.  (A hinge's limit / motor row,
+ *                the one row of a joint that can clamp: dmxBatchSetHingeLimots below.)
  *                ball:  three rows, d = e_x, e_y, e_z:  J = [ d, a_1 x d | -d, -(a_2 x d) ],  c = k ((x_2 + a_2) - (x_1 + a_1)) . d
  *                hinge: the three ball rows, then with u = R_1 axis1, w = R_2 axis2, (p, q) = dPlaneSpace(u), for r = p, q:
  *                       J = [ 0, r | 0, -r ],  c = k (u x w) . r
@@ -384,6 +385,40 @@ int dmxBatchJointFromWorld(dmxBatchID b, int kind, int32_t body1, int32_t body2,
 /* per joint of the set |p2 - p1| (the anchors' separation) and, for hinges, |u x w| (0 for balls), from the current state,
  * computed on the device (inactive joints report 0); either array may be NULL; out_max[2] = the two maxima (may be NULL) */
 int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_err, double out_max[2]);
+
+/* ---- a hinge's limits, motor and angle (dJointSetHingeParam: dParamLoStop / HiStop / Vel / FMax; dJointGetHingeAngle / Rate).
+ * This is ODE's limit / motor row for a hinge with fudge factor 1, no bounce, and the world's ERP / CFM for the stop.
+ *   angle   For a hinge with sides (body1, body2) AS GIVEN by the caller: q_i = the body's quaternion (a world side: the identity),
+ *           q_rel = conj(q_1) q_2, q_0 = the joint's stored zero pose (q_rel when the zero was taken), e = q_rel conj(q_0) = (e_w, e_v),
+ *           phi = 2 atan2(e_v . axis1, e_w) wrapped into (-pi, pi] (e and -e give the same phi).  The hinge angle is theta = -phi: the
+ *           angle of body 1 relative to body 2 about u = R_1 axis1, ODE's sign.  The rate is theta_dot = u . (omega_1 - omega_2), the
+ *           omega of a world side being 0.  A joint given as (world, body) reports the angle and rate of the sides as given: the
+ *           internal exchange of sides changes the sign of nothing the caller sees or sets.
+ *   row     A hinge whose limot is PRESENT -- fmax > 0, or a finite lo_stop, or a finite hi_stop -- has one more row, behind its five.
+ *           In the sides as given J = [ 0, u | 0, -u ]: the row's velocity is theta_dot (after an exchange of sides both angular
+ *           blocks change sign).  cfm = the world's CFM, k = ERP / h, g = fmax sign(vel) when fmax > 0, else 0 (sign(0) = 0).
+ *           Limits are on when lo_stop <= hi_stop and at least one of the two is finite.  c, lo, hi -- the first line that matches:
+ *               limits on, lo_stop == hi_stop (locked)     c = -k (theta - lo_stop)   lo = -inf    hi = +inf
+ *               limits on, theta <= lo_stop                c = -k (theta - lo_stop)   lo = g       hi = +inf
+ *               limits on, theta >= hi_stop                c = -k (theta - hi_stop)   lo = -inf    hi = g
+ *               otherwise, fmax > 0                        c = vel                    lo = -fmax   hi = +fmax
+ *               otherwise (inside its range, no motor)     c = 0                      lo = 0       hi = 0
+ *           theta is the angle at the tick's start.  The shifted bound g at a stop is ODE's "motor torque applied by hand while the
+ *           limit row is in use", written as one box row: the multiplier is the limit's force plus the motor's +-fmax, so the
+ *           limit's own part stays >= 0.  The last line keeps a present limot at exactly one row whatever the state: the row count
+ *           depends on the parameters alone.  A hinge whose limot is not present has no such row, and a tick with no present limot
+ *           anywhere stages and launches exactly what it does without limots.
+ * Without limots a hinge's q_0 is the identity: dmxBatchHingeAngles then reports the angle relative to the two frames coinciding. */
+typedef struct dmxHingeLimot { double lo_stop, hi_stop, vel, fmax; double qrel0[4]; } dmxHingeLimot;
+/* one entry per joint of the current set (entries of ball joints are ignored); n must equal dmxBatchJointCount or be 0 (removes them);
+ * copied; may be replaced every tick (a controller setting vel / fmax).  dmxBatchSetJoints drops the limots.  DMX_EINVAL: another n,
+ * a non-finite vel or fmax, a NaN stop. */
+int dmxBatchSetHingeLimots(dmxBatchID b, int64_t n, const dmxHingeLimot *limots);
+/* lo_stop = -inf, hi_stop = +inf, vel = fmax = 0, qrel0 = conj(q_1) q_2 at the bodies' CURRENT poses: "this pose is angle zero" */
+int dmxBatchHingeLimotInit(dmxBatchID b, const dmxJoint *joint, dmxHingeLimot *out);
+/* theta and theta_dot per joint of the set, from the current state, computed on the device in the batch's precision (balls and
+ * inactive joints report 0); either array may be NULL */
+int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate);
 
 /* per-body flags for the island path: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes */
 enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };

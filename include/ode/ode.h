@@ -193,8 +193,13 @@ void dJointAttach(dJointID, dBodyID body1, dBodyID body2);       /* main.c:691 *
 /* ---- articulation joints: ball-and-socket and hinge [ODE-recall objects.h].  Anchors and axes are given in world
  * coordinates after dJointAttach and kept in the bodies' frames at their poses of that moment; a body of 0 is the world.
  * dJointAttach(j, 0, body) exchanges the two, as ODE does: dJointGetBody(j, 0) is the body.  dWorldDestroy destroys the joints that
- * are in no group.  dBodyDestroy detaches the body's joints (both sides: the joint does nothing until it is attached again).  No limits,
- * motors or angles.  dWorldStep / dWorldQuickStep honour them (include/dmx_batch.h, dmxBatchSetJoints). */
+ * are in no group.  dBodyDestroy detaches the body's joints (both sides: the joint does nothing until it is attached again).
+ * dWorldStep / dWorldQuickStep honour them (include/dmx_batch.h, dmxBatchSetJoints).
+ * Hinges have limits, a motor, an angle and a rate (include/dmx_batch.h, dmxBatchSetHingeLimots): dJointSetHingeParam honours
+ * dParamLoStop, dParamHiStop, dParamVel and dParamFMax -- fudge factor 1, no bounce, the world's ERP / CFM at the stops; the other
+ * parameters print one line to stderr and are ignored on set, and read as 0.  dJointSetHingeAnchor / dJointSetHingeAxis take the
+ * bodies' current relative pose as angle zero, as ODE does.  Angle, rate, stops, motor and dJointAddHingeTorque are those of the
+ * sides as attached: body 1 relative to body 2 about the axis, also after dJointAttach(j, 0, body).  Balls have none of these. */
 enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeContact = 4 };
 dJointID dJointCreateBall(dWorldID, dJointGroupID);
 dJointID dJointCreateHinge(dWorldID, dJointGroupID);
@@ -209,6 +214,14 @@ void dJointSetHingeAxis(dJointID, dReal x, dReal y, dReal z);
 void dJointGetHingeAnchor(dJointID, dVector3 result);
 void dJointGetHingeAnchor2(dJointID, dVector3 result);
 void dJointGetHingeAxis(dJointID, dVector3 result);
+/* [ODE-recall common.h D_ALL_PARAM_NAMES, 0.13 - 0.16] */
+enum { dParamLoStop = 0, dParamHiStop, dParamVel, dParamLoVel, dParamHiVel, dParamFMax, dParamFudgeFactor, dParamBounce, dParamCFM,
+       dParamStopERP, dParamStopCFM, dParamSuspensionERP, dParamSuspensionCFM, dParamERP };
+void dJointSetHingeParam(dJointID, int parameter, dReal value);
+dReal dJointGetHingeParam(dJointID, int parameter);
+dReal dJointGetHingeAngle(dJointID);
+dReal dJointGetHingeAngleRate(dJointID);
+void dJointAddHingeTorque(dJointID, dReal torque);
 int dAreConnected(dBodyID, dBodyID);
 int dAreConnectedExcluding(dBodyID body1, dBodyID body2, int joint_type);
 

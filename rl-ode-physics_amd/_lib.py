@@ -27,6 +27,7 @@ BATCH_SYMBOLS = [
     "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision",
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
+    "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -136,5 +137,8 @@ def load():
     sig("dmxBatchJointCount", L, P)
     sig("dmxBatchJointFromWorld", I, P, I, C.c_int32, C.c_int32, P, P, P)
     sig("dmxBatchJointErrors", I, P, P, P, P)
+    sig("dmxBatchSetHingeLimots", I, P, L, P)
+    sig("dmxBatchHingeLimotInit", I, P, P, P)
+    sig("dmxBatchHingeAngles", I, P, P, P)
     _lib = lib
     return lib

@@ -37,6 +37,12 @@ JOINT_DTYPE = np.dtype({
     "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 3), (np.float64, 3), (np.float64, 3), (np.float64, 3)],
     "offsets": [0, 4, 8, 12, 16, 40, 64, 88],
     "itemsize": 112})
+# dmxHingeLimot (include/dmx_batch.h): a hinge's stops, motor and zero pose -- one entry per joint of the set (set_hinge_limots)
+HINGE_LIMOT_DTYPE = np.dtype({
+    "names": ["lo_stop", "hi_stop", "vel", "fmax", "qrel0"],
+    "formats": [np.float64, np.float64, np.float64, np.float64, (np.float64, 4)],
+    "offsets": [0, 8, 16, 24, 32],
+    "itemsize": 64})
 LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", "single", "fallback")
 # the single-launch tick of small worlds (dmxBatchSetSmallTick); the counters of dmxBatchSmallTickStats, in its order: ticks on
 # that path, step_joints ticks on the general path, then one count per reason a tick was not eligible
@@ -234,6 +240,28 @@ class BatchWorld:
         _check(self.lib.dmxBatchJointErrors(self.h, pe.ctypes.data if n else None, ae.ctypes.data if n else None, mx.ctypes.data),
                "dmxBatchJointErrors")
         return pe, ae, (float(mx[0]), float(mx[1]))
+
+    # -- the hinges' limits, motors and angles (dJointSetHingeParam, dJointGetHingeAngle / Rate) --
+    def set_hinge_limots(self, arr):
+        """the hinges' stops and motors: an array of HINGE_LIMOT_DTYPE, one entry per joint of the set (a ball's is ignored);
+        empty or None removes them.  May be replaced every tick; set_joints drops them"""
+        l = np.zeros(0, HINGE_LIMOT_DTYPE) if arr is None else np.ascontiguousarray(np.asarray(arr).astype(HINGE_LIMOT_DTYPE, copy=False)).reshape(-1)
+        _check(self.lib.dmxBatchSetHingeLimots(self.h, l.shape[0], l.ctypes.data if l.shape[0] else None), "dmxBatchSetHingeLimots")
+
+    def hinge_limot_init(self, joint):
+        """a HINGE_LIMOT_DTYPE record without stops or motor whose zero pose is the bodies' current one"""
+        j = np.ascontiguousarray(np.asarray(joint).astype(JOINT_DTYPE, copy=False)).reshape(1)
+        out = np.zeros(1, HINGE_LIMOT_DTYPE)
+        _check(self.lib.dmxBatchHingeLimotInit(self.h, j.ctypes.data, out.ctypes.data), "dmxBatchHingeLimotInit")
+        return out[0]
+
+    def hinge_angles(self):
+        """-> (theta [n], theta_dot [n]) of the set's joints at the current state, computed on the device (balls and inactive
+        joints: 0); without limots the angle is relative to the two frames coinciding"""
+        n = self.joint_count()
+        th, rate = np.zeros(n), np.zeros(n)
+        _check(self.lib.dmxBatchHingeAngles(self.h, th.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchHingeAngles")
+        return th, rate
 
     def set_stepper(self, stepper):
         """STEPPER_QUICK (dWorldQuickStep, default) / STEPPER_EXACT (dWorldStep) for step_joints"""

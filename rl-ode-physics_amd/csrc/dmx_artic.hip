@@ -1,12 +1,15 @@
 // dmx_artic.hip -- the articulation joints' entry points of the batch C ABI (include/dmx_batch.h): the persistent set
 // (dmxBatchSetJoints), a joint from world-frame anchor and axis at the bodies' current poses (dmxBatchJointFromWorld), and the
-// joints' position / axis errors from the current state, computed on the device (dmxBatchJointErrors).  The rows themselves are
-// built by joint_unit_rows (dmx_island_rows.hpp) inside the island kernels; the host side of a tick is in dmx_joints.cpp.
+// joints' position / axis errors from the current state, computed on the device (dmxBatchJointErrors); the hinges' limits and
+// motors (dmxBatchSetHingeLimots, dmxBatchHingeLimotInit) and their angles and rates, computed on the device (dmxBatchHingeAngles).
+// The rows themselves are built by joint_unit_rows (dmx_island_rows.hpp) inside the island kernels; the host side of a tick is in
+// dmx_joints.cpp.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cmath>
 
 #include "dmx_batch_priv.hpp"
+#include "dmx_island_rows.hpp"
 
 namespace dmx {
 
@@ -58,6 +61,44 @@ __global__ __launch_bounds__(256) void joint_errors(const T *__restrict__ S, con
     }
 }
 
+// One lane per joint: a hinge's theta (hinge_angle, the function the limot row is built with) and theta_dot = u . (omega_1 -
+// omega_2), u = R_1 axis1, of the sides as given, in the batch's precision.  limots null: every q_0 is the identity.  Balls and
+// inactive joints report 0.
+template <class T>
+__global__ __launch_bounds__(256) void hinge_angles(const T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, int64_t n_slots,
+                                                    const dmxJoint *__restrict__ joints, const dmxHingeLimot *__restrict__ limots, int64_t nj,
+                                                    double *__restrict__ angle, double *__restrict__ rate)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nj) return;
+    const dmxJoint j = joints[k];
+    const int s1 = j.body1, s2 = j.body2;
+    auto alive = [&](int s) { return s < n_slots && (bflags[s] & BF_ALIVE) != 0; };
+    const bool active = !(s1 < 0 && s2 < 0) && s1 != s2 && (s1 < 0 || alive(s1)) && (s2 < 0 || alive(s2));
+    double th = 0.0, thd = 0.0;
+    if (active && j.kind == DMX_JOINT_HINGE) {
+        Q4<T> q0 = { T(1), T(0), T(0), T(0) };
+        if (limots != nullptr) q0 = { (T)limots[k].qrel0[0], (T)limots[k].qrel0[1], (T)limots[k].qrel0[2], (T)limots[k].qrel0[3] };
+        auto quat = [&](int s) -> Q4<T> {
+            if (s < 0) return { T(1), T(0), T(0), T(0) };
+            return { S[slab_ix(C_QUAT + 0, s)], S[slab_ix(C_QUAT + 1, s)], S[slab_ix(C_QUAT + 2, s)], S[slab_ix(C_QUAT + 3, s)] };
+        };
+        auto omega = [&](int s) -> V3<T> {
+            if (s < 0) return { T(0), T(0), T(0) };
+            return { S[slab_ix(C_AVEL + 0, s)], S[slab_ix(C_AVEL + 1, s)], S[slab_ix(C_AVEL + 2, s)] };
+        };
+        const V3<T> axis1 = { (T)j.axis1[0], (T)j.axis1[1], (T)j.axis1[2] };
+        const Q4<T> q1 = quat(s1);
+        th = (double)hinge_angle(q1, quat(s2), q0, axis1);
+        const V3<T> u = s1 >= 0 ? mulv(quat_to_R(q1), axis1) : axis1;
+        const V3<T> w1 = omega(s1), w2 = omega(s2);
+        const V3<T> dw = { w1.x - w2.x, w1.y - w2.y, w1.z - w2.z };
+        thd = (double)dot(u, dw);
+    }
+    if (angle != nullptr) angle[k] = th;
+    if (rate != nullptr) rate[k] = thd;
+}
+
 }  // namespace dmx
 
 extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints)
@@ -67,6 +108,7 @@ extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints
         if (joints[k].kind != DMX_JOINT_BALL && joints[k].kind != DMX_JOINT_HINGE) return DMX_EINVAL;
     { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
     b->art.assign(joints, joints + n);
+    b->limot.clear();                    // (they were entries of the old set's joints)
     return DMX_OK;
 }
 
@@ -140,5 +182,81 @@ extern "C" int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_e
     if (pos_err) HIP_TRY(hipMemcpy(pos_err, d_pos, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
     if (axis_err) HIP_TRY(hipMemcpy(axis_err, d_axis, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
     if (out_max) HIP_TRY(hipMemcpy(out_max, d_max, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetHingeLimots(dmxBatchID b, int64_t n, const dmxHingeLimot *limots)
+{
+    if (!b || n < 0 || (n > 0 && !limots)) return DMX_EINVAL;
+    if (n != 0 && n != (int64_t)b->art.size()) return DMX_EINVAL;
+    for (int64_t k = 0; k < n; k++) {
+        const dmxHingeLimot &l = limots[k];
+        if (!std::isfinite(l.vel) || !std::isfinite(l.fmax) || std::isnan(l.lo_stop) || std::isnan(l.hi_stop)) return DMX_EINVAL;
+    }
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if (n == 0) b->limot.clear();
+    else b->limot.assign(limots, limots + n);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchHingeLimotInit(dmxBatchID b, const dmxJoint *joint, dmxHingeLimot *out)
+{
+    if (!b || !joint || !out) return DMX_EINVAL;
+    if (joint->body1 < -1 || joint->body2 < -1 || joint->body1 >= b->n || joint->body2 >= b->n) return DMX_EINVAL;
+    auto quat = [&](int32_t s, dmx::Q4<double> &q) -> int {
+        q = { 1.0, 0.0, 0.0, 0.0 };
+        if (s < 0) return DMX_OK;
+        double st[13];
+        if (b->precision == DMX_F32) {
+            float f[13];
+            const int rc = dmxBatchDownload(b, DMX_STATE, f, s, 1);
+            if (rc != DMX_OK) return rc;
+            for (int k = 0; k < 13; k++) st[k] = f[k];
+        } else {
+            const int rc = dmxBatchDownload(b, DMX_STATE, st, s, 1);
+            if (rc != DMX_OK) return rc;
+        }
+        q = { st[3], st[4], st[5], st[6] };
+        return DMX_OK;
+    };
+    dmx::Q4<double> q1, q2;
+    int rc = quat(joint->body1, q1);
+    if (rc == DMX_OK) rc = quat(joint->body2, q2);
+    if (rc != DMX_OK) return rc;
+    const dmx::Q4<double> r = dmx::qmul(dmx::qconj(q1), q2);
+    out->lo_stop = -__builtin_huge_val(); out->hi_stop = __builtin_huge_val(); out->vel = 0.0; out->fmax = 0.0;
+    out->qrel0[0] = r.w; out->qrel0[1] = r.x; out->qrel0[2] = r.y; out->qrel0[3] = r.z;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    const int64_t nj = (int64_t)b->art.size();
+    if (nj == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    int rc;
+    const bool lim = !b->limot.empty();
+    if ((rc = dmx_ensure_dev(b->art_dev, (size_t)nj * sizeof(dmxJoint))) != DMX_OK) return rc;
+    if ((rc = dmx_ensure_dev(b->art_err, ((size_t)2 * nj + 2) * sizeof(double))) != DMX_OK) return rc;
+    if (lim && (rc = dmx_ensure_dev(b->limot_dev, (size_t)nj * sizeof(dmxHingeLimot))) != DMX_OK) return rc;
+    double *d_angle = (double *)b->art_err.p + 2, *d_rate = d_angle + nj;
+    // (the sets live in pageable host memory: plain copies, which have read them when they return)
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->art_dev.p, b->art.data(), (size_t)nj * sizeof(dmxJoint), hipMemcpyHostToDevice));
+    if (lim) HIP_TRY(hipMemcpy(b->limot_dev.p, b->limot.data(), (size_t)nj * sizeof(dmxHingeLimot), hipMemcpyHostToDevice));
+    const dmxHingeLimot *d_lim = lim ? (const dmxHingeLimot *)b->limot_dev.p : nullptr;
+    const unsigned grid = (unsigned)((nj + 255) / 256);
+    if (b->precision == DMX_F32)
+        hipLaunchKernelGGL((dmx::hinge_angles<float>), dim3(grid), dim3(256), 0, b->stream, (const float *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, d_lim, nj, d_angle, d_rate);
+    else
+        hipLaunchKernelGGL((dmx::hinge_angles<double>), dim3(grid), dim3(256), 0, b->stream, (const double *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, d_lim, nj, d_angle, d_rate);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (angle) HIP_TRY(hipMemcpy(angle, d_angle, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
+    if (rate) HIP_TRY(hipMemcpy(rate, d_rate, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
     return DMX_OK;
 }

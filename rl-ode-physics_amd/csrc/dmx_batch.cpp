@@ -180,7 +180,7 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
         if (d->p) (void)hipFree(d->p);
     for (dmxBatch::DevBuf *d : { &b->bp_count, &b->bp_items, &b->bp_flags, &b->bp_inpair, &b->bp_snapshot, &b->hull, &b->cbuf, &b->ccount,
                                 &b->ex_arena, &b->ex_body, &b->ex_last, &b->ex_aabb, &b->sbox, &b->hull_planes, &b->rc_count, &b->rc_items, &b->rc_misc,
-                                &b->rc_rays, &b->rc_ids, &b->rc_hits, &b->art_dev, &b->art_err })
+                                &b->rc_rays, &b->rc_ids, &b->rc_hits, &b->art_dev, &b->art_err, &b->limot_dev })
         if (d->p) (void)hipFree(d->p);
     if (b->bp_flags_host) (void)hipHostFree(b->bp_flags_host);
     if (b->ex_counts_host) (void)hipHostFree(b->ex_counts_host);

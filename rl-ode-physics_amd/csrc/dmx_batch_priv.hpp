@@ -31,6 +31,7 @@ using namespace dmx;
 // a contact joint in canonical form: body1 a live dynamic slot, normal into it (dmx_joints.cpp)
 // ... or a unit of an articulation joint (unit != 0: j is null, art = its index in the batch's set): at most three rows on the
 // same two bodies, carried beside the contacts -- a ball is one DMX_UNIT_BALL, a hinge a DMX_UNIT_BALL and a DMX_UNIT_HINGE2
+// and, when its limot is present (dmxBatchSetHingeLimots), a UNIT_LIMOT of one row: the only unit whose row can clamp
 struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; int unit = 0; int art = -1; };
 
 struct dmxBatch {
@@ -188,8 +189,12 @@ struct dmxBatch {
     // articulation joints (dmxBatchSetJoints): the set, and the device staging of dmxBatchJointErrors
     std::vector<dmxJoint> art;
     DevBuf art_dev, art_err;
+    // the hinges' limits and motors (dmxBatchSetHingeLimots): empty, or one entry per joint of `art`
+    std::vector<dmxHingeLimot> limot;
+    DevBuf limot_dev;
     int64_t last_units = 0;                        // units the last dmxBatchStepJoints tick carried among its contact entries
 };
+inline bool dmx_limot_present(const dmxHingeLimot &l) { return dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax); }
 // the ticks that build their own islands on the device do not know articulation joints: they say so instead of ignoring them
 inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
 {

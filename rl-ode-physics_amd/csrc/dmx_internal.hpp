@@ -90,12 +90,21 @@ template <class T> struct IslandSet {
     int singles;           // 1: islands of one body with 1..8 contacts are left to solve_singles / solve_singles_lds (one lane each);
                            // whoever builds `big` must then keep such islands out of it
     // 1: some entries of the contact arrays are units of articulation joints (dmx_island_rows.hpp: joint_unit_rows), marked by
-    // cmu = UNIT_BALL_MU / UNIT_HINGE2_MU; within an island they come before its contacts.  0: contacts only
+    // cmu = UNIT_BALL_MU / UNIT_HINGE2_MU / UNIT_LIMOT_MU; within an island they come before its contacts.  0: contacts only
     int has_units = 0;
 };
 // a unit's marker in IslandSet::cmu: minus its row count (a contact's mu is never negative there when has_units is set)
-constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2;
-constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0;
+// (UNIT_LIMOT: a hinge's limit / motor row, dmxBatchSetHingeLimots -- the one unit whose row can clamp)
+constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2, UNIT_LIMOT = 3;
+constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0, UNIT_LIMOT_MU = -1.0;
+// Is a hinge's limot row there?  fmax > 0, or a finite stop.  Decided on the parameters alone -- the host sizes islands, schedules and LCP
+// scratch before the device has looked at the angle, so the row count must not depend on the state -- and in this one place: the
+// batch's tick (dmx_joints.cpp) and the ODE face (ode_compat.cpp: whether to hand the batch limots at all) must agree.
+inline bool limot_present(double lo_stop, double hi_stop, double fmax)
+{
+    const double inf = __builtin_huge_val();
+    return fmax > 0 || (lo_stop > -inf && lo_stop < inf) || (hi_stop > -inf && hi_stop < inf);
+}
 
 template <class T> struct StepParams {
     V3<T> g;            // gravity

@@ -63,11 +63,11 @@ __device__ __forceinline__ void stage_body(const T *S, const uint8_t *bflags, in
 }
 
 // per-contact surface arrays are optional: without them every contact carries the batch's surface (StepParams)
-// (an entry that is a unit of an articulation joint carries minus its row count there: UNIT_BALL_MU / UNIT_HINGE2_MU)
+// (an entry that is a unit of an articulation joint carries minus its row count there: UNIT_BALL_MU / UNIT_HINGE2_MU / UNIT_LIMOT_MU)
 template <class T> __device__ __forceinline__ int contact_rpc(const IslandSet<T> &I, const StepParams<T> &P, int ci)
 {
     const T mu = I.cmu != nullptr ? I.cmu[ci] : P.mu;
-    if (I.has_units && mu < 0) return mu == T(UNIT_HINGE2_MU) ? 2 : 3;
+    if (I.has_units && mu < 0) return mu == T(UNIT_HINGE2_MU) ? 2 : mu == T(UNIT_LIMOT_MU) ? 1 : 3;
     return mu > 0 ? 3 : 1;
 }
 template <class T> __device__ __forceinline__ bool contact_is_unit(const IslandSet<T> &I, int ci)
@@ -91,16 +91,114 @@ template <class T> DMX_HD T diff_of_sums(T x2, T a2, T x1, T a1)
     return r + ((e1 + e2) + e3);
 }
 
+// ---- a hinge's angle and its limit / motor row (dmxBatchSetHingeLimots; the definitions: include/dmx_batch.h) ------------------
+// atan2(s, c) for c >= 0, as the half angle of a rotation needs it.  float: the library's.  double: the library's atan2 costs the
+// island kernels that inline the limot row some twenty registers and with them a wave per SIMD (lcp_island_lds, lcp_prepare), so
+// the double version is spelled out: with a = |s|, lo = min(a, c), hi = max(a, c) and t = lo / hi in [0, 1] the angle of (hi, lo)
+// is atan(t) = 2 atan(x), x = t / (1 + sqrt(1 + t^2)) <= tan(pi/8) = 0.4142, where 24 terms of x - x^3/3 + x^5/5 - ... leave
+// 0.4142^49 / 49 < 1e-20; then the reflection about pi/4 when a > c and the sign of s.  Selects, not branches, and as few of them
+// as will do: in kernels that already spill scalar registers every compare costs some.
+template <class T> DMX_HD T half_angle_atan2(T s, T c);
+template <> DMX_HD float half_angle_atan2<float>(float s, float c) { return ::atan2f(s, c); }
+template <> DMX_HD double half_angle_atan2<double>(double s, double c)
+{
+    const double a = s < 0.0 ? -s : s;
+    const double lo = a < c ? a : c, hi = a < c ? c : a;
+    const double t = lo / (hi > 0.0 ? hi : 1.0);           // (s = c = 0, no rotation at all: 0)
+    const double x = t / (1.0 + __builtin_sqrt(fma_(t, t, 1.0)));
+    const double y = x * x;
+    double p = 1.0 / 47.0;
+#pragma unroll
+    for (int k = 45; k >= 1; k -= 2) p = fma_(-p, y, 1.0 / (double)k);
+    double r = 2.0 * (p * x);
+    r = a > c ? 1.5707963267948966 - r : r;
+    return s < 0.0 ? -r : r;
+}
+template <class T> DMX_HD Q4<T> qconj(const Q4<T> &q) { return { q.w, -q.x, -q.y, -q.z }; }
+template <class T> DMX_HD Q4<T> qmul(const Q4<T> &a, const Q4<T> &b)
+{
+    return { a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+             a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w };
+}
+// theta of the sides as given: q1, q2 = the two sides' quaternions (a world side: the identity), q0 = the stored zero pose,
+// axis1 = the hinge axis in the frame of side 1.  e = conj(q1) q2 conj(q0), phi = 2 atan2(e_v . axis1, e_w) in (-pi, pi] (e and -e
+// are the same rotation: the half angle is taken with e_w >= 0), theta = -phi: the angle of side 1 relative to side 2, ODE's sign.
+// (host too: the ODE face's dJointGetHingeAngle, tests/harness/limot_rows_harness.cpp)
+template <class T> DMX_HD T hinge_angle(const Q4<T> &q1, const Q4<T> &q2, const Q4<T> &q0, const V3<T> &axis1)
+{
+    const Q4<T> e = qmul(qmul(qconj(q1), q2), qconj(q0));
+    T s = fma_(e.z, axis1.z, fma_(e.y, axis1.y, e.x * axis1.x)), c = e.w;
+    if (c < T(0)) { s = -s; c = -c; }
+    const T pi = T(3.14159265358979323846);
+    T phi = T(2) * half_angle_atan2(s, c);
+    if (phi <= -pi) phi = pi;
+    if (phi > pi) phi = pi;
+    return -phi;
+}
+
+// The limot unit's one row, behind its hinge's five.  The unit's reals: cpos = axis1 as given (in the frame of the given body 1,
+// the world's if that side is the world), cnormal[3] + cdepth = q_0 (w, x, y, z), cbounce / cbounce_vel / csoft_erp / csoft_cfm =
+// lo_stop / hi_stop / vel / fmax; cmode != 0: the sides were exchanged (given as (world, body): this entry's body 1 is the given
+// body 2).  In the sides as given J = [ 0, u | 0, -u ], u = R_1 axis1: the row's velocity is theta_dot.
+template <class T>
+DMX_HD int limot_unit_row(const T *S, const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    const bool rev = I.cmode[ci] != 0;
+    T *row = rows + (size_t)m * RW_COUNT;
+    jb[2 * m] = I.local[s1]; jb[2 * m + 1] = s2 >= 0 ? I.local[s2] : -1;
+    const V3<T> axis1 = ld3(I.cpos + 3 * (size_t)ci);
+    // (first the angle and with it c, lo, hi, then the Jacobian: what one part needs is dead before the other begins -- the row is
+    //  built inside kernels that have no registers to spare)
+    {
+        const Q4<T> q0 = { I.cnormal[3 * (size_t)ci + 0], I.cnormal[3 * (size_t)ci + 1], I.cnormal[3 * (size_t)ci + 2], I.cdepth[ci] };
+        // the sides as given: (body 1, body 2 or the world), or after an exchange (the world, body 1)
+        const int sa = rev ? -1 : s1, sb = rev ? s1 : s2;
+        Q4<T> qa = { T(1), T(0), T(0), T(0) }, qb = { T(1), T(0), T(0), T(0) };
+        if (sa >= 0) { qa.w = S[slab_ix(C_QUAT + 0, sa)]; qa.x = S[slab_ix(C_QUAT + 1, sa)]; qa.y = S[slab_ix(C_QUAT + 2, sa)]; qa.z = S[slab_ix(C_QUAT + 3, sa)]; }
+        if (sb >= 0) { qb.w = S[slab_ix(C_QUAT + 0, sb)]; qb.x = S[slab_ix(C_QUAT + 1, sb)]; qb.y = S[slab_ix(C_QUAT + 2, sb)]; qb.z = S[slab_ix(C_QUAT + 3, sb)]; }
+        const T theta = hinge_angle(qa, qb, q0, axis1);
+        const T lo_s = I.cbounce[ci], hi_s = I.cbounce_vel[ci], vel = I.csoft_erp[ci], fmax = I.csoft_cfm[ci];
+        const T inf = Limits<T>::inf(), k = hinv * P.erp;
+        const T g = fmax > T(0) ? (vel > T(0) ? fmax : vel < T(0) ? -fmax : T(0)) : T(0);
+        const bool limited = lo_s <= hi_s && (lo_s > -inf || hi_s < inf);
+        T c = T(0), lo = T(0), hi = T(0);                  // inside its range, no motor: the row stays, and does nothing
+        if (limited && lo_s == hi_s) { c = -k * (theta - lo_s); lo = -inf; hi = inf; }
+        else if (limited && theta <= lo_s) { c = -k * (theta - lo_s); lo = g; hi = inf; }
+        else if (limited && theta >= hi_s) { c = -k * (theta - hi_s); lo = -inf; hi = g; }
+        else if (fmax > T(0)) { c = vel; lo = -fmax; hi = fmax; }
+        row[RW_LO] = lo; row[RW_HI] = hi;
+        row[RW_RHS] = c;                    // c for now
+        row[RW_AD] = P.cfm;                 // cfm for now
+        row[RW_LAM] = T(0);
+    }
+    V3<T> u = { -axis1.x, -axis1.y, -axis1.z };            // given body 1 is the world -- its axis as given -- and this entry's body 1 the given body 2
+    if (!rev) {
+        const Q4<T> qa = { S[slab_ix(C_QUAT + 0, s1)], S[slab_ix(C_QUAT + 1, s1)], S[slab_ix(C_QUAT + 2, s1)], S[slab_ix(C_QUAT + 3, s1)] };
+        u = mulv(quat_to_R(qa), axis1);
+    }
+    T *J = row + RW_J;
+    J[0] = J[1] = J[2] = T(0);
+    st3(J + 3, u);
+    for (int j = 6; j < 12; j++) J[j] = T(0);
+    if (s2 >= 0) { J[9] = -u.x; J[10] = -u.y; J[11] = -u.z; }
+    return 1;
+}
+
 // ---- rows of a unit of an articulation joint (dmxBatchSetJoints), written at island-relative row m ---------------------------
 // The unit's six reals travel in the contact arrays: cpos = the first side's anchor (ball unit) or axis (hinge unit) in the
 // frame of body 1, cnormal = the second side's in the frame of body 2 -- or in the world frame when there is no body 2.
 //   ball unit, d = e_x, e_y, e_z:  J = [ d, a1 x d | -d, -(a2 x d) ],  c = k ((x2 + a2) - (x1 + a1)) . d,   a_i = R_i anchor_i
 //   hinge unit, r = p, q of plane_space(u), u = R_1 axis1, w = R_2 axis2:  J = [ 0, r | 0, -r ],  c = k (u x w) . r
-// with k = erp / h, cfm = the world's, no bounds.  Returns the unit's row count.
+// with k = erp / h, cfm = the world's, no bounds.  (A limot unit: limot_unit_row.)  Returns the unit's row count.
 template <class T>
 DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                T *rows, int *jb, int ci, int m, T hinv)
 {
+    // (for callers outside the kernels -- the host harnesses.  The kernels come through contact_rows, which sends a limot unit to
+    //  limot_unit_row itself and never gets here with one: dispatched only from here, solve_islands<float> needs 82 VGPRs for 80 and
+    //  loses its sixth wave per SIMD, profiles/limot_kernel_resources.txt.  Keep both.)
+    if (I.cmu[ci] == T(UNIT_LIMOT_MU)) return limot_unit_row(S, I, P, rows, jb, ci, m, hinv);
     const int s1 = I.cb1[ci], s2 = I.cb2[ci];
     const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
     const bool hinge2 = I.cmu[ci] == T(UNIT_HINGE2_MU);
@@ -164,7 +262,11 @@ template <class T, int RPCK = 0>
 __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                              T *rows, int *jb, int ci, int m, T hinv)
 {
-    if (RPCK == 0 && contact_is_unit(I, ci)) { (void)joint_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv); return; }
+    if (RPCK == 0 && contact_is_unit(I, ci)) {
+        if (I.cmu[ci] == T(UNIT_LIMOT_MU)) (void)limot_unit_row(S, I, P, rows, jb, ci, m, hinv);
+        else (void)joint_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
+        return;
+    }
     const int s1 = I.cb1[ci], s2 = I.cb2[ci];
     const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
     const bool ind = I.csrc != nullptr;

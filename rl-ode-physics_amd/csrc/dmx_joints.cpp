@@ -81,12 +81,13 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     cj.reserve((size_t)nj_in);
     // `include` (optional) restricts the tick to a subset of bodies: the rest is stepped by the fused kernels
     auto live = [&](int s) { return s >= 0 && s < n && (b->h_bflags[(size_t)s] & BF_ALIVE) && (!include || include[s]); };
-    // the active articulation joints first, as units of at most three rows (a ball: one unit; a hinge: its ball unit and the two
-    // angular rows), in the order of the set: the stable sort by island below keeps them ahead of the island's contacts
+    // the active articulation joints first, as units of at most three rows (a ball: one unit; a hinge: its ball unit, the two
+    // angular rows and, when its limot is present, the limit / motor row), in the order of the set: the stable sort by island below keeps them ahead of the island's contacts
     if (!b->art.empty() && (include || geo)) {          // (every caller that steps a subset is refused before it gets here)
         fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour articulation joints (dmxBatchSetJoints)\n");
         return DMX_EINVAL;
     }
+    int n_limots = 0;
     if (!b->art.empty()) {
         for (size_t a = 0; a < b->art.size(); a++) {
             const dmxJoint &j = b->art[a];
@@ -97,13 +98,16 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             if (rev) { b1 = b2; b2 = -1; }
             DmxCanonicalJoint u; u.b1 = b1; u.b2 = b2; u.j = nullptr; u.rev = rev; u.unit = UNIT_BALL; u.art = (int)a;
             cj.push_back(u);
-            if (j.kind == DMX_JOINT_HINGE) { u.unit = UNIT_HINGE2; cj.push_back(u); }
+            if (j.kind == DMX_JOINT_HINGE) {
+                u.unit = UNIT_HINGE2; cj.push_back(u);
+                if (!b->limot.empty() && dmx_limot_present(b->limot[a])) { u.unit = UNIT_LIMOT; cj.push_back(u); n_limots++; }
+            }
         }
     }
     const int n_units = (int)cj.size();
-    // rows of an entry, and how many of them can clamp
-    auto rpc_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_HINGE2 ? 2 : 3) : (c.j->mu > 0 ? 3 : 1); };
-    auto nbd_rows_of = [](const CJ &c) { return c.unit ? 0 : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
+    // rows of an entry, and how many of them can clamp (a limot unit's one row is counted as able to, whatever its state will be)
+    auto rpc_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_HINGE2 ? 2 : c.unit == UNIT_LIMOT ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
+    auto nbd_rows_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_LIMOT ? 1 : 0) : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
     for (int64_t k = 0; k < nj_in; k++) {
         const dmxContactJoint &j = joints[k];
         int b1 = live(j.body1) ? j.body1 : -1, b2 = live(j.body2) ? j.body2 : -1;
@@ -411,6 +415,16 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     // a unit's six reals ride in the contact arrays: the first side's anchor (axis) where a contact has its
                     // position, the second side's where it has its normal; cmu says which unit it is
                     const dmxJoint &a = b->art[(size_t)c.art];
+                    if (c.unit == UNIT_LIMOT) {
+                        // the limot unit: axis1 AS GIVEN where a contact has its position, the zero pose in the normal's three
+                        // slots and the depth's, stops / vel / fmax in the four surface slots; cmode says whether the sides were exchanged
+                        const dmxHingeLimot &l = b->limot[(size_t)c.art];
+                        cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = c.rev ? 1 : 0; csrc[d] = 0;
+                        for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)a.axis1[k]; cnormal[3 * (size_t)d + k] = (T)l.qrel0[k]; }
+                        cdepth[d] = (T)l.qrel0[3]; cmu[d] = (T)UNIT_LIMOT_MU;
+                        cbounce[d] = (T)l.lo_stop; cbv[d] = (T)l.hi_stop; cserp[d] = (T)l.vel; cscfm[d] = (T)l.fmax;
+                        continue;
+                    }
                     const double *f1 = c.unit == UNIT_BALL ? (c.rev ? a.anchor2 : a.anchor1) : (c.rev ? a.axis2 : a.axis1);
                     const double *f2 = c.unit == UNIT_BALL ? (c.rev ? a.anchor1 : a.anchor2) : (c.rev ? a.axis1 : a.axis2);
                     cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = 0; csrc[d] = 0;
@@ -560,6 +574,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             // remembered under -- (body pair, ordinal of the contact within the pair this tick, row of the contact)
             lcp_grid_begin_tick(b);
             LcpIslandRows R;
+            R.limots = n_limots > 0;
             std::vector<std::pair<uint64_t, int>> &ord = b->sc_pair_ord;
             for (int isl : grid_list) {
                 R.isl = isl; R.m = b->sc_iv[10][(size_t)isl]; R.row_base = 3 * con_start[(size_t)isl];
@@ -579,8 +594,10 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     const uint64_t base = ((uint64_t)(uint32_t)(c.b1 + 1) << 38) | ((uint64_t)((uint32_t)(c.b2 + 1) & 0xffffffu) << 14) |
                                           ((uint64_t)((e - run) & 0xfffu) << 2);
                     for (int q = 0; q < rpc; q++) {
-                        R.key[(size_t)(r + q)] = base | (uint64_t)q;
-                        R.unbounded[(size_t)(r + q)] = (c.unit || (q > 0 && !(c.j->mu < __builtin_huge_val()))) ? 1 : 0;
+                        // (a limot's row: low bits 1, as a bounded friction row's -- clamped, its value need not be zero.  The
+                        //  ordinal within the pair is stable while the set and the limots' presence are)
+                        R.key[(size_t)(r + q)] = base | (uint64_t)(c.unit == UNIT_LIMOT ? 1 : q);
+                        R.unbounded[(size_t)(r + q)] = c.unit ? (c.unit != UNIT_LIMOT) : (q > 0 && !(c.j->mu < __builtin_huge_val()));
                     }
                 }
                 // every body's rows (creation order): counting sort over the island's contacts; local index = position among the

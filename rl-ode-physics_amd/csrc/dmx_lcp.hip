@@ -894,6 +894,18 @@ int lcp_grid_solve(dmxBatch *b, const IslandSet<T> &I, const StepParams<T> &P, c
             if (!known && g->warm && !g->warm_prev.empty()) { in_v[(size_t)q] = 1; nv_pred++; }      // a new contact
         }
         if (classical || nv_pred > vcap) { in_v.assign((size_t)nbd, 0); nv_pred = 0; }
+        if (R.limots && g->warm && !g->warm_prev.empty()) {
+            // a limot row remembered at a bound that is infinite this tick (a motor row then, a stop's one-sided row now): clamping it
+            // there would put an infinity into lambda.  The bounds are made on the device, so they are fetched: one wait per solve
+            // of an island with limots, which waits once per pivoting round anyway.
+            HIP_TRY(hipMemcpyAsync(h_lam, lo, (size_t)nbd * sizeof(T), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_w, hi, (size_t)nbd * sizeof(T), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (int q = 0; q < nbd; q++) {
+                if (state[(size_t)q] == ST_LO && !(h_lam[q] > -Limits<T>::inf())) state[(size_t)q] = ST_FREE;
+                if (state[(size_t)q] == ST_HI && !(h_w[q] < Limits<T>::inf())) state[(size_t)q] = ST_FREE;
+            }
+        }
         state0 = state;
         int best = m + 1, patience = g->murty_only ? 0 : 3, passes = 0, l2_passes = 0;
         bool subset_mode = false;

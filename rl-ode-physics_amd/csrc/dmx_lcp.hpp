@@ -24,6 +24,9 @@ struct LcpIslandRows {
     int row_base = 0;                 // the island's first row in the set's flat row arrays (3 x its first contact)
     std::vector<uint8_t> unbounded;
     std::vector<uint64_t> key;
+    // some of the rows are hinges' limit / motor rows (dmxBatchSetHingeLimots): which of a row's bounds is infinite changes with
+    // the hinge's angle, so a remembered LO / HI may name a bound that is not there this tick
+    bool limots = false;
     // the rows of every body of the island, ascending: body k's (k = its index within the island) are bodyrows[boff[k] .. boff[k+1]),
     // each entry 2 * row + side (0: the body is the row's first, 1: its second)
     std::vector<int> boff, bodyrows;

@@ -19,6 +19,7 @@
 #include "dmx_collide.hpp"
 #include "dmx_ray.hpp"
 #include "dmx_math.hpp"
+#include "dmx_island_rows.hpp"      // hinge_angle: the function the device builds the limit / motor row with
 
 using dmx::M3;
 using dmx::Q4;
@@ -90,6 +91,13 @@ struct dxJoint {
     int type = dJointTypeContact;
     // a ball or a hinge: anchors and axes in the frames of the two bodies (world frame for a side without a body)
     double anchor1[3] = { 0, 0, 0 }, anchor2[3] = { 0, 0, 0 }, axis1[3] = { 1, 0, 0 }, axis2[3] = { 1, 0, 0 };
+    // a hinge's limit and motor (dJointSetHingeParam) and its zero pose, conj(q_1) q_2 of the sides AS ATTACHED when the anchor or
+    // the axis was last set (include/dmx_batch.h, dmxHingeLimot).  rev: attached as (0, body) -- b1 / b2 above are exchanged, and
+    // the angle, the rate, the stops and the motor are those of the sides as attached [ODE-recall dJOINT_REVERSE: dJointGetHingeAngle
+    // and dJointAddHingeTorque change sign]
+    bool rev = false;
+    double lo_stop = -__builtin_huge_val(), hi_stop = __builtin_huge_val(), vel = 0, fmax = 0;
+    double qrel0[4] = { 1, 0, 0, 0 };
 };
 
 struct dxJointGroup {
@@ -103,7 +111,10 @@ struct dxWorld {
     std::vector<dxJoint *> joints;     // contact joints of the current tick, creation order
     std::vector<dxJoint *> arts;       // ball and hinge joints, creation order: they persist (dmxBatchSetJoints)
     bool art_dirty = false;            // ... and changed since the batch last saw them
+    bool limot_dirty = false;          // a hinge's limit / motor parameter or zero pose changed since the batch last saw them
+    bool limots_sent = false;          // the batch holds limots (dmxBatchSetHingeLimots)
     std::vector<dmxJoint> aj;
+    std::vector<dmxHingeLimot> al;
     dReal g[3] = { 0, 0, 0 };
     dReal erp = (dReal)0.2, cfm = kDefaultCFM, sor_w = (dReal)1.3;
     int iters = 20;
@@ -300,10 +311,33 @@ static int world_step(dWorldID w, dReal h, int stepper)
             a.body1 = j->b1 ? j->b1->slot : -1;
             a.body2 = j->b2 ? j->b2->slot : -1;
             for (int k = 0; k < 3; k++) { a.anchor1[k] = j->anchor1[k]; a.anchor2[k] = j->anchor2[k]; a.axis1[k] = j->axis1[k]; a.axis2[k] = j->axis2[k]; }
+            if (j->rev && j->b1 && !j->b2) {
+                // the sides as attached, (0, body): the batch exchanges them as dJointAttach did -- the same five rows -- and its
+                // limit / motor row and angle are those of the sides as given
+                a.body1 = -1; a.body2 = j->b1->slot;
+                for (int k = 0; k < 3; k++) { a.anchor1[k] = j->anchor2[k]; a.anchor2[k] = j->anchor1[k]; a.axis1[k] = j->axis2[k]; a.axis2[k] = j->axis1[k]; }
+            }
             w->aj.push_back(a);
         }
         DMX_MUST(dmxBatchSetJoints(w->batch, (int64_t)w->aj.size(), w->aj.data()));
         w->art_dirty = false;
+        w->limots_sent = false;        // (dmxBatchSetJoints drops them)
+        w->limot_dirty = true;
+    }
+    if (w->limot_dirty) {              // ... and the hinges' limits and motors when the joints or a parameter changed
+        w->al.clear();
+        bool any = false;
+        for (const dxJoint *j : w->arts) {
+            dmxHingeLimot l;
+            l.lo_stop = j->lo_stop; l.hi_stop = j->hi_stop; l.vel = j->vel; l.fmax = j->fmax;
+            for (int k = 0; k < 4; k++) l.qrel0[k] = j->qrel0[k];
+            if (j->type == dJointTypeHinge && dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax)) any = true;
+            w->al.push_back(l);
+        }
+        // (a world none of whose hinges has a limit or a motor hands the batch nothing: its ticks are what they were without them)
+        if (any) { DMX_MUST(dmxBatchSetHingeLimots(w->batch, (int64_t)w->al.size(), w->al.data())); w->limots_sent = true; }
+        else if (w->limots_sent) { DMX_MUST(dmxBatchSetHingeLimots(w->batch, 0, nullptr)); w->limots_sent = false; }
+        w->limot_dirty = false;
     }
     w->cj.clear();
     for (const dxJoint *j : w->joints) {
@@ -844,7 +878,8 @@ extern "C" void dJointAttach(dJointID j, dBodyID b1, dBodyID b2)
     j->b1 = b1; j->b2 = b2;
     if (j->type != dJointTypeContact) {
         // a ball or a hinge attached as (0, body): ODE exchanges the two, so that body 1 is the body [ODE-recall dJointAttach, dJOINT_REVERSE]
-        if (!j->b1 && j->b2) { j->b1 = j->b2; j->b2 = nullptr; }
+        j->rev = !j->b1 && j->b2;
+        if (j->rev) { j->b1 = j->b2; j->b2 = nullptr; }
         if (j->world) j->world->art_dirty = true;
     }
 }
@@ -878,6 +913,26 @@ void to_world(const dxBody *b, const double in[3], bool point, dReal out[4])
         out[k] = b ? (dReal)((double)b->R[4 * k] * in[0] + (double)b->R[4 * k + 1] * in[1] + (double)b->R[4 * k + 2] * in[2] + (point ? (double)b->pos[k] : 0.0))
                    : (dReal)in[k];
 }
+// the two sides AS ATTACHED (rev: the first is the world) and their quaternions (a world side: the identity)
+void given_sides(const dxJoint *j, const dxBody *&g1, const dxBody *&g2, dmx::Q4<double> &q1, dmx::Q4<double> &q2)
+{
+    g1 = j->rev ? nullptr : j->b1;
+    g2 = j->rev ? j->b1 : j->b2;
+    q1 = q2 = { 1.0, 0.0, 0.0, 0.0 };
+    if (g1) q1 = { (double)g1->q[0], (double)g1->q[1], (double)g1->q[2], (double)g1->q[3] };
+    if (g2) q2 = { (double)g2->q[0], (double)g2->q[1], (double)g2->q[2], (double)g2->q[3] };
+}
+// "this pose is angle zero" [ODE-recall dxJointHinge::computeInitialRelativeRotation, from dJointSetHingeAnchor / Axis]
+void take_zero_pose(dJointID j)
+{
+    if (j->type != dJointTypeHinge) return;
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    const dmx::Q4<double> r = dmx::qmul(dmx::qconj(q1), q2);
+    j->qrel0[0] = r.w; j->qrel0[1] = r.x; j->qrel0[2] = r.y; j->qrel0[3] = r.z;
+    if (j->world) j->world->limot_dirty = true;
+}
 void set_anchor(dJointID j, dReal x, dReal y, dReal z)
 {
     if (!j || j->type == dJointTypeContact) return;
@@ -885,6 +940,7 @@ void set_anchor(dJointID j, dReal x, dReal y, dReal z)
     const double p[3] = { (double)x, (double)y, (double)z };
     to_body(j->b1, p, true, j->anchor1);
     to_body(j->b2, p, true, j->anchor2);
+    take_zero_pose(j);
     if (j->world) j->world->art_dirty = true;
 }
 void get_anchor(dJointID j, int side, dVector3 out)
@@ -926,6 +982,7 @@ extern "C" void dJointSetHingeAxis(dJointID j, dReal x, dReal y, dReal z)
     const double a[3] = { x / l, y / l, z / l };
     to_body(j->b1, a, false, j->axis1);
     to_body(j->b2, a, false, j->axis2);
+    take_zero_pose(j);
     if (j->world) j->world->art_dirty = true;
 }
 extern "C" void dJointGetHingeAxis(dJointID j, dVector3 r)
@@ -933,6 +990,85 @@ extern "C" void dJointGetHingeAxis(dJointID j, dVector3 r)
     if (!j) return;
     if (j->world) j->world->to_host();
     to_world(j->b1, j->axis1, false, r);
+}
+// ---- a hinge's limit, motor, angle and rate.  dParamLoStop / HiStop / Vel / FMax are honoured (include/dmx_batch.h,
+// dmxBatchSetHingeLimots: fudge factor 1, no bounce, the world's ERP / CFM at the stops); the other parameters say so once each
+// call and are ignored.
+extern "C" void dJointSetHingeParam(dJointID j, int parameter, dReal value)
+{
+    if (!j || j->type != dJointTypeHinge) return;
+    const double v = (double)value;
+    const bool finite = v > -__builtin_huge_val() && v < __builtin_huge_val();
+    switch (parameter) {
+    case dParamLoStop: case dParamHiStop:
+        if (v != v) { fprintf(stderr, "libode_mi355: dJointSetHingeParam: a stop that is not a number; ignored\n"); return; }
+        (parameter == dParamLoStop ? j->lo_stop : j->hi_stop) = v;
+        break;
+    case dParamVel: case dParamFMax:
+        if (!finite) { fprintf(stderr, "libode_mi355: dJointSetHingeParam: dParamVel / dParamFMax must be finite; ignored\n"); return; }
+        (parameter == dParamVel ? j->vel : j->fmax) = v;
+        break;
+    default:
+        fprintf(stderr, "libode_mi355: dJointSetHingeParam: parameter %d is not supported (dParamLoStop, HiStop, Vel, FMax are); ignored\n", parameter);
+        return;
+    }
+    if (j->world) j->world->limot_dirty = true;
+}
+extern "C" dReal dJointGetHingeParam(dJointID j, int parameter)
+{
+    if (!j || j->type != dJointTypeHinge) return 0;
+    switch (parameter) {
+    case dParamLoStop: return (dReal)j->lo_stop;
+    case dParamHiStop: return (dReal)j->hi_stop;
+    case dParamVel: return (dReal)j->vel;
+    case dParamFMax: return (dReal)j->fmax;
+    default: return 0;
+    }
+}
+// the hinge axis of the sides as attached, in the world frame: u = R_1 axis1
+static void given_axis(const dxJoint *j, double u[3])
+{
+    dReal r[4];
+    if (j->rev) to_world(nullptr, j->axis2, false, r); else to_world(j->b1, j->axis1, false, r);
+    for (int k = 0; k < 3; k++) u[k] = (double)r[k];
+}
+extern "C" dReal dJointGetHingeAngle(dJointID j)
+{
+    if (!j || j->type != dJointTypeHinge || !j->b1) return 0;
+    if (j->world) j->world->to_host();
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    const double *ax = j->rev ? j->axis2 : j->axis1;
+    const dmx::Q4<double> q0 = { j->qrel0[0], j->qrel0[1], j->qrel0[2], j->qrel0[3] };
+    const dmx::V3<double> axis1 = { ax[0], ax[1], ax[2] };
+    return (dReal)dmx::hinge_angle(q1, q2, q0, axis1);
+}
+extern "C" dReal dJointGetHingeAngleRate(dJointID j)
+{
+    if (!j || j->type != dJointTypeHinge || !j->b1) return 0;
+    if (j->world) j->world->to_host();
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    double u[3], d[3];
+    given_axis(j, u);
+    for (int k = 0; k < 3; k++) d[k] = (g1 ? (double)g1->avel[k] : 0.0) - (g2 ? (double)g2->avel[k] : 0.0);
+    return (dReal)(u[0] * d[0] + u[1] * d[1] + u[2] * d[2]);
+}
+// +t u on body 1 and -t u on body 2 (the sides as attached), through the bodies' torque accumulators
+extern "C" void dJointAddHingeTorque(dJointID j, dReal torque)
+{
+    if (!j || j->type != dJointTypeHinge || !j->b1) return;
+    if (j->world) j->world->to_host();
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    double u[3];
+    given_axis(j, u);
+    const double t = (double)torque;
+    if (g1) dBodyAddTorque(const_cast<dxBody *>(g1), (dReal)(t * u[0]), (dReal)(t * u[1]), (dReal)(t * u[2]));
+    if (g2) dBodyAddTorque(const_cast<dxBody *>(g2), (dReal)(-t * u[0]), (dReal)(-t * u[1]), (dReal)(-t * u[2]));
 }
 // is there a joint between the two bodies (dAreConnectedExcluding: one whose type is not joint_type)?
 extern "C" int dAreConnectedExcluding(dBodyID b1, dBodyID b2, int joint_type)
