@@ -397,7 +397,8 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
         const bool ext = b->ext_pending && s == 0;
         P.ticks = ext ? 1 : std::min(per, nsteps - s);
         T *S = (T *)b->slab + slab_ix(0, first);
-        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream));
+        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev));
+        if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
         s += P.ticks;
     }
     b->stepped_with_plane = dmx_fused_contacts(b);

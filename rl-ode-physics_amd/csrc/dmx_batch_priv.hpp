@@ -49,6 +49,11 @@ struct dmxBatch {
     void *slab_alt = nullptr;
     bool flip_armed = false;         // the next fast launch starts a chunk: write out of place and swap
     bool flipped = false;            // this chunk has swapped: its snapshot is `slab_alt`
+    // The direction in which the next contact-free launch walks the tiles (dmx_sweep.hpp); flipped after every such launch, the
+    // out-of-place first launch of a chunk included (the lines it wrote into the other slab are what the next tick reads).
+    // Any direction is correct, so a rollback or a rebuilt chunk needs no care; a launch recorded into a HIP graph bakes its
+    // direction in -- the replays of one recording alternate among themselves as recorded, and whatever the neighbours do is correct.
+    bool sweep_rev = false;
     int snapshot_mode = DMX_SNAPSHOT_PINGPONG;
     int snap_kind = 0;               // how the chunk in flight keeps its start state (dmx_general.cpp: SNAP_*)
     // a collision-proof chunk left open by dmxBatchStep (dmx_general.cpp "lazy chunks"): its calls so far, to replay

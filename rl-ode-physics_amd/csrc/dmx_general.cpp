@@ -213,7 +213,8 @@ template <class T> int launch_fast(dmxBatch *b, const StepParams<T> &P, bool ext
             So = (T *)b->slab_alt;
         }
     }
-    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream));
+    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream, b->sweep_rev));
+    if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
     b->bp_fresh = false;                     // the poses have moved on from the ones the zones were built at
     if (So != S) {
         // ghost slots [n_active, n) are not stepped: their state follows by copy (a few boundary rows)

@@ -221,10 +221,17 @@ struct StepDiag {
 
 // S: the slab the tick reads (state, constants, zones); So: the slab the new state is written to -- S itself for an
 // in-place tick, or the batch's other slab (constants and zones are kept identical in both), which leaves S's state
-// behind untouched: the zero-cost snapshot of a collision-proof chunk (dmx_general.cpp)
+// behind untouched: the zero-cost snapshot of a collision-proof chunk (dmx_general.cpp).
+// rev: the direction in which a contact-free launch (integrate_free) walks the tiles (dmx_sweep.hpp; dmx_next_sweep in
+// dmx_batch_priv.hpp hands out alternating ones); the kernels of ticks with contacts take no notice of it.
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st);
+                       StepDiag *diag, hipStream_t st, int rev);
+// does launch_step take these parameters to integrate_free (no plane, no static geometry with contact slots)?
+template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
+{
+    return !(P.n_static > 0 && P.sbuf != nullptr) && !P.plane_on;
+}
 template <class T>
 hipError_t launch_islands(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                           StepDiag *diag, hipStream_t st);

@@ -21,6 +21,7 @@
 #include "dmx_math.hpp"
 #include "dmx_collide.hpp"
 #include "dmx_step_fused.hpp"
+#include "dmx_sweep.hpp"
 
 namespace dmx {
 
@@ -38,6 +39,12 @@ namespace dmx {
 // A dropped scene of unit-mass bodies under gravity along y (the reference's AddBody + dWorldSetGravity) then moves
 // 13 reals in and 6 out (pos.y, quat, lvel.y) = 19 per body-step; any other scene moves what it changes, up to the 30.
 // Same values into the same free_body_step either way: same bits.
+// Sweep order (dmx_sweep.hpp): `rev` -- a scalar argument of its own, StepParams does not grow -- says in which direction this
+// launch walks the tiles; workgroup b works on tile group sweep_block(b, gridDim.x, rev).  The callers alternate it from one
+// contact-free launch to the next, so that the lines the last launch touched last, still in the XCDs' L2s, are read first.  The
+// grid is a multiple of 8 workgroups (launch_step rounds it up; the surplus ones find their bodies at or beyond n and leave),
+// which keeps a tile group on the same residue b % 8, hence -- as the dispatcher is observed to deal -- on the same XCD, in both
+// directions.  Which workgroup steps a body changes nothing in the body's tick: same bits in either direction.
 // ---------------------------------------------------------------------------------------------
 enum : int { OPT_ELIDE = 1, OPT_UNI = 2 };
 template <class T> struct BitsOf;
@@ -50,7 +57,7 @@ template <class T> __device__ __forceinline__ bool bits_differ(T a, T b)
 }
 
 template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0>
-__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P)
+__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P, int rev)
 {
     constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
     constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
@@ -59,7 +66,7 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
     if (P.gate != nullptr && *P.gate == 0u) return;
     const int nticks = MULTI ? P.ticks : 1;         // MULTI = false: the one-tick kernel, no loop
     const bool in_place = ELIDE && So == S;         // wave-uniform: two kernel arguments
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+    for (int64_t i = sweep_block(blockIdx.x, gridDim.x, rev) * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
         T c[NLOAD];
@@ -506,7 +513,7 @@ constexpr int64_t kOneLaunchBodies = 256 * 4 * 64;
 
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st)
+                       StepDiag *diag, hipStream_t st, int rev)
 {
     if (P.n_static > 0 && P.sbuf != nullptr) {
         // bodies at static geometry: narrowphase against the plane and the static boxes, then the fused solve + integrate
@@ -532,7 +539,10 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         // with every load and store, 72 in the default instantiation below): measured, on the kernel moving all 30 reals,
         // 21.1 / 22.2 / 22.4 us per tick for 1 / 2 / 4 bodies per lane at 1 Mi f32 bodies
         // (profiles/r01_integrate_free_tiled_sweep.txt).  Pad bodies up to `stride` are valid memory.
-        const unsigned grid = blocks_for(n, 256);
+        // The grid is rounded up to a multiple of 8 workgroups (the surplus ones leave at the kernel's i < n): the sweep order
+        // (dmx_sweep.hpp) is defined on such grids, and workgroup b of every launch then has the same b % 8, whether the
+        // dispatcher starts its round-robin over the XCDs anew at each launch or carries it on.  `rev` is this launch's direction.
+        const unsigned grid = sweep_grid(blocks_for(n, 256));
         // what the result does not need (the kernel's header): store elision, and constants as arguments when the batch's are uniform.
         // The constants' scalars cost the f32 one-tick kernel three registers (71 -> 74 VGPRs = 6 waves per SIMD): a launch bound
         // of 7 waves (MWU) makes the allocator fit them into the 72 that 7 waves allow, without scratch; the kernels with force
@@ -543,7 +553,7 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
         constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
         const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0);
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P); };
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1); };
         if (P.ticks > 1) {
             if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
             else launch(integrate_free<T, false, 1, true, 0>);
@@ -656,7 +666,7 @@ hipError_t launch_soa_to_aos(const T *S, int64_t stride, int comp0, int k, int64
 
 #define DMX_INSTANTIATE(T)                                                                                         \
     template hipError_t launch_step<T>(T *, T *, const uint8_t *, int64_t, int64_t, const StepParams<T> &, bool,   \
-                                       StepDiag *, hipStream_t);                                                   \
+                                       StepDiag *, hipStream_t, int);                                              \
     template hipError_t launch_pack_transforms<T>(const T *, int64_t, int64_t, int64_t, T *, hipStream_t);         \
     template hipError_t launch_gather<T>(const T *, int64_t, const int32_t *, int64_t, T *, hipStream_t);          \
     template hipError_t launch_scatter<T>(T *, int64_t, const int32_t *, int64_t, const T *, hipStream_t);         \
