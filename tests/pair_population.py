@@ -484,11 +484,18 @@ def pop_id(key):
 def oracle_world(pop, dtype, shift=None, max_contacts=8):
     """the population in the oracle: plane, hull, static boxes, then the bodies ONE BY ONE in slot order (the bulk adders would impose
     an order by class); mass 1 and identity inertia are dBodyCreate's own.  -> (Oracle, World, scene)"""
-    sc = pop.scene(dtype, shift)
+    return oracle_world_of(pop.scene(dtype, shift), dtype, max_contacts)
+
+
+def oracle_world_of(sc, dtype, max_contacts=8, cfm=None):
+    """`oracle_world` for a scene already made (its values are cast to `dtype`); cfm None: the precision's default"""
+    sc = sc.astype(dtype)
     orc = Oracle(dtype)
     lib = orc.lib
     ow = orc.world()
     lib.orc_world_set_max_contacts(ow.w, int(max_contacts))
+    if cfm is not None:
+        lib.orc_world_set_cfm(ow.w, cfm)
     if sc.plane is not None:
         ow.add_plane(*sc.plane)
     if sc.hull_points is not None:
@@ -652,3 +659,144 @@ def analyse(pop, dtype, shift=None, max_contacts=8):
     out.update(colliding=int((st > 0).sum()), two_statics=int((touched >= 2).sum()), over_8=int((st > 8).sum()), aabb_marginal=marginal,
                per_cell=st, joints=js)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------ float32 against float64
+# One tick of a population in float32 against the same tick in float64 ON THE SAME float32 VALUES, both at cfm 1e-5 (the precisions'
+# defaults, 1e-5 / 1e-10, alone move the states at the 1e-3 level).  tests/test_pair_population.py measures and asserts this through the
+# two oracles; tests/test_gpu_precision_pairs.py holds the device to the same numbers.  DESIGN.md section 5, "float32 against float64
+# geometry", carries the tables.
+EPS32 = float(np.finfo(np.float32).eps)
+CFM_BOTH = 1e-5
+MAX_NOT_COMPARABLE = 0.08            # share of a population's cells whose contacts may differ in count, slot or by more than the band
+
+# k of the band k eps32 M, per collider: the largest deviation of the float32 oracle from the float64 numpy references of
+# tests/test_collider_geometry.py over >= 10^5 draws, near and far, x 2, rounded up to a power of two (the measured maxima are in
+# that file's F32_MEASURED and in DESIGN.md).  K_CONTACT, the band of a contact joint in the tick comparison, is their maximum.
+K_BAND = {"box_box": 4, "box_on_face": 2, "sphere_box": 2, "sphere_sphere": 2, "sphere_plane": 4, "box_plane": 8, "hulls": 2}
+K_CONTACT = max(K_BAND.values())
+
+# measured through the two oracles (tests/test_pair_population.py::test_one_tick_in_float32_against_float64 prints them): the largest |float32 - float64| over the
+# comparable cells' bodies per population class and place, velocities in eps32 M_world / h, poses in eps32 M_world.
+# (lvel, avel, pos, quat); the tolerance is 4 x these (the maxima sit 3-10 x over the p99: a long tail).
+TICK_MEASURED = {
+    "box_box": {"near": (0.01, 0.037, 0.25, 0.017), "far": (0.017, 0.046, 0.45, 0.024)},
+    "sphere_box": {"near": (0.08, 0.027, 0.25, 0.011), "far": (0.26, 0.16, 0.44, 0.068)},
+    "sphere_sphere": {"near": (0.0014, 0.012, 0.25, 0.0061), "far": (0.0024, 0.023, 0.44, 0.011)},
+    "hull_hull": {"near": (0.061, 0.17, 0.27, 0.077), "far": (0.5, 0.45, 0.59, 0.2)},
+    "sphere_hull": {"near": (0.0033, 0.0099, 0.25, 0.0049), "far": (0.0063, 0.022, 0.45, 0.01)},
+    "box_hull": {"near": (0.054, 0.2, 0.27, 0.089), "far": (0.29, 0.41, 0.48, 0.19)},
+    "on_plane": {"near": (0.022, 0.051, 0.26, 0.029), "far": (0.034, 0.072, 0.42, 0.034)},
+    "on_statics": {"near": (0.11, 0.089, 0.31, 0.05), "far": (0.1, 0.16, 0.56, 0.063)},
+}
+TICK_FACTOR = 4.0
+
+
+def tick_tolerance(name, far):
+    """(lvel, avel, pos, quat) tolerances in the units of `precision_tick`, for a population class and place"""
+    return tuple(TICK_FACTOR * v for v in TICK_MEASURED[name]["far" if far else "near"])
+
+
+def scene_in_float32_values(pop, shift=None):
+    """the population's float32 scene and the same VALUES as a float64 scene: the plane and the static boxes, which `astype` leaves as
+    Python floats, rounded to float32 too"""
+    sc = pop.scene("float32", shift)
+    r = lambda v: float(np.float32(v))
+    plane = None if sc.plane is None else tuple(r(v) for v in sc.plane)
+    statics = None if not sc.static_boxes else [(tuple(r(v) for v in sz), tuple(r(v) for v in at), [r(v) for v in R12])
+                                                for sz, at, R12 in sc.static_boxes]
+    sc32 = pkg.scenes.Scene(sc.pos, sc.quat, sc.lvel, sc.avel, sc.mass, sc.inertia, sc.sides, sc.gtype, plane, sc.hull_points,
+                            sc.hull_planes, statics)
+    return sc32, sc32.astype("float64")
+
+
+def _extents(pop, sc):
+    """per body: the bounding radius and the smallest extent (sphere: r; box: half the diagonal / the least side; hull: its radius /
+    twice the nearest face's distance from the centre)"""
+    s = np.asarray(sc.sides, float)
+    big = np.where(sc.gtype == SPHERE, s[:, 0], 0.5 * np.linalg.norm(s, axis=1))
+    small = np.where(sc.gtype == SPHERE, s[:, 0], s.min(axis=1))
+    if pop.hull is not None:
+        cv = sc.gtype == CONVEX
+        big[cv] = pop.hull.radius
+        small[cv] = 2.0 * float(np.min(pop.hull.planes[:, 3]))
+    return big, small
+
+
+def _static_reach(sc):
+    """the static geometry's own numbers: (|plane offset|, normalised; the largest |coordinate| of the static boxes' AABBs)"""
+    off = 0.0 if sc.plane is None else abs(sc.plane[3]) / float(np.linalg.norm(sc.plane[:3]))
+    far = 0.0
+    if sc.static_boxes:
+        lo, hi = static_aabbs(sc)
+        far = float(max(np.abs(lo).max(), np.abs(hi).max()))
+    return off, far
+
+
+@functools.lru_cache(maxsize=None)
+def precision_tick(key, far, k_contact=K_CONTACT):
+    """One tick of population `key` through the float32 and the float64 oracle on the same float32 values, cfm 1e-5 in both.
+    COMPARABLE cells, decided from the two oracles' joints alone: the same contact count, every contact in the same slot between the
+    same bodies, pos and depth within band = k eps32 M_cell and the normal within band / (the cell's smallest extent) radians;
+    M_cell = the largest |coordinate| of the cell's bodies and of the static boxes + the bodies' bounding radii + |plane offset|.  -> a dict; the states
+    are read-only."""
+    pop = get(*key)
+    sc32, sc64 = scene_in_float32_values(pop, FAR if far else None)
+    nc = int(pop.cell.max()) + 1
+    side = {}
+    for dtype, sc in (("float32", sc32), ("float64", sc64)):
+        orc, ow, _ = oracle_world_of(sc, dtype, cfm=CFM_BOTH)
+        ow.tick(orc.dtype.type(H))
+        st = ow.state()
+        for a in st:
+            a.setflags(write=False)
+        per = [[] for _ in range(nc)]
+        for j in ow.joints():
+            per[pop.cell[j[0]]].append(j)
+        side[dtype] = (st, per, ow.n_contacts())
+        ow.close()
+    big, small = _extents(pop, sc64)
+    plane_off, static_far = _static_reach(sc64)
+    m_body = np.abs(sc64.pos).max(axis=1)
+    m_cell = np.zeros(nc); ext = np.full(nc, np.inf)
+    r_cell = np.zeros(nc)
+    np.maximum.at(m_cell, pop.cell, m_body)
+    np.add.at(r_cell, pop.cell, big)
+    np.minimum.at(ext, pop.cell, small)
+    m_cell = np.maximum(m_cell, static_far) + r_cell + plane_off
+    band = k_contact * EPS32 * m_cell
+    comparable = np.ones(nc, bool)
+    by_count = 0
+    worst = np.zeros(3)                                   # pos, depth (in eps32 M_cell), normal (in eps32 M_cell / extent) over same-slot contacts
+    for c in range(nc):
+        a, b = side["float32"][1][c], side["float64"][1][c]
+        if len(a) != len(b):
+            comparable[c] = False; by_count += 1
+            continue
+        for ja, jb in zip(a, b):
+            if ja[0] != jb[0] or ja[1] != jb[1]:
+                comparable[c] = False
+                break
+            dp = float(np.max(np.abs(np.subtract(ja[2], jb[2])))); dd = abs(ja[4] - jb[4])
+            dn = float(np.linalg.norm(np.subtract(ja[3], jb[3])))
+            if dp > band[c] or dd > band[c] or dn > band[c] / ext[c]:
+                comparable[c] = False
+                break
+            u = EPS32 * m_cell[c]
+            worst = np.maximum(worst, [dp / u, dd / u, dn * ext[c] / u])
+    m_world = float(max(m_body.max(), static_far) + big.max() + plane_off)
+    body_ok = comparable[pop.cell]
+    units = (EPS32 * m_world / H, EPS32 * m_world / H, EPS32 * m_world, EPS32 * m_world)          # lvel, avel, pos, quat
+    s32, s64 = side["float32"][0], side["float64"][0]
+    order = (2, 3, 0, 1)                                   # state() is (pos, quat, lvel, avel)
+    dev = tuple(float(np.max(np.abs(s32[i][body_ok].astype(float) - s64[i][body_ok]))) / u for i, u in zip(order, units))
+    n32 = np.array([len(x) for x in side["float32"][1]]); n64 = np.array([len(x) for x in side["float64"][1]])
+    return dict(pop=pop, sc32=sc32, sc64=sc64, state32=s32, state64=s64, comparable=comparable, body_ok=body_ok, m_world=m_world,
+                units=units, dev=dev, not_comparable=int((~comparable).sum()), by_count=by_count, cells=nc, contacts32=n32, contacts64=n64,
+                total32=side["float32"][2], total64=side["float64"][2], contact_dev=tuple(float(v) for v in worst))
+
+
+def deviation(state_a, state_b, body_ok, units):
+    """(lvel, avel, pos, quat) largest |a - b| over the bodies of `body_ok`, in `units`; states are (pos, quat, lvel, avel)"""
+    return tuple(float(np.max(np.abs(np.asarray(state_a[i], float)[body_ok] - np.asarray(state_b[i], float)[body_ok]))) / u
+                 for i, u in zip((2, 3, 0, 1), units))

@@ -1,6 +1,8 @@
 """The populations of tests/pair_population.py through the oracle alone (no GPU), in float64 and float32: the COVERAGE CONDITIONS --
 conditions on the inputs of a one-tick device-against-oracle comparison, not measurements of anything under test.  A generator that misses
-one is changed; the bound is not.  DESIGN.md section 5 carries the table these tests print."""
+one is changed; the bound is not.  DESIGN.md section 5 carries the table these tests print.  Last: one tick of every population in
+float32 against the same tick in float64 (pair_population.precision_tick), the numbers tests/test_gpu_precision_pairs.py holds the
+device to."""
 import numpy as np
 import pytest
 
@@ -123,3 +125,23 @@ def test_far_translation_keeps_the_shares(key):
         assert a["colliding"] >= 0.6 * a["bodies"]
     else:
         assert a["colliding"] >= 0.6 * a["bodies"] and a["two_statics"] >= 50 and a["over_8"] >= 20
+
+
+@pytest.mark.parametrize("far", [False, True], ids=["near", "far"])
+@pytest.mark.parametrize("key", pp.ALL, ids=pp.pop_id)
+def test_one_tick_in_float32_against_float64(key, far):
+    """One tick through the float32 oracle against the float64 oracle on the same float32 values, cfm 1e-5 in both, near the origin and
+    at FAR.  Cells whose contacts differ in count, slot or by more than the band (pp.precision_tick) are left out -- at most 8 % of a
+    population's cells, or its generator is changed; on the rest the states agree within 4 x the maxima measured here (pp.TICK_MEASURED,
+    per population class and place; this test prints what it measures), velocities in eps32 M_world / h, poses in eps32 M_world."""
+    r = pp.precision_tick(key, far)
+    share = r["not_comparable"] / r["cells"]
+    print(f"PRECISION {pp.pop_id(key)} {'far' if far else 'near'}: M_world {r['m_world']:.0f} m; not comparable {r['not_comparable']} of {r['cells']} cells "
+          f"({100 * share:.2f} %, {r['by_count']} by count); lvel / avel / pos / quat " + " / ".join(f"{v:.3g}" for v in r["dev"])
+          + "; same-slot contacts pos / depth / normal " + " / ".join(f"{v:.3g}" for v in r["contact_dev"]))
+    assert share <= pp.MAX_NOT_COMPARABLE, f"{pp.pop_id(key)}: {100 * share:.1f} % of the cells not comparable: change the generator"
+    assert r["comparable"].sum() >= 0.5 * r["cells"]
+    for a in r["state32"] + r["state64"]:
+        assert np.all(np.isfinite(a))
+    for name, got, tol in zip(("lvel", "avel", "pos", "quat"), r["dev"], pp.tick_tolerance(key[0], far)):
+        assert got <= tol, f"{pp.pop_id(key)} {name}: float32 is {got:.3g} units from float64, tolerance {tol:.3g}"
