@@ -16,8 +16,9 @@ namespace dmx {
 // A body touching static geometry only (the ground plane, static boxes) is an island of its own: all its rows share the one
 // body, so the sweep is a pure chain -- a wavefront per island (solve_island_wg) would run one lane at a time.  Here a LANE
 // owns the island: up to SINGLE_MAXC contacts x 3 rows live in its registers (no row traffic at all), 64 islands per wave.
-// Same phase arithmetic as stage_body / contact_rows / body_tmp / row_setup / row_sor / finish_body with the second body
-// absent, operation for operation: same bits.  (What a box resting on the reference's floor, main.c:115, costs per tick.)
+// stage_body, body_tmp and finish_body are the general island step's own; contact_rows, row_setup and row_sor are restated here with
+// the second body absent (the "contact_rows" block twice, in solve_singles_body and solve_singles_lds_body: change both), held to the
+// general path bit for bit by tests/test_gpu_static.py and tests/test_gpu_parity.py.  (What a box resting on the reference's floor, main.c:115, costs per tick.)
 constexpr int SINGLE_MAXC = 4;          // rows in registers (solve_singles)
 constexpr int SINGLE_MAXC_LDS = 8;      // rows in LDS (solve_singles_lds): a convex hull's eight contacts with the floor
 

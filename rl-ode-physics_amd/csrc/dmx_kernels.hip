@@ -151,7 +151,9 @@ __global__ __launch_bounds__(256, MINW) void step_plane(T *S, T *So, const uint8
 // (AddBodyMap, main.c:735-761; the reference's floor is one, main.c:115).  The contacts come from np_static /
 // np_convex_static (dmx_narrow.hip) in joint creation order and canonical form; here: rows (normal + 2 friction per
 // contact, every contact with its own normal) -> SOR-PGS sweeps -> velocity update -> integrate, one lane per body, rows in
-// registers, the arithmetic of step_plane / solve_singles operation for operation (same bits as the oracle).
+// registers.  Around the rows the tick is tick_head / tick_tail (dmx_step_fused.hpp), as in step_plane_body and free_body_step; the
+// loads, rows, sweep, stores and diagnostics are a second copy of step_plane_body's, with every contact's own normal and M^-1 J^T's
+// linear part kept per row: change both (same bits as the oracle, tests/test_gpu_static.py).
 // Two instantiations share a tick: NC = 4 steps the bodies with 0..4 contacts (free bodies included), NC = 8 -- launched
 // behind it when the batch may have such bodies (P.have8) -- those with 5..8; each leaves the other's lanes alone.  A body
 // with more contacts than the buffer holds raises BPF_NOFAST (the exact path steps it: the chunk is rolled back).
@@ -197,15 +199,9 @@ __global__ __launch_bounds__(256, MINW) void step_contacts(T *S, T *So, int64_t 
         }
 
         const T h = P.h;
-        const M3<T> R = quat_to_R(q);
         const T invMass = T(1) / mass;
-        const V3<T> invIb = { T(1) / Ib.x, T(1) / Ib.y, T(1) / Ib.z };
-        facc.x = fma_(mass, P.g.x, facc.x); facc.y = fma_(mass, P.g.y, facc.y); facc.z = fma_(mass, P.g.z, facc.z);
-        const M3<T> invIw = rotate_diag(R, invIb);
-        if (P.gyro != 0 && !isotropic(Ib)) {
-            const M3<T> Iw = rotate_diag(R, Ib);
-            add_gyro_torque(tacc, Iw, w, h, P.gyro);
-        }
+        M3<T> invIw;
+        tick_head(q, w, mass, Ib, facc, tacc, P.g, h, P.gyro, invIw);
         const int nc = cnt > SC_MAXC ? SC_MAXC : cnt;
         my_contacts = nc;
         int ncu = 0;     // largest contact count among the wave's lanes stepped here (wave-uniform by construction)
@@ -283,7 +279,8 @@ __global__ __launch_bounds__(256, MINW) void step_contacts(T *S, T *So, int64_t 
             // ---- SOR-PGS: lambda = 0 start, rows in creation order; branch-free row update as in step_plane ----
             V3<T> fl = { T(0), T(0), T(0) }, fa = { T(0), T(0), T(0) };
             T rsum = T(0);
-            // (FULL: as in step_plane -- every contact slot taken in every lane stepped here, friction rows present)
+            // (the second copy of step_plane_body's sweep and dispatch, dmx_step_fused.hpp: change both.  FULL: as there -- every contact
+            //  slot taken in every lane stepped here, friction rows present)
             auto sweep = [&](auto FAST, auto LAST, auto FULL) {
 #pragma unroll
                 for (int k = 0; k < NC; k++) {
@@ -338,14 +335,7 @@ __global__ __launch_bounds__(256, MINW) void step_contacts(T *S, T *So, int64_t 
             }
         }
 
-        // ---- v += h M^-1 f_ext ; integrate ----------------------------------------------------
-        const T hm = h * invMass;
-        v.x = fma_(hm, facc.x, v.x); v.y = fma_(hm, facc.y, v.y); v.z = fma_(hm, facc.z, v.z);
-        tacc.x *= h; tacc.y *= h; tacc.z *= h;
-        const V3<T> dw = mulv(invIw, tacc);
-        w.x += dw.x; w.y += dw.y; w.z += dw.z;
-        x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
-        integrate_quat(q, w, h);
+        tick_tail(x, q, v, w, invMass, invIw, facc, tacc, h);
         pack_boundary(P, i, x, q, v, w);
 
         So[slab_ix(C_POS + 0, i)] = x.x; So[slab_ix(C_POS + 1, i)] = x.y; So[slab_ix(C_POS + 2, i)] = x.z;

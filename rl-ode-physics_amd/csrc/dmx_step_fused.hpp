@@ -1,5 +1,6 @@
-// dmx_step_fused.hpp -- the fused tick of a single-body island on the ground plane as a DEVICE function (step_plane_body), with
-// the helpers the fused kernels share, so that the step can ride in another kernel's launch: dmx_kernels.hip wraps it as
+// dmx_step_fused.hpp -- the head and the tail of one body's tick (tick_head, tick_tail: what free_body_step, step_plane_body and
+// step_contacts all do around their rows), and the fused tick of a single-body island on the ground plane as a DEVICE function
+// (step_plane_body), with the helpers the fused kernels share, so that the step can ride in another kernel's launch: dmx_kernels.hip wraps it as
 // step_plane; dmx_islands.hip puts it behind the island solve of a small-scene exact tick (solve_islands_and_step: the two
 // touch disjoint bodies, one launch runs both kinds of workgroup side by side).
 #pragma once
@@ -56,24 +57,36 @@ __device__ __forceinline__ void pack_boundary(const StepParams<T> &P, int64_t i,
     o[7] = v.x; o[8] = v.y; o[9] = v.z; o[10] = w.x; o[11] = w.y; o[12] = w.z;
 }
 
-// One body: external force/torque -> new velocities (no constraints) -> new pose.
-//   facc = fext + m g ; tacc = text + gyro
-//   v += (h/m) facc ; w += Iw^-1 (h tacc)
+// ---------------------------------------------------------------------------------------------
+// One body's tick around the constraint solve: integrate_free (through free_body_step), step_plane_body and step_contacts call
+// these two functions, so what the tick computes for a body without rows is defined here, once.  The callers compute 1/m themselves,
+// the fused kernels ahead of the head and free_body_step as the tail's argument: that is where the statements stood, and it keeps
+// every kernel's code as it was (profiles/fused_dedup_resources.txt).
+//   facc = fext + m g ; tacc = text + gyro                   (tick_head)
+//   [ rows, sweeps: v += h M^-1 J^T lambda ]                  (the caller's)
+//   v += (h/m) facc ; w += Iw^-1 (h tacc)                     (tick_tail)
 //   x += h v ; q += h/2 (0,w) q ; q /= |q|
+// ---------------------------------------------------------------------------------------------
+// gravity into facc, the gyroscopic torque into tacc; the world-frame inverse inertia for the tail and for whoever builds rows
 template <class T>
-__device__ __forceinline__ void free_body_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w,
-                                               T mass, const V3<T> &Ib, V3<T> facc, V3<T> tacc,
-                                               const V3<T> &g, T h, int gyro)
+__device__ __forceinline__ void tick_head(const Q4<T> &q, const V3<T> &w, T mass, const V3<T> &Ib, V3<T> &facc, V3<T> &tacc,
+                                          const V3<T> &g, T h, int gyro, M3<T> &invIw)
 {
     const M3<T> R = quat_to_R(q);
-    const T invMass = T(1) / mass;
     const V3<T> invIb = { T(1) / Ib.x, T(1) / Ib.y, T(1) / Ib.z };
     facc.x = fma_(mass, g.x, facc.x); facc.y = fma_(mass, g.y, facc.y); facc.z = fma_(mass, g.z, facc.z);
-    const M3<T> invIw = rotate_diag(R, invIb);
+    invIw = rotate_diag(R, invIb);
     if (gyro != 0 && !isotropic(Ib)) {
         const M3<T> Iw = rotate_diag(R, Ib);
         add_gyro_torque(tacc, Iw, w, h, gyro);
     }
+}
+
+// v += h M^-1 f ; w += Iw^-1 (h tacc) ; integrate
+template <class T>
+__device__ __forceinline__ void tick_tail(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T invMass, const M3<T> &invIw,
+                                          const V3<T> &facc, V3<T> tacc, T h)
+{
     const T hm = h * invMass;
     v.x = fma_(hm, facc.x, v.x); v.y = fma_(hm, facc.y, v.y); v.z = fma_(hm, facc.z, v.z);
     tacc.x *= h; tacc.y *= h; tacc.z *= h;
@@ -81,6 +94,17 @@ __device__ __forceinline__ void free_body_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<
     w.x += dw.x; w.y += dw.y; w.z += dw.z;
     x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
     integrate_quat(q, w, h);
+}
+
+// a body without rows: head and tail, nothing between them
+template <class T>
+__device__ __forceinline__ void free_body_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w,
+                                               T mass, const V3<T> &Ib, V3<T> facc, V3<T> tacc,
+                                               const V3<T> &g, T h, int gyro)
+{
+    M3<T> invIw;
+    tick_head(q, w, mass, Ib, facc, tacc, g, h, gyro, invIw);
+    tick_tail(x, q, v, w, T(1) / mass, invIw, facc, tacc, h);
 }
 
 template <class T> __device__ __forceinline__ T wave_sum(T x)
@@ -131,15 +155,10 @@ __device__ __forceinline__ void step_plane_body(T *S, T *So, const uint8_t *__re
         }
 
         const T h = P.h;
-        const M3<T> R = quat_to_R(q);
+        const M3<T> R = quat_to_R(q);      // (the box collider's; the head's own is the same value)
         const T invMass = T(1) / mass;
-        const V3<T> invIb = { T(1) / Ib.x, T(1) / Ib.y, T(1) / Ib.z };
-        facc.x = fma_(mass, P.g.x, facc.x); facc.y = fma_(mass, P.g.y, facc.y); facc.z = fma_(mass, P.g.z, facc.z);
-        const M3<T> invIw = rotate_diag(R, invIb);
-        if (P.gyro != 0 && !isotropic(Ib)) {
-            const M3<T> Iw = rotate_diag(R, Ib);
-            add_gyro_torque(tacc, Iw, w, h, P.gyro);
-        }
+        M3<T> invIw;
+        tick_head(q, w, mass, Ib, facc, tacc, P.g, h, P.gyro, invIw);
 
         // ---- narrowphase (dCollide) --------------------------------------------------------
         constexpr int MAXC = NC, MAXR = 3 * NC;
@@ -237,6 +256,8 @@ __device__ __forceinline__ void step_plane_body(T *S, T *So, const uint8_t *__re
             for (int k = 0; k < MAXC; k++)
                 if (__ballot(nc > k) != 0ull) ncu = k + 1;
             T rsum = T(0);
+            // (The rows, the sweep and its dispatch exist twice, here and in step_contacts (dmx_kernels.hip), which keeps M^-1 J^T's
+            //  linear part per row: change both.  Why they are not shared yet: DESIGN.md section 4.)
             // One sweep over the wave's rows.  FAST: the friction rows are unbounded (mu = inf, the reference's surface): no
             // friction clamp.  LAST: only the final sweep tallies |delta lambda|.  Same arithmetic in every variant.
             // FULL: every contact slot of every active lane is taken and friction rows exist (a box resting on the plane: four
@@ -294,14 +315,7 @@ __device__ __forceinline__ void step_plane_body(T *S, T *So, const uint8_t *__re
             w.x = fma_(h, fa.x, w.x); w.y = fma_(h, fa.y, w.y); w.z = fma_(h, fa.z, w.z);
         }
 
-        // ---- v += h M^-1 f_ext ; integrate ----------------------------------------------------
-        const T hm = h * invMass;
-        v.x = fma_(hm, facc.x, v.x); v.y = fma_(hm, facc.y, v.y); v.z = fma_(hm, facc.z, v.z);
-        tacc.x *= h; tacc.y *= h; tacc.z *= h;
-        const V3<T> dw = mulv(invIw, tacc);
-        w.x += dw.x; w.y += dw.y; w.z += dw.z;
-        x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
-        integrate_quat(q, w, h);
+        tick_tail(x, q, v, w, invMass, invIw, facc, tacc, h);
         pack_boundary(P, i, x, q, v, w);
 
         So[slab_ix(C_POS + 0, i)] = x.x; So[slab_ix(C_POS + 1, i)] = x.y; So[slab_ix(C_POS + 2, i)] = x.z;

@@ -7,11 +7,12 @@ than eight workgroups of 256, a partial workgroup, a partial wavefront) of every
            tests/test_integrator_reference.py recorded ON THE CPU of the float64 device; no tolerance is taken from the device
   5. / 6.  nothing is NaN / Inf where the reference is finite; |q| = 1 within 4 eps on every path
 
-The copies: free_body_step (integrate_free; every elision mask, 1 and 7 ticks per launch, the out-of-place first launch of a chunk
-and the in-place ones behind it, with and without external force / torque; per-body constants and -- batches with ONE mass and one
-anisotropic inertia -- constants passed as kernel arguments), the one inlined in step_plane_body (a ground plane 1 km below), the one
-in step_contacts (a static box 1 km away), and the island path's (step_joints without joints), which also serves the single-launch
-tick of small worlds.  One tick runs on the `stress` population, 64 ticks on `flight` (the ranges in which the reference itself is
+The paths: free_body_step = tick_head + tick_tail (integrate_free; every elision mask, 1 and 7 ticks per launch, the out-of-place
+first launch of a chunk and the in-place ones behind it, with and without external force / torque; per-body constants and -- batches
+with ONE mass and one anisotropic inertia -- constants passed as kernel arguments), the same two functions called by step_plane_body
+(a ground plane 1 km below) and by step_contacts (a static box 1 km away), each behind its own loads and before its own stores, and
+the island path's stage_body + finish_body, the one other definition (step_joints without joints), which also serves the
+single-launch tick of small worlds.  One tick runs on the `stress` population, 64 ticks on `flight` (the ranges in which the reference itself is
 stable)."""
 import functools
 

@@ -91,11 +91,8 @@ def test_fused_and_exact_static_paths_agree_with_the_oracle(dtype):
     _same(states[False], ow.state())
 
 
-@pytest.mark.parametrize("dtype", ["float64", "float32"])
-def test_boxes_across_a_narrow_plank_have_five_to_eight_contacts(dtype):
-    """a box lying diagonally across a plank narrower than itself: the clipped face is a hexagon / octagon -- more than
-    four contacts from ONE geom pair, the second step_contacts launch (rows of 5..8 contacts in registers) steps it"""
-    n = 24
+def _boxes_across_a_plank(n=24):
+    """boxes lying diagonally across a plank narrower than themselves -> (pos, quat, mass, inertia, sides), the plank"""
     rng = np.random.default_rng(5)
     pos = np.stack([np.arange(n) * 3.0 - 1.5 * n, np.full(n, 0.62), np.zeros(n)], axis=1)
     yaw = rng.uniform(0.5, 1.0, n)
@@ -103,8 +100,22 @@ def test_boxes_across_a_narrow_plank_have_five_to_eight_contacts(dtype):
     sides = np.tile([1.6, 0.4, 1.6], (n, 1))
     mass = np.full((n, 1), 1.6 * 0.4 * 1.6)
     inertia = np.stack([mass[:, 0] / 12 * (0.4 ** 2 + 1.6 ** 2), mass[:, 0] / 12 * (1.6 ** 2 + 1.6 ** 2), mass[:, 0] / 12 * (0.4 ** 2 + 1.6 ** 2)], axis=1)
-    scene = pkg.scenes.Scene(pos, quat, np.zeros((n, 3)), np.zeros((n, 3)), mass, inertia, sides, np.full(n, pkg.scenes.GEOM_BOX, np.uint8), None).astype(dtype)
     plank = [((200.0, 0.8, 0.9), (0.0, 0.0, 0.0), pkg.scenes._rot_z(0.0))]
+    return (pos, quat, mass, inertia, sides), plank
+
+
+def _box_scene(pos, quat, mass, inertia, sides, dtype):
+    n = len(pos)
+    return pkg.scenes.Scene(pos, quat, np.zeros((n, 3)), np.zeros((n, 3)), mass, inertia, sides, np.full(n, pkg.scenes.GEOM_BOX, np.uint8), None).astype(dtype)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_boxes_across_a_narrow_plank_have_five_to_eight_contacts(dtype):
+    """a box lying diagonally across a plank narrower than itself: the clipped face is a hexagon / octagon -- more than
+    four contacts from ONE geom pair, the second step_contacts launch (rows of 5..8 contacts in registers) steps it"""
+    n = 24
+    boxes, plank = _boxes_across_a_plank(n)
+    scene = _box_scene(*boxes, dtype)
     steps = 90
     ow = _oracle(dtype, scene, plank)
     most = 0
@@ -119,6 +130,70 @@ def test_boxes_across_a_narrow_plank_have_five_to_eight_contacts(dtype):
     assert st["careful_ticks"] == 0 and st["fast_ticks"] == steps, st          # the chunk that met such a body first ran again, fused
     assert w.last_contact_count() == ow.n_contacts()
     w.close()
+
+
+@pytest.mark.parametrize("forced", [False, True], ids=["unforced", "forced"])
+def test_two_launch_form_steps_five_to_eight_contacts_in_a_large_float32_batch(forced):
+    """A float32 batch of more than 65 536 bodies takes the tick at static geometry in two launches: the 24 boxes across the plank
+    (five to eight contacts each: the second launch steps them) among 65 576 unit boxes at rest 1 km up, on a grid of 3 m pitch far
+    from the plank, which fall about 11 m in the 90 ticks and touch nothing.  A body at static geometry is an island of its own:
+    the 24 end up, bit for bit, where the float32 oracle puts them in the scene without the others; the others where a batch that
+    holds only them, with no static geometry (integrate_free, elision 0), puts them.
+    forced: a force and a torque on the 24, uploaded before the first step, the oracle's accumulators alike.  Pending accumulators
+    send the first tick the careful way (as tests/test_gpu_integrator.py has it for the free bodies); the boxes still hang 0.02 m
+    above the plank then, so the external-force form of the first launch steps everybody without rows and that of the second
+    finds nobody and leaves: this variant covers the accumulators' way through a large batch and the 89 fast ticks behind it.
+    NOT covered, here or elsewhere: step_contacts<float, true, 1, 8, false> building rows -- with the collision proof on, a
+    body that already has five to eight contacts never meets pending accumulators on the fused path."""
+    dtype, nb, steps = "float32", 24, 90
+    side = 257
+    nf = 65536 + 40
+    assert nf <= side * side
+    boxes, plank = _boxes_across_a_plank(nb)
+    k = np.arange(nf)
+    fpos = np.stack([300.0 + 3.0 * (k % side), np.full(nf, 1000.0), 300.0 + 3.0 * (k // side)], axis=1)
+    fillers = (fpos, np.tile([1.0, 0.0, 0.0, 0.0], (nf, 1)), np.ones((nf, 1)), np.full((nf, 3), 1.0 / 6.0), np.ones((nf, 3)))
+    scene = _box_scene(*boxes, dtype)
+    alone = _box_scene(*fillers, dtype)
+    both = _box_scene(*(np.concatenate([a, b]) for a, b in zip(boxes, fillers)), dtype)
+    assert both.n == 65600
+    rng = np.random.default_rng(11)
+    force = np.zeros((both.n, 3), dtype); torque = np.zeros((both.n, 3), dtype)
+    if forced:
+        force[:nb] = rng.uniform(-2.0, 2.0, (nb, 3)); torque[:nb] = rng.uniform(-0.5, 0.5, (nb, 3))
+
+    orc = _orc(dtype)
+    ow = _oracle(dtype, scene, plank)
+    most = 0
+    for b in range(nb if forced else 0):
+        orc.lib.orc_body_add_force(ow.w, b, *[float(x) for x in force[b]])
+        orc.lib.orc_body_add_torque(ow.w, b, *[float(x) for x in torque[b]])
+    for _ in range(steps):
+        ow.tick(H)
+        most = max(most, int(_contacts_per_body(ow, nb).max()))
+    assert 5 <= most <= 8, most
+
+    w = _world(dtype, both, plank)
+    if forced:
+        w.upload(pkg.batch.FORCE, force); w.upload(pkg.batch.TORQUE, torque)
+    w.step(H, steps)
+    got = w.state()
+    st = w.collision_stats()
+    contacts = w.last_contact_count()
+    w.close()
+    _same([a[:nb] for a in got], ow.state())
+    want = (steps - 1, 1) if forced else (steps, 0)
+    assert (st["fast_ticks"], st["careful_ticks"]) == want, st
+    assert contacts == ow.n_contacts()              # the fillers have none
+
+    w = pkg.BatchWorld(alone.n, dtype=dtype)
+    w.set_elision(0)
+    w.load_scene(alone)
+    w.step(H, steps)
+    free = w.state()
+    w.close()
+    assert free[0][:, 1].max() < 990.0              # (they fell)
+    _same([a[nb:] for a in got], free)
 
 
 def test_box_wedged_in_a_corner_overflows_the_fused_buffer():
