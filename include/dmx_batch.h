@@ -208,6 +208,22 @@ int dmxBatchSetTicksPerLaunch(dmxBatchID b, int ticks);
  * sees a later upload of mass or inertia like an eager tick does.  Default: both (DMX_ELIDE=<mask> in the environment changes the default); 0: every load and store. */
 enum { DMX_ELIDE_STORES = 1, DMX_ELIDE_CONSTANTS = 2 };
 int dmxBatchSetElision(dmxBatchID b, int mask);
+/* A third removal, active only while DMX_ELIDE_STORES is on: loads of lateral state a tile has proven fixed.  The library keeps
+ * one word per 64-body tile on the device; an axis k of a tile is fixed once a launch has loaded pos.k and lvel.k of the tile's
+ * bodies, run the tick and found the bits of both unchanged in every lane -- the tick computes them from themselves, h, g.k and
+ * the mass, so the same launch again would find the same.  One-tick launches over the whole active slab then leave out the
+ * loads, ballots and stores of pos.x/lvel.x and pos.z/lvel.z in such tiles (13 -> 9 state loads for bodies dropped at rest under
+ * gravity along y), for as long as nothing but such launches with the same h, gravity, mass, gyro mode, active count and elision
+ * mask touches the batch: any other call of this API than dmxBatchStep / dmxBatchChunkTick(s) themselves, a rollback, an exact or
+ * joints tick makes the next launch load everything and establish the words anew (csrc/dmx_fixed.hpp has the rule).  Any
+ * dmxBatchDevicePtr call, and any stepping call made while the batch's stream is being captured into a HIP graph, end it for the
+ * batch's lifetime.  Same results bit for bit.  Default on (DMX_ELIDE_LOADS=0 in the environment, read at dmxBatchCreate: off). */
+int dmxBatchSetLoadElision(dmxBatchID b, int on);
+/* for tests and diagnostics, never on a hot path (takes the counts, then settles the batch -- which, like every observer, breaks
+ * the chain: that break shows in the next call's count -- and reads the words back): [0] launches that established the
+ * words, [1] lean launches, [2] times the chain was broken, [3] 1 once ended for good, [4] / [5] tiles of the active range whose
+ * word says x / z fixed, as the last establishing or lean launch left them */
+int dmxBatchLoadElisionStats(dmxBatchID b, int64_t out[6]);
 int dmxBatchCollisionStats(dmxBatchID b, int64_t out[6]);
 /* the same six numbers and [6] AABB pairs met so far that had no collider (always 0 since every class pair has one), [7] exact ticks
  * of the one-workgroup pipeline whose island solve and fused step were enqueued before the host had the tick's counts, and stood

@@ -24,7 +24,7 @@ BATCH_SYMBOLS = [
     "dmxBatchChunkBegin", "dmxBatchChunkTick", "dmxBatchCheckZonesOnStream", "dmxBatchChunkEnd",
     "dmxBatchChunkCommit", "dmxBatchChunkRollback", "dmxBatchExactTick", "dmxBatchRefreshGhostsOnStream", "dmxBatchSetConvexHull", "dmxBatchChunkTicks", "dmxBatchSetTicksPerLaunch",
     "dmxBatchSetSnapshotMode", "dmxBatchSetStaticBoxes", "dmxBatchSetStepper", "dmxBatchSetConvexHullFaces",
-    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision",
+    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision", "dmxBatchSetLoadElision", "dmxBatchLoadElisionStats",
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles",
@@ -108,6 +108,8 @@ def load():
     sig("dmxBatchSetTicksPerLaunch", I, P, I)
     sig("dmxBatchSetSnapshotMode", I, P, I)
     sig("dmxBatchSetElision", I, P, I)
+    sig("dmxBatchSetLoadElision", I, P, I)
+    sig("dmxBatchLoadElisionStats", I, P, P)
     sig("dmxBatchSetExactPipeline", I, P, I)
     sig("dmxBatchSetStaticPath", I, P, I)
     sig("dmxBatchSetClassPairs", I, P, I, I, I)

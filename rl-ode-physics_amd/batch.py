@@ -342,6 +342,18 @@ class BatchWorld:
         kernel arguments.  Default 3; 0 = every load and store (include/dmx_batch.h).  Same results bit for bit."""
         _check(self.lib.dmxBatchSetElision(self.h, int(mask)), "dmxBatchSetElision")
 
+    def set_load_elision(self, on=True):
+        """contact-free launches leave out the loads of pos.x/z and lvel.x/z in tiles that have proven them fixed (default on; active
+        only while bit 0 of set_elision is on; include/dmx_batch.h).  Same results bit for bit."""
+        _check(self.lib.dmxBatchSetLoadElision(self.h, 1 if on else 0), "dmxBatchSetLoadElision")
+
+    def load_elision_stats(self):
+        """dict: establish / lean launches, chain breaks, ended for good, tiles with x / z fixed.  Settles the batch."""
+        out = (C.c_int64 * 6)()
+        _check(self.lib.dmxBatchLoadElisionStats(self.h, out), "dmxBatchLoadElisionStats")
+        keys = ("establish", "lean", "breaks", "ended", "tiles_x_fixed", "tiles_z_fixed")
+        return {k: int(v) for k, v in zip(keys, out)}
+
     def check_zones_on(self, stream_handle, first, count):
         _check(self.lib.dmxBatchCheckZonesOnStream(self.h, stream_handle, first, count), "dmxBatchCheckZonesOnStream")
 

@@ -88,6 +88,8 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
     {
         static const int elide_default = [] { const char *e = getenv("DMX_ELIDE"); return e ? atoi(e) & 3 : (DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS); }();
         b->elide = elide_default;
+        static const bool loads_default = [] { const char *e = getenv("DMX_ELIDE_LOADS"); return !(e && atoi(e) == 0); }();
+        b->fix.on = loads_default;
     }
     b->prof_on = getenv("DMX_HOST_PROFILE") != nullptr;
     {
@@ -115,6 +117,8 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
         if (hipMalloc(&b->slab_alt, (size_t)C_COUNT * b->stride * b->rsize) != hipSuccess) { rc = DMX_ENOMEM; break; }
         if (hipMalloc((void **)&b->gtype, (size_t)b->stride) != hipSuccess) { rc = DMX_ENOMEM; break; }
         if (hipMalloc((void **)&b->bflags, (size_t)b->stride) != hipSuccess) { rc = DMX_ENOMEM; break; }
+        if (hipMalloc((void **)&b->fix_words, (size_t)(b->stride / 64) * sizeof(uint32_t)) != hipSuccess) { rc = DMX_ENOMEM; break; }
+        if (hipMemset(b->fix_words, 0, (size_t)(b->stride / 64) * sizeof(uint32_t)) != hipSuccess) { rc = DMX_EHIP; break; }
         b->h_bflags.assign((size_t)b->stride, 0);
         for (int64_t i = 0; i < n; i++) b->h_bflags[(size_t)i] = BF_ALIVE;
         if (hipMemcpy(b->bflags, b->h_bflags.data(), (size_t)b->stride, hipMemcpyHostToDevice) != hipSuccess) { rc = DMX_EHIP; break; }
@@ -176,6 +180,7 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
     if (b->slab_alt) (void)hipFree(b->slab_alt);
     if (b->gtype) (void)hipFree(b->gtype);
     if (b->bflags) (void)hipFree(b->bflags);
+    if (b->fix_words) (void)hipFree(b->fix_words);
     for (dmxBatch::DevBuf *d : { &b->jd_int, &b->jd_real, &b->jd_rows, &b->jd_rowjb, &b->jd_bscr, &b->jd_local, &b->jd_order })
         if (d->p) (void)hipFree(d->p);
     for (dmxBatch::DevBuf *d : { &b->bp_count, &b->bp_items, &b->bp_flags, &b->bp_inpair, &b->bp_snapshot, &b->hull, &b->cbuf, &b->ccount,
@@ -379,6 +384,7 @@ extern "C" void *dmxBatchDevicePtr(dmxBatchID b, int field, int component)
     // ... and neither are the constants known to be uniform any more: whatever field was asked for, the address is one into
     // the slab, whose layout the header documents -- components 13..16 can be reached from it
     b->uni_mass.poison(); b->uni_inertia.poison();
+    b->fix.end();                 // ... nor can any tile's state be known to stay as a launch found it
     return (char *)b->slab + (size_t)slab_ix(k_field_comp0[field] + component, 0) * b->rsize;
 }
 
@@ -397,7 +403,8 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
         const bool ext = b->ext_pending && s == 0;
         P.ticks = ext ? 1 : std::min(per, nsteps - s);
         T *S = (T *)b->slab + slab_ix(0, first);
-        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev));
+        const int fix_mode = dmx_fix_next<T>(b, P, first, count, true, ext);
+        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev, fix_mode, b->fix_words));
         if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
         s += P.ticks;
     }
@@ -412,9 +419,9 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
     if (dmx_refuse_joints(b, "dmxBatchStep")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
-    dmx_state_written(b);
+    dmx_state_stepped(b);
     if (b->bp_enabled) return dmx_step_collide(b, h, nsteps);
-    SETTLE(b);
+    { const int rc_close = dmx_close_chunk(b); if (rc_close != DMX_OK) return rc_close; }
     int rc = b->precision == DMX_F32 ? step_t<float>(b, h, nsteps, 0, b->n_active, true)
                                      : step_t<double>(b, h, nsteps, 0, b->n_active, true);
     b->ext_pending = false;   // the step cleared the accumulators
@@ -476,6 +483,33 @@ extern "C" int dmxBatchSetElision(dmxBatchID b, int mask)
     if (!b || mask < 0 || mask > (DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS)) return DMX_EINVAL;
     SETTLE(b);
     b->elide = mask;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetLoadElision(dmxBatchID b, int on)
+{
+    if (!b || (on != 0 && on != 1)) return DMX_EINVAL;
+    SETTLE(b);
+    b->fix.set_on(on != 0);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchLoadElisionStats(dmxBatchID b, int64_t out[6])
+{
+    if (!b || !out) return DMX_EINVAL;
+    // the counts first: the settle below breaks the chain like every observer does, and that break is this call's, not the run's
+    out[0] = b->fix.n_establish; out[1] = b->fix.n_lean; out[2] = b->fix.n_breaks; out[3] = b->fix.ended ? 1 : 0;
+    out[4] = out[5] = 0;
+    SETTLE(b);
+    HIP_TRY(hipSetDevice(b->device));
+    // the words of the tiles with an active body, as the last establishing or lean launch left them: they say something only
+    // while the feature has run at all, and nothing about tiles no such launch has stepped
+    const size_t nt = (size_t)((b->n_active + 63) / 64);
+    if (b->fix.n_establish == 0 || nt == 0) return DMX_OK;
+    std::vector<uint32_t> w(nt);
+    HIP_TRY(hipMemcpyAsync(w.data(), b->fix_words, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (size_t t = 0; t < nt; t++) { out[4] += w[t] & 1u; out[5] += (w[t] >> 2) & 1u; }
     return DMX_OK;
 }
 
@@ -623,7 +657,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
     if (dmx_refuse_joints(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
-    dmx_state_written(b);
+    dmx_state_stepped(b);
     return dmx_chunk_tick(b, h, check);
 }
 extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_first, int check_last)
@@ -632,7 +666,7 @@ extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_
     if (dmx_refuse_joints(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
-    dmx_state_written(b);
+    dmx_state_stepped(b);
     return dmx_chunk_ticks(b, h, nticks, check_first, check_last);
 }
 extern "C" int dmxBatchSetTicksPerLaunch(dmxBatchID b, int ticks)

@@ -15,6 +15,7 @@
 #include "../../include/dmx_batch.h"
 #include "dmx_internal.hpp"
 #include "dmx_uniform.hpp"
+#include "dmx_fixed.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -103,6 +104,11 @@ struct dmxBatch {
     int elide = DMX_ELIDE_STORES | DMX_ELIDE_CONSTANTS;
     dmx::UniformTracker<1> uni_mass; dmx::UniformTracker<3> uni_inertia;
     bool capturing = false;          // the stream was being captured into a HIP graph at the last stepping call (dmx_note_capture)
+    // integrate_free's third removal (dmxBatchSetLoadElision; DMX_ELIDE_LOADS=0 in the environment switches it off): loads of
+    // pos.x/z and lvel.x/z in tiles that have proven them fixed.  fix_words: one word per 64-body tile, on the device, bits 0..2 =
+    // axis x, y, z fixed; `fix` says before each contact-free launch whether the words may be used (dmx_fixed.hpp has the rule).
+    dmx::FixedChain fix;
+    uint32_t *fix_words = nullptr;   // stride / 64 words
     bool stepped_with_plane = false;
     // general island path (explicit contact joints)
     uint8_t *bflags = nullptr;                 // device, per-slot BF_* flags
@@ -210,17 +216,27 @@ inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
 }
 // A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later
 // upload of another mass while eager ticks use the new one: launches recorded during a capture read the constants from the
-// slab.  Asked once per stepping call of the C ABI (the entry points that can reach integrate_free), and only while the
-// answer matters, not per tick: the exact ticks of small scenes are bound by host latency.
+// slab.  Asked once per stepping call of the C ABI (the entry points that can reach integrate_free), not per tick.
+// The fixed-axis words (dmx_fixed.hpp) cannot outlive a capture either: a replay steps the bodies behind the library's back, so a
+// stepping call made during a capture ends that feature for the batch, and the question is asked for as long as it has not ended --
+// also while it is switched off (dmxBatchSetLoadElision(0), DMX_ELIDE=0), since a graph recorded then is replayed all the same
+// after it has been switched on.  The cost: one hipStreamIsCapturing, a host-side query, on EVERY stepping call of every batch
+// that has not handed out a device pointer or been captured -- no longer only while the constants are uniform.  The exact ticks
+// of small scenes, which are bound by host latency, measure what they did (configs[0] and the pen in profiles/ab_loads.txt).
 inline void dmx_note_capture(dmxBatch *b)
 {
     b->capturing = false;
-    if (!(b->elide & DMX_ELIDE_CONSTANTS) || !b->uni_mass.uniform || !b->uni_inertia.uniform) return;
+    const bool uni = (b->elide & DMX_ELIDE_CONSTANTS) && b->uni_mass.uniform && b->uni_inertia.uniform;
+    if (!uni && b->fix.ended) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     b->capturing = hipStreamIsCapturing(b->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (b->capturing) b->fix.end();
 }
-// called by everything that changes body state in the slab other than the single-launch tick
-inline void dmx_state_written(dmxBatch *b) { b->sm_mirror_valid = false; b->state_version++; }
+// a stepping call of the C ABI is about to advance the bodies: what dmx_state_written does, but the fixed-axis chain stands --
+// the launches themselves tell the record what they are (dmx_fix_next)
+inline void dmx_state_stepped(dmxBatch *b) { b->sm_mirror_valid = false; b->state_version++; }
+// called by everything else that changes body state in the slab other than the single-launch tick
+inline void dmx_state_written(dmxBatch *b) { dmx_state_stepped(b); b->fix.brk(); }
 
 int dmx_ensure_dev(dmxBatch::DevBuf &d, size_t bytes);
 // do the fused kernels make contacts (and so leave contact diagnostics behind)?  The ground plane, or static boxes on the fused path
@@ -259,6 +275,9 @@ int dmx_step_collide(dmxBatch *b, double h, int nsteps);
 // close the chunk dmxBatchStep may have left open (flag read; rollback + replay on a violation).  Every entry point that
 // observes or changes the batch calls this first.
 int dmx_settle(dmxBatch *b);
+// the same without breaking the fixed-axis chain (dmx_fixed.hpp): for dmxBatchStep alone, whose calls follow one another in the
+// reference's loop with nothing between them; a rollback found at the close breaks the chain itself
+int dmx_close_chunk(dmxBatch *b);
 // the collision-checked loop in pieces (dmx_general.cpp)
 int dmx_chunk_begin(dmxBatch *b, int *exact_only, int *ballistic);
 int dmx_chunk_tick(dmxBatch *b, double h, int check);
@@ -322,3 +341,21 @@ template <class T> inline StepParams<T> dmx_make_params(dmxBatch *b, double h)
     return P;
 }
 
+// What is the contact-free launch of `count` bodies from slot `first` about to be enqueued with these parameters, for the
+// fixed-axis words: FIX_OFF, FIX_ESTABLISH or FIX_LEAN?  Asked exactly once per launch_step call that is not handed FIX_OFF
+// blindly; the record (dmx_fixed.hpp) takes the answer as given.
+template <class T> inline int dmx_fix_next(dmxBatch *b, const StepParams<T> &P, int64_t first, int64_t count, bool in_place, bool ext)
+{
+    if (!step_is_contact_free(P)) { b->fix.brk(); return FIX_OFF; }
+    FixedLaunch L;
+    L.eligible = P.ticks == 1 && !ext && (P.elide & DMX_ELIDE_STORES) != 0 && !b->capturing && !b->slab_exposed && b->fix_words != nullptr;
+    L.whole = first == 0 && count == b->n_active && P.skip == nullptr && P.gate == nullptr;
+    L.in_place = in_place; L.bp_check = P.bp_check != 0; L.pack = P.pack_out != nullptr;
+    L.key.h = FixedKey::bits(P.h);
+    L.key.g[0] = FixedKey::bits(P.g.x); L.key.g[1] = FixedKey::bits(P.g.y); L.key.g[2] = FixedKey::bits(P.g.z);
+    L.key.mass_uniform = (P.uni && (P.elide & DMX_ELIDE_CONSTANTS)) ? 1 : 0;
+    L.key.mass = L.key.mass_uniform ? FixedKey::bits(P.uni_mass) : 0;
+    L.key.gyro = P.gyro; L.key.elide = P.elide;
+    L.key.n_active = b->n_active;
+    return b->fix.next(L);
+}

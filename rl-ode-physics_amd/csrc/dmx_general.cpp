@@ -191,6 +191,7 @@ template <class T> int snapshot_restore(dmxBatch *b)
         HIP_TRY(launch_copy_state<T>((T *)b->slab, (T *)b->bp_snapshot.p, b->stride, false, b->stream));
     else if (b->snap_kind == SNAP_PINGPONG)
         std::swap(b->slab, b->slab_alt);        // the untouched start state (ghost slots included) is current again
+    b->fix.brk();                               // the fixed-axis words describe the state that has just been thrown away
     b->flip_armed = false; b->flipped = false;
     b->snap_kind = SNAP_NONE;
     b->bp_fresh = b->snap_fresh;
@@ -213,7 +214,8 @@ template <class T> int launch_fast(dmxBatch *b, const StepParams<T> &P, bool ext
             So = (T *)b->slab_alt;
         }
     }
-    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream, b->sweep_rev));
+    const int fix_mode = dmx_fix_next<T>(b, P, 0, b->n_active, So == S, ext);
+    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream, b->sweep_rev, fix_mode, b->fix_words));
     if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
     b->bp_fresh = false;                     // the poses have moved on from the ones the zones were built at
     if (So != S) {
@@ -462,6 +464,7 @@ template <class T> int careful_tick(dmxBatch *b, double h)
 {
     int rc;
     snapshot_drop(b);           // exact ticks run in place and are never rolled back
+    b->fix.brk();               // ... and step bodies through kernels that know nothing of the fixed-axis words
     std::unique_ptr<DmxPhase> ph(new DmxPhase(b, 0));
     if (!b->ex_counts_host && (rc = alloc_host_record(&b->ex_counts_host, sizeof(ExactCounts))) != DMX_OK) return rc;
     const StepParams<T> P = dmx_make_params<T>(b, h);
@@ -1025,6 +1028,12 @@ int dmx_find_pairs(dmxBatch *b)
 }
 
 int dmx_settle(dmxBatch *b)
+{
+    b->fix.brk();       // whoever settles is about to observe or change the batch (dmx_fixed.hpp)
+    return dmx_close_chunk(b);
+}
+
+int dmx_close_chunk(dmxBatch *b)
 {
     if (!b->oc.open) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));

@@ -224,9 +224,11 @@ struct StepDiag {
 // behind untouched: the zero-cost snapshot of a collision-proof chunk (dmx_general.cpp).
 // rev: the direction in which a contact-free launch (integrate_free) walks the tiles (dmx_sweep.hpp; dmx_next_sweep in
 // dmx_batch_priv.hpp hands out alternating ones); the kernels of ticks with contacts take no notice of it.
+// fix_mode / fix_words: what dmx_fixed.hpp's record said about a contact-free launch (FIX_OFF = 0: the launch it always was),
+// and the batch's word per tile; a launch that does not reach integrate_free must come with FIX_OFF.
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st, int rev);
+                       StepDiag *diag, hipStream_t st, int rev, int fix_mode = 0, uint32_t *fix_words = nullptr);
 // does launch_step take these parameters to integrate_free (no plane, no static geometry with contact slots)?
 template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
 {

@@ -647,6 +647,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
 int dmx_step_joints(dmxBatch *b, double h, int64_t n_joints, const dmxContactJoint *joints, const uint8_t *include,
                     const DevGeometry *geo)
 {
+    b->fix.brk();       // the joints tick, single-launch or not, steps bodies behind the fixed-axis words' back (dmx_fixed.hpp)
     return b->precision == DMX_F32 ? step_joints_t<float>(b, h, n_joints, joints, include, geo)
                                    : step_joints_t<double>(b, h, n_joints, joints, include, geo);
 }

@@ -22,6 +22,7 @@
 #include "dmx_collide.hpp"
 #include "dmx_step_fused.hpp"
 #include "dmx_sweep.hpp"
+#include "dmx_fixed.hpp"
 
 namespace dmx {
 
@@ -39,6 +40,16 @@ namespace dmx {
 // A dropped scene of unit-mass bodies under gravity along y (the reference's AddBody + dWorldSetGravity) then moves
 // 13 reals in and 6 out (pos.y, quat, lvel.y) = 19 per body-step; any other scene moves what it changes, up to the 30.
 // Same values into the same free_body_step either way: same bits.
+//   FIX        (a template parameter of its own, not a bit of OPT: dmxBatchSetElision keeps its two) the one-tick kernels with
+//              store elision also exist with the fixed-axis mode built in, for launches over the whole active slab that
+//              dmx_fixed.hpp's record has called establishing or lean (fix_mode, a scalar argument of its own like `rev`).  A word
+//              per 64-body tile (fix_words) says in bits 0..2 that a launch loaded pos.k and lvel.k of the tile's active lanes, ran
+//              the tick and found both unchanged in every lane's bits -- the very ballots of the store elision.  The tick computes
+//              them from themselves, h, g.k and the mass alone, so they stay for as long as the record's chain is unbroken.  An
+//              establishing launch loads all 13 and writes every tile's word; a lean one reads the word, issues neither the two
+//              loads nor the ballots and stores of a fixed lateral axis (x, z), tests a clear axis as an establishing launch does
+//              and rewrites a word that changes (-0.0 -> +0.0 clears the bit in the tick where it happens).  The dropped scene
+//              then moves 9 reals in and 6 out = 15 per body-step.  Every other launch is the kernel without FIX, as it always was.
 // Sweep order (dmx_sweep.hpp): `rev` -- a scalar argument of its own, StepParams does not grow -- says in which direction this
 // launch walks the tiles; workgroup b works on tile group sweep_block(b, gridDim.x, rev).  The callers alternate it from one
 // contact-free launch to the next, so that the lines the last launch touched last, still in the XCDs' L2s, are read first.  The
@@ -56,10 +67,15 @@ template <class T> __device__ __forceinline__ bool bits_differ(T a, T b)
     return __builtin_bit_cast(U, a) != __builtin_bit_cast(U, b);
 }
 
-template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0>
-__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P, int rev)
+// the tile's axis (x, y, z = 0, 1, 2) a state component belongs to for the fixed-axis words: pos and lvel; -1 for quat and avel
+__host__ __device__ constexpr int fix_axis_of(int k) { return k < C_QUAT ? k - C_POS : (k >= C_LVEL && k < C_AVEL) ? k - C_LVEL : -1; }
+
+template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0, bool FIX = false>
+__global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P, int rev, int fix_mode,
+                                                            uint32_t *fix_words)
 {
     constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
+    static_assert(!FIX || (ELIDE && !EXT && !MULTI), "the fixed-axis mode is built into the one-tick kernels with store elision only");
     constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
     // So = where the new state goes: S itself (in place) or the batch's other slab (the first launch of a
     // collision-proof chunk, which thereby leaves the chunk's start state behind as the rollback snapshot)
@@ -70,8 +86,27 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
          i += (int64_t)gridDim.x * blockDim.x) {
         if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
         T c[NLOAD];
+        uint32_t fixed = 0, seen = 0;       // FIX, lean launches: the tile's word as read, and its lateral axes (wave-uniform)
+        if constexpr (FIX) {
+            // The tile's word first, then the loads every tile needs (pos.y, quat, lvel.y, avel and the constants): they are in flight
+            // before anything waits on the word.  Only then the lateral loads, one scalar branch per axis around both of its loads.
+            // The y axis is among the loads issued ahead of the word, so a fixed y saves nothing and bit 1 is kept for the record.
+            uint32_t word = 0;
+            if (fix_mode == FIX_LEAN) word = fix_words[__builtin_amdgcn_readfirstlane((int)(i >> 6))];
 #pragma unroll
-        for (int k = 0; k < NLOAD; k++) c[k] = S[slab_ix(k, i)];
+            for (int k = 0; k < NLOAD; k++)
+                if (k >= C_MASS || fix_axis_of(k) < 0 || fix_axis_of(k) == 1) c[k] = S[slab_ix(k, i)];
+            seen = __builtin_amdgcn_readfirstlane(word);
+            fixed = seen & 5u;
+#pragma unroll
+            for (int ax = 0; ax < 3; ax += 2) {
+                if (fixed & (1u << ax)) { c[C_POS + ax] = T(0); c[C_LVEL + ax] = T(0); }     // never looked at: see the stores
+                else { c[C_POS + ax] = S[slab_ix(C_POS + ax, i)]; c[C_LVEL + ax] = S[slab_ix(C_LVEL + ax, i)]; }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NLOAD; k++) c[k] = S[slab_ix(k, i)];
+        }
         T was[ELIDE ? C_MASS : 1];          // the state as loaded, to tell which components the launch changed
         if constexpr (ELIDE) {
 #pragma unroll
@@ -116,12 +151,31 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
             c[C_LVEL] = v.x; c[C_LVEL + 1] = v.y; c[C_LVEL + 2] = v.z;
             c[C_AVEL] = w.x; c[C_AVEL + 1] = w.y; c[C_AVEL + 2] = w.z;
         }
+        if constexpr (FIX) {
+            uint32_t moved = 0;             // axes on which some lane's pos or lvel changed its bits in this tick
+#pragma unroll
+            for (int k = 0; k < C_MASS; k++) {
+                const int ax = fix_axis_of(k);
+                if (ax >= 0 && (fixed & (1u << ax))) continue;      // proven fixed and not loaded: nothing to test, nothing to write
+                if (in_place || ax >= 0) {
+                    const bool changed = __ballot(bits_differ(c[k], was[k])) != 0ull;
+                    if (ax >= 0 && changed) moved |= 1u << ax;
+                    if (in_place && !changed) continue;
+                }
+                So[slab_ix(k, i)] = c[k];
+            }
+            // what this launch observed: an establishing launch writes every tile's word, a lean one only a word that changes
+            // (an axis it did not load keeps its bit: same inputs, same bits)
+            const uint32_t word = ~moved & 7u;
+            if ((fix_mode != FIX_LEAN || word != seen) && (threadIdx.x & 63) == 0) fix_words[i >> 6] = word;
+        } else {
 #pragma unroll
         for (int k = 0; k < C_MASS; k++) {
             if constexpr (ELIDE) if (in_place) {
                 if (__ballot(bits_differ(c[k], was[k])) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
             }
             So[slab_ix(k, i)] = c[k];
+        }
         }
         if (EXT) {
 #pragma unroll
@@ -503,7 +557,7 @@ constexpr int64_t kOneLaunchBodies = 256 * 4 * 64;
 
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st, int rev)
+                       StepDiag *diag, hipStream_t st, int rev, int fix_mode, uint32_t *fix_words)
 {
     if (P.n_static > 0 && P.sbuf != nullptr) {
         // bodies at static geometry: narrowphase against the plane and the static boxes, then the fused solve + integrate
@@ -543,8 +597,16 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
         constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
         const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0);
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1); };
-        if (P.ticks > 1) {
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1, fix_mode, fix_words); };
+        // an establishing or lean launch (dmx_fixed.hpp; the caller has asked the batch's record) is one of the two instantiations
+        // with the fixed-axis mode built in; every other launch is the kernel it always was
+        if (fix_mode != FIX_OFF) {
+            if (P.ticks > 1 || ext || !(opt & OPT_ELIDE) || fix_words == nullptr || P.skip != nullptr || P.gate != nullptr) return hipErrorInvalidValue;
+            // a lean launch has not loaded every pos.x / pos.z: it cannot fill another slab, test safe zones or pack the boundary
+            if (fix_mode == FIX_LEAN && (So != S || P.bp_check != 0 || P.pack_out != nullptr)) return hipErrorInvalidValue;
+            if (opt == 3) launch(integrate_free<T, false, MWU, false, 3, true>);
+            else launch(integrate_free<T, false, 1, false, 1, true>);
+        } else if (P.ticks > 1) {
             if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
             else launch(integrate_free<T, false, 1, true, 0>);
         } else if (ext) {
@@ -656,7 +718,7 @@ hipError_t launch_soa_to_aos(const T *S, int64_t stride, int comp0, int k, int64
 
 #define DMX_INSTANTIATE(T)                                                                                         \
     template hipError_t launch_step<T>(T *, T *, const uint8_t *, int64_t, int64_t, const StepParams<T> &, bool,   \
-                                       StepDiag *, hipStream_t, int);                                              \
+                                       StepDiag *, hipStream_t, int, int, uint32_t *);                                            \
     template hipError_t launch_pack_transforms<T>(const T *, int64_t, int64_t, int64_t, T *, hipStream_t);         \
     template hipError_t launch_gather<T>(const T *, int64_t, const int32_t *, int64_t, T *, hipStream_t);          \
     template hipError_t launch_scatter<T>(T *, int64_t, const int32_t *, int64_t, const T *, hipStream_t);         \
@@ -683,6 +745,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
     if (real_bytes == 4) {
         touch((const void *)&integrate_free<float, false, 1, false>);
         touch((const void *)&integrate_free<float, false, 7, false, 3>);
+        touch((const void *)&integrate_free<float, false, 7, false, 3, true>);
         touch((const void *)&step_plane<float, false, 2, 4>);
         touch((const void *)&step_contacts<float, false, 1, 8, true>);
         touch((const void *)&check_zones<float>);
@@ -690,6 +753,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
     } else {
         touch((const void *)&integrate_free<double, false, 1, false>);
         touch((const void *)&integrate_free<double, false, 1, false, 3>);
+        touch((const void *)&integrate_free<double, false, 1, false, 3, true>);
         touch((const void *)&step_plane<double, false, 1, 4>);
         touch((const void *)&step_contacts<double, false, 1, 8, true>);
         touch((const void *)&check_zones<double>);
