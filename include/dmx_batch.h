@@ -367,7 +367,7 @@ int dmxBatchSmallTickStats(dmxBatchID b, int64_t out[DMX_SMALL_TICK_NSTATS]);
 enum { DMX_ORDER_CREATION = 0, DMX_ORDER_ODE = 1 };
 int dmxBatchSetRowOrder(dmxBatchID b, int order, uint32_t seed);
 
-/* ---- articulation joints: ball-and-socket and hinge (dJointCreateBall / dJointCreateHinge).  Unlike contact joints, which
+/* ---- articulation joints: ball-and-socket and hinge (dJointCreateBall / dJointCreateHinge); slider and fixed: further below.  Unlike contact joints, which
  * live for one tick, the set given to dmxBatchSetJoints persists until it is replaced and takes part in every
  * dmxBatchStepJoints tick -- both steppers, both precisions, the general path and the single-launch tick of small worlds.
  * Anchors and axes are stored in the frames of the two bodies (world frame for a side that is -1, the world).
@@ -386,7 +386,7 @@ int dmxBatchSetRowOrder(dmxBatchID b, int order, uint32_t seed);
  * dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick(s), dmxBatchExactTick -- and QuickStep's dmxBatchStepJoints under DMX_ORDER_ODE
  * return DMX_EINVAL with one line on stderr: nothing is silently ignored.  (Under DMX_STEPPER_EXACT the row order is never used, so
  * there is nothing to refuse.)  Everything else is unaffected; dmxBatchLastContactCount goes on counting contact joints only. */
-enum { DMX_JOINT_BALL = 1, DMX_JOINT_HINGE = 2 };
+enum { DMX_JOINT_BALL = 1, DMX_JOINT_HINGE = 2, DMX_JOINT_SLIDER = 3, DMX_JOINT_FIXED = 4 };
 typedef struct dmxJoint {
     int32_t kind, body1, body2, reserved;     /* slots; -1 = the world */
     double anchor1[3], anchor2[3];            /* in the frame of body1 / body2; world frame for a side that is -1 */
@@ -395,11 +395,13 @@ typedef struct dmxJoint {
 int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints);   /* copied; replaces the set; n = 0 removes it */
 int64_t dmxBatchJointCount(dmxBatchID b);
 /* a joint from world-frame anchor / axis at the bodies' CURRENT poses (what dJointSetHingeAnchor / Axis mean); axis_w may be
- * NULL for a ball */
+ * NULL for a ball and for a fixed joint.  A slider takes an anchor (any point of its line) and a non-zero axis. */
 int dmxBatchJointFromWorld(dmxBatchID b, int kind, int32_t body1, int32_t body2, const double anchor_w[3], const double axis_w[3],
                            dmxJoint *out);
 /* per joint of the set |p2 - p1| (the anchors' separation) and, for hinges, |u x w| (0 for balls), from the current state,
- * computed on the device (inactive joints report 0); either array may be NULL; out_max[2] = the two maxima (may be NULL) */
+ * computed on the device (inactive joints report 0); either array may be NULL; out_max[2] = the two maxima (may be NULL).
+ * A slider: pos_err = the length of the part of p_2 - p_1 across u, axis_err = |2 e_v|; a fixed joint: |p_2 - p_1| and |2 e_v|
+ * (e as defined at DMX_JOINT_SLIDER below, with the joint's q_0). */
 int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_err, double out_max[2]);
 
 /* ---- a hinge's limits, motor and angle (dJointSetHingeParam: dParamLoStop / HiStop / Vel / FMax; dJointGetHingeAngle / Rate).
@@ -426,7 +428,8 @@ int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_err, double 
  *           anywhere stages and launches exactly what it does without limots.
  * Without limots a hinge's q_0 is the identity: dmxBatchHingeAngles then reports the angle relative to the two frames coinciding. */
 typedef struct dmxHingeLimot { double lo_stop, hi_stop, vel, fmax; double qrel0[4]; } dmxHingeLimot;
-/* one entry per joint of the current set (entries of ball joints are ignored); n must equal dmxBatchJointCount or be 0 (removes them);
+/* one entry per joint of the current set, whatever its kind (entries of ball joints are ignored; a slider's or a fixed joint's
+ * gives its zero pose, a slider's also its stops and motor); n must equal dmxBatchJointCount or be 0 (removes them);
  * copied; may be replaced every tick (a controller setting vel / fmax).  dmxBatchSetJoints drops the limots.  DMX_EINVAL: another n,
  * a non-finite vel or fmax, a NaN stop. */
 int dmxBatchSetHingeLimots(dmxBatchID b, int64_t n, const dmxHingeLimot *limots);
@@ -435,6 +438,30 @@ int dmxBatchHingeLimotInit(dmxBatchID b, const dmxJoint *joint, dmxHingeLimot *o
 /* theta and theta_dot per joint of the set, from the current state, computed on the device in the batch's precision (balls and
  * inactive joints report 0); either array may be NULL */
 int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate);
+
+/* ---- slider and fixed joints (dJointCreateSlider / dJointCreateFixed): DMX_JOINT_SLIDER, DMX_JOINT_FIXED in dmxBatchSetJoints.
+ * Everything follows the conventions above: canonical sides (body1 = -1 with a live body2 exchanges the sides, anchors and axes
+ * included), the activity rules, k = ERP / h, cfm = the world's, a_i = R_i anchor_i, p_i = x_i + a_i; a world side has p = anchor,
+ * a = 0 and no Jacobian block.
+ *   zero pose    q_0 is the qrel0 of the joint's entry in dmxBatchSetHingeLimots, which takes one entry per joint of the set whatever
+ *                its kind (only a ball's entry is ignored); the identity when no limots are set, as for a hinge.
+ *                dmxBatchHingeLimotInit serves any kind.  In canonical sides q_0c = q_0, or conj(q_0) after an exchange of sides.
+ *   angular lock (three rows; slider and fixed)  e = conj(q_1) q_2 conj(q_0c), negated when e_w < 0; Phi = R_1 (2 e_v); for
+ *                d = e_x, e_y, e_z:  J = [ 0, d | 0, -d ],  c = k Phi . d;  unbounded.  (To first order the hinge unit's c = k (u x w) . r.)
+ *   slider's linear unit (two rows)  u = R_1 axis1, (p, q) = dPlaneSpace(u); for r = p, q:
+ *                J = [ r, (p_2 - x_1) x r | -r, -(a_2 x r) ],  c = k (p_2 - p_1) . r;  unbounded.  The ball's row with body 1's arm taken
+ *                to body 2's anchor point: the exact derivative of (p_2 - p_1) . r when r turns with body 1.
+ *   position     in the sides AS GIVEN, as a hinge's angle:  s = u . (p_1 - p_2), u = R_1 axis1 of the given side 1 (a world side 1: its
+ *                axis as given);  s_dot = [ u, (p_2 - x_1) x u | -u, -(a_2 x u) ] . (v_1, w_1, v_2, w_2), the exact derivative of s.
+ *                When the given side 1 is the world the row in canonical form is [ -u, -(a x u) | 0 ], a = the body's arm.
+ *   slider limot one row behind the slider's five, PRESENT by the hinge's rule (fmax > 0 or a finite stop); its Jacobian is the one
+ *                s_dot is written with; c, lo, hi from the hinge's five-line table with s for theta: stops in metres, vel in m/s,
+ *                fmax in N.  The inside-range line keeps the row (c = lo = hi = 0): the row count depends on parameters alone.
+ *   row order    slider: lock (3), linear (2), limot (1 if present).  fixed: ball unit (3, the anchors as given), lock (3).
+ * A set without sliders and fixed joints stages and launches exactly what it did before these kinds existed. */
+/* s and s_dot per joint of the set, from the current state, computed on the device in the batch's precision (other kinds and
+ * inactive joints report 0); either array may be NULL */
+int dmxBatchSliderPositions(dmxBatchID b, double *pos, double *rate);
 
 /* per-body flags for the island path: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes */
 enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };

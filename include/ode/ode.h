@@ -190,7 +190,7 @@ void dJointGroupDestroy(dJointGroupID);                          /* main.c:265 *
 dJointID dJointCreateContact(dWorldID, dJointGroupID, const dContact *);   /* main.c:690 */
 void dJointAttach(dJointID, dBodyID body1, dBodyID body2);       /* main.c:691 */
 
-/* ---- articulation joints: ball-and-socket and hinge [ODE-recall objects.h].  Anchors and axes are given in world
+/* ---- articulation joints: ball-and-socket, hinge, slider and fixed [ODE-recall objects.h].  Anchors and axes are given in world
  * coordinates after dJointAttach and kept in the bodies' frames at their poses of that moment; a body of 0 is the world.
  * dJointAttach(j, 0, body) exchanges the two, as ODE does: dJointGetBody(j, 0) is the body.  dWorldDestroy destroys the joints that
  * are in no group.  dBodyDestroy detaches the body's joints (both sides: the joint does nothing until it is attached again).
@@ -200,9 +200,11 @@ void dJointAttach(dJointID, dBodyID body1, dBodyID body2);       /* main.c:691 *
  * parameters print one line to stderr and are ignored on set, and read as 0.  dJointSetHingeAnchor / dJointSetHingeAxis take the
  * bodies' current relative pose as angle zero, as ODE does.  Angle, rate, stops, motor and dJointAddHingeTorque are those of the
  * sides as attached: body 1 relative to body 2 about the axis, also after dJointAttach(j, 0, body).  Balls have none of these. */
-enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeContact = 4 };
+enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeSlider = 3, dJointTypeContact = 4, dJointTypeFixed = 7 };
 dJointID dJointCreateBall(dWorldID, dJointGroupID);
 dJointID dJointCreateHinge(dWorldID, dJointGroupID);
+dJointID dJointCreateSlider(dWorldID, dJointGroupID);
+dJointID dJointCreateFixed(dWorldID, dJointGroupID);
 void dJointDestroy(dJointID);
 int dJointGetType(dJointID);
 dBodyID dJointGetBody(dJointID, int index);
@@ -222,6 +224,21 @@ dReal dJointGetHingeParam(dJointID, int parameter);
 dReal dJointGetHingeAngle(dJointID);
 dReal dJointGetHingeAngleRate(dJointID);
 void dJointAddHingeTorque(dJointID, dReal torque);
+/* Sliders and fixed joints (include/dmx_batch.h, DMX_JOINT_SLIDER / DMX_JOINT_FIXED).  dJointSetSliderAxis takes the axis in world
+ * coordinates, puts the anchor at body 1's centre (body 2's when body 1 is the world) and takes the current pose as the zero pose and
+ * as position zero.  Position, rate, stops (metres), motor (m/s, N) and dJointAddSliderForce are those of the sides as attached:
+ * the position grows when body 1 moves along the axis relative to body 2.  dJointSetSliderParam honours the four parameters
+ * dJointSetHingeParam honours; the others print the same line and are ignored.  dJointAddSliderForce applies +f u to body 1 and -f u
+ * to body 2, both at body 2's anchor point: the pair's momentum and angular momentum do not change.  dJointSetFixed welds the two
+ * bodies at their current relative pose, the anchor at body 2's centre. */
+void dJointSetSliderAxis(dJointID, dReal x, dReal y, dReal z);
+void dJointGetSliderAxis(dJointID, dVector3 result);
+dReal dJointGetSliderPosition(dJointID);
+dReal dJointGetSliderPositionRate(dJointID);
+void dJointSetSliderParam(dJointID, int parameter, dReal value);
+dReal dJointGetSliderParam(dJointID, int parameter);
+void dJointAddSliderForce(dJointID, dReal force);
+void dJointSetFixed(dJointID);
 int dAreConnected(dBodyID, dBodyID);
 int dAreConnectedExcluding(dBodyID body1, dBodyID body2, int joint_type);
 

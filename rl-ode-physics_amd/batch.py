@@ -30,14 +30,16 @@ CONTACT_JOINT_DTYPE = np.dtype({
                 np.float64, np.float64, np.float64],
     "offsets": [0, 24, 48, 56, 60, 64, 72, 80, 88, 96, 104],
     "itemsize": 112})
-# dmxJoint (include/dmx_batch.h): an articulation joint -- a ball or a hinge -- of the persistent set (set_joints)
-JOINT_BALL, JOINT_HINGE = 1, 2
+# dmxJoint (include/dmx_batch.h): an articulation joint -- a ball, a hinge, a slider or a fixed joint -- of the persistent set
+# (set_joints)
+JOINT_BALL, JOINT_HINGE, JOINT_SLIDER, JOINT_FIXED = 1, 2, 3, 4
 JOINT_DTYPE = np.dtype({
     "names": ["kind", "body1", "body2", "reserved", "anchor1", "anchor2", "axis1", "axis2"],
     "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 3), (np.float64, 3), (np.float64, 3), (np.float64, 3)],
     "offsets": [0, 4, 8, 12, 16, 40, 64, 88],
     "itemsize": 112})
-# dmxHingeLimot (include/dmx_batch.h): a hinge's stops, motor and zero pose -- one entry per joint of the set (set_hinge_limots)
+# dmxHingeLimot (include/dmx_batch.h): a hinge's or a slider's stops, motor and zero pose (a fixed joint's zero pose) -- one entry per
+# joint of the set (set_hinge_limots)
 HINGE_LIMOT_DTYPE = np.dtype({
     "names": ["lo_stop", "hi_stop", "vel", "fmax", "qrel0"],
     "formats": [np.float64, np.float64, np.float64, np.float64, (np.float64, 4)],
@@ -213,7 +215,8 @@ class BatchWorld:
         _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
                "dmxBatchStepJoints")
 
-    # -- articulation joints: ball and hinge (dJointCreateBall / dJointCreateHinge), a set that persists between ticks --
+    # -- articulation joints: ball, hinge, slider and fixed (dJointCreateBall / Hinge / Slider / Fixed), a set that persists
+    #    between ticks --
     def set_joints(self, arr):
         """replace the set of articulation joints (an array of JOINT_DTYPE; empty or None removes it); every later
         step_joints tick honours them, ahead of the tick's contact joints"""
@@ -224,7 +227,8 @@ class BatchWorld:
         return int(self.lib.dmxBatchJointCount(self.h))
 
     def joint_from_world(self, kind, body1, body2, anchor, axis=None):
-        """a JOINT_DTYPE record from a world-frame anchor (and axis, for a hinge) at the bodies' current poses; -1 = the world"""
+        """a JOINT_DTYPE record from a world-frame anchor (and axis, for a hinge or a slider: a slider's anchor is any point of
+        its line) at the bodies' current poses; -1 = the world"""
         out = np.zeros(1, JOINT_DTYPE)
         a = np.ascontiguousarray(anchor, np.float64).reshape(3)
         x = None if axis is None else np.ascontiguousarray(axis, np.float64).reshape(3)
@@ -234,7 +238,8 @@ class BatchWorld:
 
     def joint_errors(self):
         """-> (pos_err [n], axis_err [n], (max pos_err, max axis_err)) of the set at the current state: the anchors' separation
-        and, for hinges, |u x w|, computed on the device"""
+        and, for hinges, |u x w|, computed on the device.  A slider: the separation across its axis and |2 e_v|, the rotation
+        away from its zero pose; a fixed joint: the separation and |2 e_v|"""
         n = self.joint_count()
         pe, ae, mx = np.zeros(n), np.zeros(n), np.zeros(2)
         _check(self.lib.dmxBatchJointErrors(self.h, pe.ctypes.data if n else None, ae.ctypes.data if n else None, mx.ctypes.data),
@@ -243,8 +248,9 @@ class BatchWorld:
 
     # -- the hinges' limits, motors and angles (dJointSetHingeParam, dJointGetHingeAngle / Rate) --
     def set_hinge_limots(self, arr):
-        """the hinges' stops and motors: an array of HINGE_LIMOT_DTYPE, one entry per joint of the set (a ball's is ignored);
-        empty or None removes them.  May be replaced every tick; set_joints drops them"""
+        """the hinges' and sliders' stops and motors (a slider's in metres, m/s and N) and the zero poses of hinges, sliders and
+        fixed joints: an array of HINGE_LIMOT_DTYPE, one entry per joint of the set (a ball's is ignored); empty or None removes
+        them.  May be replaced every tick; set_joints drops them"""
         l = np.zeros(0, HINGE_LIMOT_DTYPE) if arr is None else np.ascontiguousarray(np.asarray(arr).astype(HINGE_LIMOT_DTYPE, copy=False)).reshape(-1)
         _check(self.lib.dmxBatchSetHingeLimots(self.h, l.shape[0], l.ctypes.data if l.shape[0] else None), "dmxBatchSetHingeLimots")
 
@@ -262,6 +268,14 @@ class BatchWorld:
         th, rate = np.zeros(n), np.zeros(n)
         _check(self.lib.dmxBatchHingeAngles(self.h, th.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchHingeAngles")
         return th, rate
+
+    def slider_positions(self):
+        """-> (s [n], s_dot [n]) of the set's joints at the current state, computed on the device (other kinds and inactive
+        joints: 0): the position of side 1 against side 2 along the axis, zero where the two anchors meet"""
+        n = self.joint_count()
+        s, rate = np.zeros(n), np.zeros(n)
+        _check(self.lib.dmxBatchSliderPositions(self.h, s.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchSliderPositions")
+        return s, rate
 
     def set_stepper(self, stepper):
         """STEPPER_QUICK (dWorldQuickStep, default) / STEPPER_EXACT (dWorldStep) for step_joints"""

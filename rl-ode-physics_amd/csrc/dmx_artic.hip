@@ -1,7 +1,8 @@
 // dmx_artic.hip -- the articulation joints' entry points of the batch C ABI (include/dmx_batch.h): the persistent set
 // (dmxBatchSetJoints), a joint from world-frame anchor and axis at the bodies' current poses (dmxBatchJointFromWorld), and the
 // joints' position / axis errors from the current state, computed on the device (dmxBatchJointErrors); the hinges' limits and
-// motors (dmxBatchSetHingeLimots, dmxBatchHingeLimotInit) and their angles and rates, computed on the device (dmxBatchHingeAngles).
+// motors (dmxBatchSetHingeLimots, dmxBatchHingeLimotInit) and their angles and rates, computed on the device (dmxBatchHingeAngles),
+// and the sliders' positions and rates (dmxBatchSliderPositions).
 // The rows themselves are built by joint_unit_rows (dmx_island_rows.hpp) inside the island kernels; the host side of a tick is in
 // dmx_joints.cpp.
 #include <hip/hip_runtime.h>
@@ -14,12 +15,13 @@
 namespace dmx {
 
 // One lane per joint: |p2 - p1| with p_i = x_i + R_i anchor_i (a world side: its anchor), and for hinges |u x w| with
-// u = R_1 axis1, w = R_2 axis2 -- the quantities the rows' right-hand sides pull to zero, in the batch's precision.  The two
+// u = R_1 axis1, w = R_2 axis2; for a slider the part of p2 - p1 across its axis, and for sliders and fixed joints |2 e_v|, e = conj(q_1)
+// q_2 conj(q_0) (limots null: q_0 the identity) -- the quantities the rows' right-hand sides pull to zero, in the batch's precision.  The two
 // maxima: a wave reduction, then one atomic per wavefront on the values' bit patterns (non-negative doubles order like their bits).
 template <class T>
 __global__ __launch_bounds__(256) void joint_errors(const T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, int64_t n_slots,
-                                                    const dmxJoint *__restrict__ joints, int64_t nj, double *__restrict__ pos_err,
-                                                    double *__restrict__ axis_err, unsigned long long *__restrict__ maxima)
+                                                    const dmxJoint *__restrict__ joints, const dmxHingeLimot *__restrict__ limots, int64_t nj,
+                                                    double *__restrict__ pos_err, double *__restrict__ axis_err, unsigned long long *__restrict__ maxima)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double pe = 0.0, ae = 0.0;
@@ -41,9 +43,24 @@ __global__ __launch_bounds__(256) void joint_errors(const T *__restrict__ S, con
             V3<T> p1, p2, u, w;
             side(s1, j.anchor1, j.axis1, p1, u);
             side(s2, j.anchor2, j.axis2, p2, w);
-            const V3<T> d = { p2.x - p1.x, p2.y - p1.y, p2.z - p1.z };
+            V3<T> d = { p2.x - p1.x, p2.y - p1.y, p2.z - p1.z };
+            if (j.kind == DMX_JOINT_SLIDER) {
+                // the part of p2 - p1 across the axis of side 1 (after an exchange of sides: of the given side 2)
+                const V3<T> a = s1 >= 0 ? u : w;
+                const T along = dot(d, a);
+                d = { d.x - along * a.x, d.y - along * a.y, d.z - along * a.z };
+            }
             pe = (double)tsqrt<T>(dot(d, d));
             if (j.kind == DMX_JOINT_HINGE) { const V3<T> c = cross(u, w); ae = (double)tsqrt<T>(dot(c, c)); }
+            if (j.kind == DMX_JOINT_SLIDER || j.kind == DMX_JOINT_FIXED) {
+                // |2 e_v| of e = conj(q_1) q_2 conj(q_0): the same for the sides as given and exchanged
+                Q4<T> q0 = { T(1), T(0), T(0), T(0) }, q1 = q0, q2 = q0;
+                if (limots != nullptr) q0 = { (T)limots[k].qrel0[0], (T)limots[k].qrel0[1], (T)limots[k].qrel0[2], (T)limots[k].qrel0[3] };
+                if (s1 >= 0) q1 = ldq(S, s1);
+                if (s2 >= 0) q2 = ldq(S, s2);
+                const V3<T> c = lock_error(pose_error(q1, q2, q0));
+                ae = (double)tsqrt<T>(dot(c, c));
+            }
         }
         pos_err[k] = pe;
         axis_err[k] = ae;
@@ -99,13 +116,41 @@ __global__ __launch_bounds__(256) void hinge_angles(const T *__restrict__ S, con
     if (rate != nullptr) rate[k] = thd;
 }
 
+// One lane per joint: a slider's s and s_dot of the sides as given (slider_position, dmx_island_rows.hpp: what the limot row is
+// built from), in the batch's precision.  Other kinds and inactive joints report 0.
+template <class T>
+__global__ __launch_bounds__(256) void slider_positions(const T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, int64_t n_slots,
+                                                        const dmxJoint *__restrict__ joints, int64_t nj, double *__restrict__ pos, double *__restrict__ rate)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nj) return;
+    const dmxJoint j = joints[k];
+    const int s1 = j.body1, s2 = j.body2;
+    auto alive = [&](int s) { return s < n_slots && (bflags[s] & BF_ALIVE) != 0; };
+    const bool active = !(s1 < 0 && s2 < 0) && s1 != s2 && (s1 < 0 || alive(s1)) && (s2 < 0 || alive(s2));
+    T sp = T(0), sd = T(0);
+    if (active && j.kind == DMX_JOINT_SLIDER) {
+        const V3<T> zero = { T(0), T(0), T(0) };
+        const Q4<T> ident = { T(1), T(0), T(0), T(0) };
+        V3<T> x1 = zero, v1 = zero, w1 = zero, x2 = zero, v2 = zero, w2 = zero;
+        Q4<T> q1 = ident, q2 = ident;
+        if (s1 >= 0) { x1 = ldS(S, stride, C_POS, s1); q1 = ldq(S, s1); v1 = ldS(S, stride, C_LVEL, s1); w1 = ldS(S, stride, C_AVEL, s1); }
+        if (s2 >= 0) { x2 = ldS(S, stride, C_POS, s2); q2 = ldq(S, s2); v2 = ldS(S, stride, C_LVEL, s2); w2 = ldS(S, stride, C_AVEL, s2); }
+        const V3<T> an1 = { (T)j.anchor1[0], (T)j.anchor1[1], (T)j.anchor1[2] }, an2 = { (T)j.anchor2[0], (T)j.anchor2[1], (T)j.anchor2[2] };
+        const V3<T> axis1 = { (T)j.axis1[0], (T)j.axis1[1], (T)j.axis1[2] };
+        slider_position(s1 >= 0, x1, q1, v1, w1, s2 >= 0, x2, q2, v2, w2, an1, an2, axis1, sp, sd);
+    }
+    if (pos != nullptr) pos[k] = (double)sp;
+    if (rate != nullptr) rate[k] = (double)sd;
+}
+
 }  // namespace dmx
 
 extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints)
 {
     if (!b || n < 0 || (n > 0 && !joints)) return DMX_EINVAL;
     for (int64_t k = 0; k < n; k++)
-        if (joints[k].kind != DMX_JOINT_BALL && joints[k].kind != DMX_JOINT_HINGE) return DMX_EINVAL;
+        if (joints[k].kind < DMX_JOINT_BALL || joints[k].kind > DMX_JOINT_FIXED) return DMX_EINVAL;
     { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
     b->art.assign(joints, joints + n);
     b->limot.clear();                    // (they were entries of the old set's joints)
@@ -117,14 +162,15 @@ extern "C" int64_t dmxBatchJointCount(dmxBatchID b) { return b ? (int64_t)b->art
 extern "C" int dmxBatchJointFromWorld(dmxBatchID b, int kind, int32_t body1, int32_t body2, const double anchor_w[3], const double axis_w[3],
                                       dmxJoint *out)
 {
-    if (!b || !out || !anchor_w || (kind != DMX_JOINT_BALL && kind != DMX_JOINT_HINGE) || (kind == DMX_JOINT_HINGE && !axis_w)) return DMX_EINVAL;
+    const bool needs_axis = kind == DMX_JOINT_HINGE || kind == DMX_JOINT_SLIDER;
+    if (!b || !out || !anchor_w || kind < DMX_JOINT_BALL || kind > DMX_JOINT_FIXED || (needs_axis && !axis_w)) return DMX_EINVAL;
     if (body1 < -1 || body2 < -1 || body1 >= b->n || body2 >= b->n) return DMX_EINVAL;
     memset(out, 0, sizeof(*out));
     out->kind = kind; out->body1 = body1; out->body2 = body2;
     double ax[3] = { 0, 0, 0 };
     if (axis_w) {
         const double l = std::sqrt(axis_w[0] * axis_w[0] + axis_w[1] * axis_w[1] + axis_w[2] * axis_w[2]);
-        if (kind == DMX_JOINT_HINGE && !(l > 0)) return DMX_EINVAL;
+        if (needs_axis && !(l > 0)) return DMX_EINVAL;
         if (l > 0) for (int k = 0; k < 3; k++) ax[k] = axis_w[k] / l;
     }
     auto side = [&](int32_t s, double *anchor, double *axis) -> int {
@@ -164,19 +210,25 @@ extern "C" int dmxBatchJointErrors(dmxBatchID b, double *pos_err, double *axis_e
     int rc;
     if ((rc = dmx_ensure_dev(b->art_dev, (size_t)nj * sizeof(dmxJoint))) != DMX_OK) return rc;
     if ((rc = dmx_ensure_dev(b->art_err, ((size_t)2 * nj + 2) * sizeof(double))) != DMX_OK) return rc;
+    // (the zero poses are read for sliders and fixed joints only: a set without them copies what it always did)
+    bool lim = false;
+    if (!b->limot.empty()) for (const dmxJoint &j : b->art) lim = lim || j.kind == DMX_JOINT_SLIDER || j.kind == DMX_JOINT_FIXED;
+    if (lim && (rc = dmx_ensure_dev(b->limot_dev, (size_t)nj * sizeof(dmxHingeLimot))) != DMX_OK) return rc;
     double *d_pos = (double *)b->art_err.p + 2, *d_axis = d_pos + nj;
     unsigned long long *d_max = (unsigned long long *)b->art_err.p;
     // (the set lives in pageable host memory: plain copies, which have read it when they return)
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(b->art_dev.p, b->art.data(), (size_t)nj * sizeof(dmxJoint), hipMemcpyHostToDevice));
+    if (lim) HIP_TRY(hipMemcpy(b->limot_dev.p, b->limot.data(), (size_t)nj * sizeof(dmxHingeLimot), hipMemcpyHostToDevice));
+    const dmxHingeLimot *d_lim = lim ? (const dmxHingeLimot *)b->limot_dev.p : nullptr;
     HIP_TRY(hipMemsetAsync(d_max, 0, 2 * sizeof(double), b->stream));
     const unsigned grid = (unsigned)((nj + 255) / 256);
     if (b->precision == DMX_F32)
         hipLaunchKernelGGL((dmx::joint_errors<float>), dim3(grid), dim3(256), 0, b->stream, (const float *)b->slab, b->bflags, b->stride, b->n,
-                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_axis, d_max);
+                           (const dmxJoint *)b->art_dev.p, d_lim, nj, d_pos, d_axis, d_max);
     else
         hipLaunchKernelGGL((dmx::joint_errors<double>), dim3(grid), dim3(256), 0, b->stream, (const double *)b->slab, b->bflags, b->stride, b->n,
-                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_axis, d_max);
+                           (const dmxJoint *)b->art_dev.p, d_lim, nj, d_pos, d_axis, d_max);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (pos_err) HIP_TRY(hipMemcpy(pos_err, d_pos, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
@@ -257,6 +309,34 @@ extern "C" int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (angle) HIP_TRY(hipMemcpy(angle, d_angle, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
+    if (rate) HIP_TRY(hipMemcpy(rate, d_rate, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSliderPositions(dmxBatchID b, double *pos, double *rate)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    const int64_t nj = (int64_t)b->art.size();
+    if (nj == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    int rc;
+    if ((rc = dmx_ensure_dev(b->art_dev, (size_t)nj * sizeof(dmxJoint))) != DMX_OK) return rc;
+    if ((rc = dmx_ensure_dev(b->art_err, ((size_t)2 * nj + 2) * sizeof(double))) != DMX_OK) return rc;
+    double *d_pos = (double *)b->art_err.p + 2, *d_rate = d_pos + nj;
+    // (the set lives in pageable host memory: a plain copy, which has read it when it returns)
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->art_dev.p, b->art.data(), (size_t)nj * sizeof(dmxJoint), hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)((nj + 255) / 256);
+    if (b->precision == DMX_F32)
+        hipLaunchKernelGGL((dmx::slider_positions<float>), dim3(grid), dim3(256), 0, b->stream, (const float *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_rate);
+    else
+        hipLaunchKernelGGL((dmx::slider_positions<double>), dim3(grid), dim3(256), 0, b->stream, (const double *)b->slab, b->bflags, b->stride, b->n,
+                           (const dmxJoint *)b->art_dev.p, nj, d_pos, d_rate);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (pos) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
     if (rate) HIP_TRY(hipMemcpy(rate, d_rate, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost));
     return DMX_OK;
 }

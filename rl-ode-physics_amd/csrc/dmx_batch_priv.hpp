@@ -32,7 +32,8 @@ using namespace dmx;
 // a contact joint in canonical form: body1 a live dynamic slot, normal into it (dmx_joints.cpp)
 // ... or a unit of an articulation joint (unit != 0: j is null, art = its index in the batch's set): at most three rows on the
 // same two bodies, carried beside the contacts -- a ball is one DMX_UNIT_BALL, a hinge a DMX_UNIT_BALL and a DMX_UNIT_HINGE2
-// and, when its limot is present (dmxBatchSetHingeLimots), a UNIT_LIMOT of one row: the only unit whose row can clamp
+// and, when its limot is present (dmxBatchSetHingeLimots), a UNIT_LIMOT of one row; a slider a UNIT_LOCK, a UNIT_SLIDER2 and, when
+// present, a UNIT_SLIMOT; a fixed joint a UNIT_BALL and a UNIT_LOCK.  The two limot units are the only ones whose row can clamp
 struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; int unit = 0; int art = -1; };
 
 struct dmxBatch {

@@ -90,13 +90,16 @@ template <class T> struct IslandSet {
     int singles;           // 1: islands of one body with 1..8 contacts are left to solve_singles / solve_singles_lds (one lane each);
                            // whoever builds `big` must then keep such islands out of it
     // 1: some entries of the contact arrays are units of articulation joints (dmx_island_rows.hpp: joint_unit_rows), marked by
-    // cmu = UNIT_BALL_MU / UNIT_HINGE2_MU / UNIT_LIMOT_MU; within an island they come before its contacts.  0: contacts only
+    // cmu = UNIT_*_MU; within an island they come before its contacts.  0: contacts only
     int has_units = 0;
 };
-// a unit's marker in IslandSet::cmu: minus its row count (a contact's mu is never negative there when has_units is set)
+// a unit's marker in IslandSet::cmu: a negative number (for the first three minus the row count; a contact's mu is never negative there when has_units is set)
 // (UNIT_LIMOT: a hinge's limit / motor row, dmxBatchSetHingeLimots -- the one unit whose row can clamp)
-constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2, UNIT_LIMOT = 3;
-constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0, UNIT_LIMOT_MU = -1.0;
+// (UNIT_LOCK: the three angular rows of a slider or a fixed joint; UNIT_SLIDER2: a slider's two linear rows; UNIT_SLIMOT: a slider's
+//  limit / motor row, which can clamp as a hinge's can.  Their markers are distinct numbers below the others: a unit's row count
+//  comes from its kind, unit_rows_of in dmx_island_rows.hpp and rpc_of in dmx_joints.cpp)
+constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2, UNIT_LIMOT = 3, UNIT_LOCK = 4, UNIT_SLIDER2 = 5, UNIT_SLIMOT = 6;
+constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0, UNIT_LIMOT_MU = -1.0, UNIT_LOCK_MU = -4.0, UNIT_SLIDER2_MU = -5.0, UNIT_SLIMOT_MU = -6.0;
 // Is a hinge's limot row there?  fmax > 0, or a finite stop.  Decided on the parameters alone -- the host sizes islands, schedules and LCP
 // scratch before the device has looked at the angle, so the row count must not depend on the state -- and in this one place: the
 // batch's tick (dmx_joints.cpp) and the ODE face (ode_compat.cpp: whether to hand the batch limots at all) must agree.

@@ -1,5 +1,5 @@
 // dmx_island_rows.hpp -- the per-body / per-contact / per-row phase functions of the general island step (gravity and
-// world-frame inertia, the rows of a contact joint and of a ball / hinge joint's units, rhs and M^-1 J^T, one SOR row update, the integration of a body).
+// world-frame inertia, the rows of a contact joint and of the units of a ball, hinge, slider or fixed joint, rhs and M^-1 J^T, one SOR row update, the integration of a body).
 // Shared by the SOR kernels (dmx_islands.hip) and the exact solve of dWorldStep (dmx_lcp.hip): both steppers build the same
 // rows [ODE-recall: dxStepIsland / dxQuickStepIsland share getInfo1/getInfo2], /root/reference/src/main.c:213.
 #pragma once
@@ -63,11 +63,16 @@ __device__ __forceinline__ void stage_body(const T *S, const uint8_t *bflags, in
 }
 
 // per-contact surface arrays are optional: without them every contact carries the batch's surface (StepParams)
-// (an entry that is a unit of an articulation joint carries minus its row count there: UNIT_BALL_MU / UNIT_HINGE2_MU / UNIT_LIMOT_MU)
+// (an entry that is a unit of an articulation joint carries its unit's marker there, a negative number: UNIT_*_MU, and the
+//  marker says how many rows the unit has)
+template <class T> DMX_HD int unit_rows_of(T mu)
+{
+    return (mu == T(UNIT_HINGE2_MU) || mu == T(UNIT_SLIDER2_MU)) ? 2 : (mu == T(UNIT_LIMOT_MU) || mu == T(UNIT_SLIMOT_MU)) ? 1 : 3;
+}
 template <class T> __device__ __forceinline__ int contact_rpc(const IslandSet<T> &I, const StepParams<T> &P, int ci)
 {
     const T mu = I.cmu != nullptr ? I.cmu[ci] : P.mu;
-    if (I.has_units && mu < 0) return mu == T(UNIT_HINGE2_MU) ? 2 : mu == T(UNIT_LIMOT_MU) ? 1 : 3;
+    if (I.has_units && mu < 0) return unit_rows_of(mu);
     return mu > 0 ? 3 : 1;
 }
 template <class T> __device__ __forceinline__ bool contact_is_unit(const IslandSet<T> &I, int ci)
@@ -124,9 +129,16 @@ template <class T> DMX_HD Q4<T> qmul(const Q4<T> &a, const Q4<T> &b)
 // axis1 = the hinge axis in the frame of side 1.  e = conj(q1) q2 conj(q0), phi = 2 atan2(e_v . axis1, e_w) in (-pi, pi] (e and -e
 // are the same rotation: the half angle is taken with e_w >= 0), theta = -phi: the angle of side 1 relative to side 2, ODE's sign.
 // (host too: the ODE face's dJointGetHingeAngle, tests/harness/limot_rows_harness.cpp)
-template <class T> DMX_HD T hinge_angle(const Q4<T> &q1, const Q4<T> &q2, const Q4<T> &q0, const V3<T> &axis1)
+// e = conj(q1) q2 conj(q0): the rotation of side 2 against side 1 since the zero pose, in the frame of side 1
+template <class T> DMX_HD Q4<T> pose_error(const Q4<T> &q1, const Q4<T> &q2, const Q4<T> &q0) { return qmul(qmul(qconj(q1), q2), qconj(q0)); }
+// 2 e_v with e_w >= 0: what the angular lock of a slider or a fixed joint pulls to zero (host too: dmxBatchJointErrors' axis_err)
+template <class T> DMX_HD V3<T> lock_error(const Q4<T> &e)
 {
-    const Q4<T> e = qmul(qmul(qconj(q1), q2), qconj(q0));
+    const T two = e.w < T(0) ? T(-2) : T(2);
+    return { two * e.x, two * e.y, two * e.z };
+}
+template <class T> DMX_HD T hinge_angle_of(const Q4<T> &e, const V3<T> &axis1)
+{
     T s = fma_(e.z, axis1.z, fma_(e.y, axis1.y, e.x * axis1.x)), c = e.w;
     if (c < T(0)) { s = -s; c = -c; }
     const T pi = T(3.14159265358979323846);
@@ -135,7 +147,15 @@ template <class T> DMX_HD T hinge_angle(const Q4<T> &q1, const Q4<T> &q2, const 
     if (phi > pi) phi = pi;
     return -phi;
 }
+template <class T> DMX_HD T hinge_angle(const Q4<T> &q1, const Q4<T> &q2, const Q4<T> &q0, const V3<T> &axis1)
+{
+    return hinge_angle_of(pose_error(q1, q2, q0), axis1);
+}
 
+template <class T> DMX_HD Q4<T> ldq(const T *S, int s)
+{
+    return { S[slab_ix(C_QUAT + 0, s)], S[slab_ix(C_QUAT + 1, s)], S[slab_ix(C_QUAT + 2, s)], S[slab_ix(C_QUAT + 3, s)] };
+}
 // The limot unit's one row, behind its hinge's five.  The unit's reals: cpos = axis1 as given (in the frame of the given body 1,
 // the world's if that side is the world), cnormal[3] + cdepth = q_0 (w, x, y, z), cbounce / cbounce_vel / csoft_erp / csoft_cfm =
 // lo_stop / hi_stop / vel / fmax; cmode != 0: the sides were exchanged (given as (world, body): this entry's body 1 is the given
@@ -185,12 +205,141 @@ DMX_HD int limot_unit_row(const T *S, const IslandSet<T> &I, const StepParams<T>
     return 1;
 }
 
+// ---- the slider and fixed joints' units (the definitions: include/dmx_batch.h at DMX_JOINT_SLIDER) ------------------------------
+// What the slider's linear unit and its limot row share, in canonical sides: a_1, a_2 (a world side: 0) and err = p_2 - p_1, formed
+// as the ball unit forms it (diff_of_sums).  ci = the LINEAR unit's entry: cpos = anchor 1, cnormal = anchor 2.
+template <class T>
+DMX_HD void slider_arms(const T *S, int64_t stride, const IslandSet<T> &I, int ci, const M3<T> &R1, V3<T> &a1, V3<T> &a2, V3<T> &err)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    a1 = mulv(R1, ld3(I.cpos + 3 * (size_t)ci));
+    const V3<T> f2 = ld3(I.cnormal + 3 * (size_t)ci);
+    const V3<T> x1 = ldS(S, stride, C_POS, s1);
+    V3<T> x2 = f2;
+    a2 = { T(0), T(0), T(0) };
+    if (s2 >= 0) { x2 = ldS(S, stride, C_POS, s2); a2 = mulv(quat_to_R(ldq(S, s2)), f2); }
+    err = { diff_of_sums(x2.x, a2.x, x1.x, a1.x), diff_of_sums(x2.y, a2.y, x1.y, a1.y), diff_of_sums(x2.z, a2.z, x1.z, a1.z) };
+}
+// one row J = [ r, arm x r | -r, -(a2 x r) ]
+template <class T> DMX_HD void slider_row_J(T *J, const V3<T> &r, const V3<T> &arm, const V3<T> &a2, bool two)
+{
+    st3(J, r);
+    st3(J + 3, cross(arm, r));
+    if (two) {
+        const V3<T> g = cross(a2, r);
+        J[6] = -r.x; J[7] = -r.y; J[8] = -r.z;
+        J[9] = -g.x; J[10] = -g.y; J[11] = -g.z;
+    } else {
+        for (int j = 6; j < 12; j++) J[j] = T(0);
+    }
+}
+
+// The slider's linear unit, two rows.  The unit's reals: cpos / cnormal = the two sides' anchors (as a ball unit's), cbounce /
+// cbounce_vel / csoft_erp = axis1 in the frame of body 1 (canonical sides).  u = R_1 axis1, r = p, q of plane_space(u):
+// J = [ r, (p_2 - x_1) x r | -r, -(a_2 x r) ], c = k (p_2 - p_1) . r; p_2 - x_1 = a_1 + (p_2 - p_1).
+template <class T>
+DMX_HD int slider_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
+    const M3<T> R1 = quat_to_R(ldq(S, s1));
+    V3<T> a1, a2, err;
+    slider_arms(S, stride, I, ci, R1, a1, a2, err);
+    const V3<T> axis1 = { I.cbounce[ci], I.cbounce_vel[ci], I.csoft_erp[ci] };
+    V3<T> dir[2];
+    plane_space(mulv(R1, axis1), dir[0], dir[1]);
+    const V3<T> arm = { a1.x + err.x, a1.y + err.y, a1.z + err.z };
+    const T k = hinv * P.erp;
+    for (int dnum = 0; dnum < 2; dnum++) {
+        T *row = rows + (size_t)(m + dnum) * RW_COUNT;
+        jb[2 * (m + dnum)] = l1; jb[2 * (m + dnum) + 1] = l2;
+        slider_row_J(row + RW_J, dir[dnum], arm, a2, s2 >= 0);
+        row[RW_LO] = -Limits<T>::inf(); row[RW_HI] = Limits<T>::inf();
+        row[RW_RHS] = k * dot(err, dir[dnum]);      // c for now
+        row[RW_AD] = P.cfm;                         // cfm for now
+        row[RW_LAM] = T(0);
+    }
+    return 2;
+}
+
+// c, lo, hi of a limit / motor row from its coordinate (a hinge's theta, a slider's s): the table of include/dmx_batch.h
+template <class T> DMX_HD void limot_table(T x, T lo_s, T hi_s, T vel, T fmax, T k, T &c, T &lo, T &hi)
+{
+    const T inf = Limits<T>::inf();
+    const T g = fmax > T(0) ? (vel > T(0) ? fmax : vel < T(0) ? -fmax : T(0)) : T(0);
+    const bool limited = lo_s <= hi_s && (lo_s > -inf || hi_s < inf);
+    c = T(0); lo = T(0); hi = T(0);                        // inside its range, no motor: the row stays, and does nothing
+    if (limited && lo_s == hi_s) { c = -k * (x - lo_s); lo = -inf; hi = inf; }
+    else if (limited && x <= lo_s) { c = -k * (x - lo_s); lo = g; hi = inf; }
+    else if (limited && x >= hi_s) { c = -k * (x - hi_s); lo = -inf; hi = g; }
+    else if (fmax > T(0)) { c = vel; lo = -fmax; hi = fmax; }
+}
+
+// The slider limot's one row, behind the slider's five: the entry directly before it is the joint's linear unit (the host emits a
+// joint's units back to back), whose anchors it reads.  Its own reals: cpos = axis1 AS GIVEN, cbounce / cbounce_vel / csoft_erp /
+// csoft_cfm = lo_stop / hi_stop / vel / fmax; cmode != 0: the sides were exchanged.  With w = u = R_1 axis1 -- or, after an exchange
+// (given side 1 is the world: u = its axis as given, and there is no body 2), w = -u -- in canonical sides s = -w . (p_2 - p_1) and
+// J = [ w, arm x w | -w, -(a_2 x w) ], arm = p_2 - x_1 (after an exchange a_1): the row's velocity is s_dot.
+template <class T>
+DMX_HD int slimot_unit_row(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    const bool rev = I.cmode[ci] != 0;
+    T *row = rows + (size_t)m * RW_COUNT;
+    jb[2 * m] = I.local[s1]; jb[2 * m + 1] = s2 >= 0 ? I.local[s2] : -1;
+    const M3<T> R1 = quat_to_R(ldq(S, s1));
+    V3<T> a1, a2, err;
+    slider_arms(S, stride, I, ci - 1, R1, a1, a2, err);
+    const V3<T> axis1 = ld3(I.cpos + 3 * (size_t)ci);
+    V3<T> w = { -axis1.x, -axis1.y, -axis1.z }, arm = a1;
+    if (!rev) { w = mulv(R1, axis1); arm = { a1.x + err.x, a1.y + err.y, a1.z + err.z }; }
+    T c, lo, hi;
+    limot_table(-dot(w, err), I.cbounce[ci], I.cbounce_vel[ci], I.csoft_erp[ci], I.csoft_cfm[ci], hinv * P.erp, c, lo, hi);
+    row[RW_LO] = lo; row[RW_HI] = hi;
+    row[RW_RHS] = c;                    // c for now
+    row[RW_AD] = P.cfm;                 // cfm for now
+    row[RW_LAM] = T(0);
+    slider_row_J(row + RW_J, w, arm, a2, s2 >= 0);
+    return 1;
+}
+
+// s and s_dot of a slider in the sides AS GIVEN (dmxBatchSliderPositions, the ODE face's dJointGetSliderPosition / Rate): has_i =
+// side i is a body with position x_i, quaternion q_i, velocities v_i, w_i; anchor_i, axis1 in the side's frame (the world's when it
+// is the world).  s = u . (p_1 - p_2), s_dot = [ u, (p_2 - x_1) x u | -u, -(a_2 x u) ] . (v_1, w_1, v_2, w_2).
+template <class T>
+DMX_HD void slider_position(bool has1, const V3<T> &x1, const Q4<T> &q1, const V3<T> &v1, const V3<T> &w1,
+                            bool has2, const V3<T> &x2, const Q4<T> &q2, const V3<T> &v2, const V3<T> &w2,
+                            const V3<T> &anchor1, const V3<T> &anchor2, const V3<T> &axis1, T &s, T &s_dot)
+{
+    V3<T> u = axis1, a1 = { T(0), T(0), T(0) }, a2 = a1, c1 = anchor1, c2 = anchor2;
+    if (has1) { const M3<T> R = quat_to_R(q1); u = mulv(R, axis1); a1 = mulv(R, anchor1); c1 = x1; }
+    if (has2) { a2 = mulv(quat_to_R(q2), anchor2); c2 = x2; }
+    const V3<T> err = { diff_of_sums(c2.x, a2.x, c1.x, a1.x), diff_of_sums(c2.y, a2.y, c1.y, a1.y), diff_of_sums(c2.z, a2.z, c1.z, a1.z) };
+    s = -dot(u, err);
+    s_dot = T(0);
+    if (has1) { const V3<T> arm = { a1.x + err.x, a1.y + err.y, a1.z + err.z }; s_dot = dot(u, v1) + dot(cross(arm, u), w1); }
+    if (has2) s_dot -= dot(u, v2) + dot(cross(a2, u), w2);
+}
+
+// the slider's two linear units, by marker (both at or below UNIT_SLIDER2_MU)
+template <class T>
+DMX_HD int slider_linear_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
+{
+    const T mu = I.cmu[ci];
+    if (mu == T(UNIT_SLIDER2_MU)) return slider_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
+    return slimot_unit_row(S, stride, I, P, rows, jb, ci, m, hinv);
+}
+
 // ---- rows of a unit of an articulation joint (dmxBatchSetJoints), written at island-relative row m ---------------------------
 // The unit's six reals travel in the contact arrays: cpos = the first side's anchor (ball unit) or axis (hinge unit) in the
 // frame of body 1, cnormal = the second side's in the frame of body 2 -- or in the world frame when there is no body 2.
 //   ball unit, d = e_x, e_y, e_z:  J = [ d, a1 x d | -d, -(a2 x d) ],  c = k ((x2 + a2) - (x1 + a1)) . d,   a_i = R_i anchor_i
 //   hinge unit, r = p, q of plane_space(u), u = R_1 axis1, w = R_2 axis2:  J = [ 0, r | 0, -r ],  c = k (u x w) . r
-// with k = erp / h, cfm = the world's, no bounds.  (A limot unit: limot_unit_row.)  Returns the unit's row count.
+//   lock unit (slider, fixed), d = e_x, e_y, e_z:  J = [ 0, d | 0, -d ],  c = k Phi . d,  Phi = R_1 (2 e_v), e = conj(q_1) q_2 conj(q_0c):
+//     cnormal + cdepth = q_0c (w, x, y, z).  It is built here, as a variant of the hinge unit, and not in a function of its own:
+//     that costs solve_islands<float> eleven VGPRs and a wave per SIMD (profiles/slider_kernel_resources.txt)
+// with k = erp / h, cfm = the world's, no bounds.  (A limot unit: limot_unit_row; a slider's linear and limot units:
+// slider_linear_unit_rows.)  Returns the unit's row count.
 template <class T>
 DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                T *rows, int *jb, int ci, int m, T hinv)
@@ -199,14 +348,24 @@ DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, co
     //  limot_unit_row itself and never gets here with one: dispatched only from here, solve_islands<float> needs 82 VGPRs for 80 and
     //  loses its sixth wave per SIMD, profiles/limot_kernel_resources.txt.  Keep both.)
     if (I.cmu[ci] == T(UNIT_LIMOT_MU)) return limot_unit_row(S, I, P, rows, jb, ci, m, hinv);
+    if (I.cmu[ci] <= T(UNIT_SLIDER2_MU)) return slider_linear_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
     const int s1 = I.cb1[ci], s2 = I.cb2[ci];
     const int l1 = I.local[s1], l2 = s2 >= 0 ? I.local[s2] : -1;
-    const bool hinge2 = I.cmu[ci] == T(UNIT_HINGE2_MU);
-    const V3<T> f1 = ld3(I.cpos + 3 * (size_t)ci), f2 = ld3(I.cnormal + 3 * (size_t)ci);
+    const bool hinge2 = I.cmu[ci] == T(UNIT_HINGE2_MU), lock = I.cmu[ci] == T(UNIT_LOCK_MU);
+    V3<T> f1 = ld3(I.cpos + 3 * (size_t)ci);
+    const V3<T> f2 = ld3(I.cnormal + 3 * (size_t)ci);
     const Q4<T> q1 = { S[slab_ix(C_QUAT + 0, s1)], S[slab_ix(C_QUAT + 1, s1)], S[slab_ix(C_QUAT + 2, s1)], S[slab_ix(C_QUAT + 3, s1)] };
-    const V3<T> w1 = mulv(quat_to_R(q1), f1);              // a1 (ball unit) / u (hinge unit)
+    if (lock) {
+        // the angular-lock unit of a slider or a fixed joint: cnormal[3] + cdepth = q_0c, the zero pose in canonical sides; what
+        // is turned into the world frame below is 2 e_v of e = conj(q_1) q_2 conj(q_0c)
+        Q4<T> q2 = { T(1), T(0), T(0), T(0) };
+        if (s2 >= 0) q2 = ldq(S, s2);
+        const Q4<T> q0 = { f2.x, f2.y, f2.z, I.cdepth[ci] };
+        f1 = lock_error(pose_error(q1, q2, q0));
+    }
+    const V3<T> w1 = mulv(quat_to_R(q1), f1);              // a1 (ball unit) / u (hinge unit) / Phi (lock unit)
     V3<T> w2 = f2;                                         // a world side: the anchor / axis as given
-    if (s2 >= 0) {
+    if (s2 >= 0 && !lock) {
         const Q4<T> q2 = { S[slab_ix(C_QUAT + 0, s2)], S[slab_ix(C_QUAT + 1, s2)], S[slab_ix(C_QUAT + 2, s2)], S[slab_ix(C_QUAT + 3, s2)] };
         w2 = mulv(quat_to_R(q2), f2);
     }
@@ -218,6 +377,10 @@ DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, co
         plane_space(w1, dir[0], dir[1]);
         dir[2] = { T(0), T(0), T(0) };
         err = cross(w1, w2);
+    } else if (lock) {
+        n = 3;
+        dir[0] = { T(1), T(0), T(0) }; dir[1] = { T(0), T(1), T(0) }; dir[2] = { T(0), T(0), T(1) };
+        err = w1;
     } else {
         n = 3;
         dir[0] = { T(1), T(0), T(0) }; dir[1] = { T(0), T(1), T(0) }; dir[2] = { T(0), T(0), T(1) };
@@ -236,12 +399,13 @@ DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, co
         T *J = row + RW_J;
         const V3<T> d = dir[dnum];
         const V3<T> zero = { T(0), T(0), T(0) };
-        const V3<T> lin = hinge2 ? zero : d;
-        const V3<T> ang1 = hinge2 ? d : cross(w1, d);
+        const bool angular = hinge2 || lock;
+        const V3<T> lin = angular ? zero : d;
+        const V3<T> ang1 = angular ? d : cross(w1, d);
         st3(J, lin);
         st3(J + 3, ang1);
         if (s2 >= 0) {
-            const V3<T> ang2 = hinge2 ? d : cross(w2, d);
+            const V3<T> ang2 = angular ? d : cross(w2, d);
             J[6] = -lin.x; J[7] = -lin.y; J[8] = -lin.z;
             J[9] = -ang2.x; J[10] = -ang2.y; J[11] = -ang2.z;
         } else {
@@ -264,6 +428,7 @@ __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const I
 {
     if (RPCK == 0 && contact_is_unit(I, ci)) {
         if (I.cmu[ci] == T(UNIT_LIMOT_MU)) (void)limot_unit_row(S, I, P, rows, jb, ci, m, hinv);
+        else if (I.cmu[ci] <= T(UNIT_SLIDER2_MU)) (void)slider_linear_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
         else (void)joint_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
         return;
     }

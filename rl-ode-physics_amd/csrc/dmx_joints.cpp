@@ -82,7 +82,9 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // `include` (optional) restricts the tick to a subset of bodies: the rest is stepped by the fused kernels
     auto live = [&](int s) { return s >= 0 && s < n && (b->h_bflags[(size_t)s] & BF_ALIVE) && (!include || include[s]); };
     // the active articulation joints first, as units of at most three rows (a ball: one unit; a hinge: its ball unit, the two
-    // angular rows and, when its limot is present, the limit / motor row), in the order of the set: the stable sort by island below keeps them ahead of the island's contacts
+    // angular rows and, when its limot is present, the limit / motor row; a slider: the angular lock, the two linear rows and, when
+    // present, its limot row; a fixed joint: a ball unit and the lock), in the order of the set: the stable sort by island below
+    // keeps them ahead of the island's contacts
     if (!b->art.empty() && (include || geo)) {          // (every caller that steps a subset is refused before it gets here)
         fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour articulation joints (dmxBatchSetJoints)\n");
         return DMX_EINVAL;
@@ -97,17 +99,28 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             const bool rev = b1 < 0;
             if (rev) { b1 = b2; b2 = -1; }
             DmxCanonicalJoint u; u.b1 = b1; u.b2 = b2; u.j = nullptr; u.rev = rev; u.unit = UNIT_BALL; u.art = (int)a;
+            const bool limot = !b->limot.empty() && dmx_limot_present(b->limot[a]);
+            if (j.kind == DMX_JOINT_SLIDER) {
+                // lock (3), linear (2), limot (1 if present): the limot's entry reads its anchors from the linear unit before it
+                u.unit = UNIT_LOCK; cj.push_back(u);
+                u.unit = UNIT_SLIDER2; cj.push_back(u);
+                if (limot) { u.unit = UNIT_SLIMOT; cj.push_back(u); n_limots++; }
+                continue;
+            }
             cj.push_back(u);
             if (j.kind == DMX_JOINT_HINGE) {
                 u.unit = UNIT_HINGE2; cj.push_back(u);
-                if (!b->limot.empty() && dmx_limot_present(b->limot[a])) { u.unit = UNIT_LIMOT; cj.push_back(u); n_limots++; }
+                if (limot) { u.unit = UNIT_LIMOT; cj.push_back(u); n_limots++; }
+            } else if (j.kind == DMX_JOINT_FIXED) {
+                u.unit = UNIT_LOCK; cj.push_back(u);
             }
         }
     }
     const int n_units = (int)cj.size();
     // rows of an entry, and how many of them can clamp (a limot unit's one row is counted as able to, whatever its state will be)
-    auto rpc_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_HINGE2 ? 2 : c.unit == UNIT_LIMOT ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
-    auto nbd_rows_of = [](const CJ &c) { return c.unit ? (c.unit == UNIT_LIMOT ? 1 : 0) : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
+    auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT; };
+    auto rpc_of = [&](const CJ &c) { return c.unit ? ((c.unit == UNIT_HINGE2 || c.unit == UNIT_SLIDER2) ? 2 : is_limot(c.unit) ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
+    auto nbd_rows_of = [&](const CJ &c) { return c.unit ? (is_limot(c.unit) ? 1 : 0) : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
     for (int64_t k = 0; k < nj_in; k++) {
         const dmxContactJoint &j = joints[k];
         int b1 = live(j.body1) ? j.body1 : -1, b2 = live(j.body2) ? j.body2 : -1;
@@ -396,6 +409,19 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     T *cpos = hr, *cnormal = cpos + 3 * (size_t)nc, *cdepth = cnormal + 3 * (size_t)nc, *cmu = cdepth + nc,
       *cbounce = cmu + nc, *cbv = cbounce + nc, *cserp = cbv + nc, *cscfm = cserp + nc;
 
+    // a slider's limot entry reads its anchors from the entry before it, which must be its own joint's linear unit: units are
+    // emitted back to back and the sort by island is stable (and the ODE row order, which is not, is refused with joints set)
+    if (n_limots)
+        for (int d = 0; d < nc; d++) {
+            const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
+            if (c.unit != UNIT_SLIMOT) continue;
+            const CJ *before = d > 0 ? &cj[(size_t)con_sorted[(size_t)d - 1]] : nullptr;
+            if (!before || before->unit != UNIT_SLIDER2 || before->art != c.art || crow_h[(size_t)d] != crow_h[(size_t)d - 1] + 2) {
+                fprintf(stderr, "libode_mi355: internal error: a slider's limit / motor unit does not follow its linear unit\n");
+                for (int s : slots) { b->sc_parent[(size_t)s] = s; island_of[(size_t)s] = -1; }     // scratch back to its idle state
+                return DMX_EINVAL;
+            }
+        }
     // counting sort of bodies and joints by island (stable: ascending slots / creation order)
     memset(body_off, 0, (size_t)(ni + 1) * sizeof(int));
     memset(con_off, 0, (size_t)(ni + 1) * sizeof(int));
@@ -423,6 +449,36 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                         for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)a.axis1[k]; cnormal[3 * (size_t)d + k] = (T)l.qrel0[k]; }
                         cdepth[d] = (T)l.qrel0[3]; cmu[d] = (T)UNIT_LIMOT_MU;
                         cbounce[d] = (T)l.lo_stop; cbv[d] = (T)l.hi_stop; cserp[d] = (T)l.vel; cscfm[d] = (T)l.fmax;
+                        continue;
+                    }
+                    if (c.unit == UNIT_SLIMOT) {
+                        // a slider's limot unit: axis1 AS GIVEN, stops / vel / fmax, cmode as the hinge's; its anchors are the linear
+                        // unit's, the entry before it (a joint's units are emitted back to back and the sort by island is stable)
+                        const dmxHingeLimot &l = b->limot[(size_t)c.art];
+                        cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = c.rev ? 1 : 0; csrc[d] = 0;
+                        for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)a.axis1[k]; cnormal[3 * (size_t)d + k] = T(0); }
+                        cdepth[d] = T(0); cmu[d] = (T)UNIT_SLIMOT_MU;
+                        cbounce[d] = (T)l.lo_stop; cbv[d] = (T)l.hi_stop; cserp[d] = (T)l.vel; cscfm[d] = (T)l.fmax;
+                        continue;
+                    }
+                    if (c.unit == UNIT_LOCK) {
+                        // the zero pose in canonical sides where a contact has its normal and depth: q_0, conj(q_0) after an exchange,
+                        // the identity without limots
+                        double q0[4] = { 1.0, 0.0, 0.0, 0.0 };
+                        if (!b->limot.empty()) for (int k = 0; k < 4; k++) q0[k] = (k > 0 && c.rev ? -1.0 : 1.0) * b->limot[(size_t)c.art].qrel0[k];
+                        cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = 0; csrc[d] = 0;
+                        for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = T(0); cnormal[3 * (size_t)d + k] = (T)q0[k]; }
+                        cdepth[d] = (T)q0[3]; cmu[d] = (T)UNIT_LOCK_MU;
+                        cbounce[d] = T(0); cbv[d] = T(0); cserp[d] = T(0); cscfm[d] = T(0);
+                        continue;
+                    }
+                    if (c.unit == UNIT_SLIDER2) {
+                        // the anchors as a ball unit's, the axis of (canonical) side 1 in three of the surface slots
+                        const double *f1 = c.rev ? a.anchor2 : a.anchor1, *f2 = c.rev ? a.anchor1 : a.anchor2, *ax = c.rev ? a.axis2 : a.axis1;
+                        cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = 0; csrc[d] = 0;
+                        for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)f1[k]; cnormal[3 * (size_t)d + k] = (T)f2[k]; }
+                        cdepth[d] = T(0); cmu[d] = (T)UNIT_SLIDER2_MU;
+                        cbounce[d] = (T)ax[0]; cbv[d] = (T)ax[1]; cserp[d] = (T)ax[2]; cscfm[d] = T(0);
                         continue;
                     }
                     const double *f1 = c.unit == UNIT_BALL ? (c.rev ? a.anchor2 : a.anchor1) : (c.rev ? a.axis2 : a.axis1);
@@ -596,8 +652,8 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     for (int q = 0; q < rpc; q++) {
                         // (a limot's row: low bits 1, as a bounded friction row's -- clamped, its value need not be zero.  The
                         //  ordinal within the pair is stable while the set and the limots' presence are)
-                        R.key[(size_t)(r + q)] = base | (uint64_t)(c.unit == UNIT_LIMOT ? 1 : q);
-                        R.unbounded[(size_t)(r + q)] = c.unit ? (c.unit != UNIT_LIMOT) : (q > 0 && !(c.j->mu < __builtin_huge_val()));
+                        R.key[(size_t)(r + q)] = base | (uint64_t)(is_limot(c.unit) ? 1 : q);
+                        R.unbounded[(size_t)(r + q)] = c.unit ? !is_limot(c.unit) : (q > 0 && !(c.j->mu < __builtin_huge_val()));
                     }
                 }
                 // every body's rows (creation order): counting sort over the island's contacts; local index = position among the

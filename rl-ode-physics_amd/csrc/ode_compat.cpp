@@ -89,9 +89,10 @@ struct dxJoint {
     dContact contact;
     dxBody *b1 = nullptr, *b2 = nullptr;
     int type = dJointTypeContact;
-    // a ball or a hinge: anchors and axes in the frames of the two bodies (world frame for a side without a body)
+    // a ball, a hinge, a slider or a fixed joint: anchors and axes in the frames of the two bodies (world frame for a side without a body)
     double anchor1[3] = { 0, 0, 0 }, anchor2[3] = { 0, 0, 0 }, axis1[3] = { 1, 0, 0 }, axis2[3] = { 1, 0, 0 };
-    // a hinge's limit and motor (dJointSetHingeParam) and its zero pose, conj(q_1) q_2 of the sides AS ATTACHED when the anchor or
+    // a hinge's or a slider's limit and motor (dJointSetHingeParam / dJointSetSliderParam) and the zero pose -- a slider's and a fixed
+    // joint's too --, conj(q_1) q_2 of the sides AS ATTACHED when the anchor or
     // the axis was last set (include/dmx_batch.h, dmxHingeLimot).  rev: attached as (0, body) -- b1 / b2 above are exchanged, and
     // the angle, the rate, the stops and the motor are those of the sides as attached [ODE-recall dJOINT_REVERSE: dJointGetHingeAngle
     // and dJointAddHingeTorque change sign]
@@ -109,7 +110,7 @@ struct dxWorld {
     int cap = 0;
     std::vector<dxBody *> slots;       // slot -> body (nullptr = free)
     std::vector<dxJoint *> joints;     // contact joints of the current tick, creation order
-    std::vector<dxJoint *> arts;       // ball and hinge joints, creation order: they persist (dmxBatchSetJoints)
+    std::vector<dxJoint *> arts;       // ball, hinge, slider and fixed joints, creation order: they persist (dmxBatchSetJoints)
     bool art_dirty = false;            // ... and changed since the batch last saw them
     bool limot_dirty = false;          // a hinge's limit / motor parameter or zero pose changed since the batch last saw them
     bool limots_sent = false;          // the batch holds limots (dmxBatchSetHingeLimots)
@@ -307,7 +308,9 @@ static int world_step(dWorldID w, dReal h, int stepper)
         for (const dxJoint *j : w->arts) {
             dmxJoint a;
             memset(&a, 0, sizeof a);
-            a.kind = j->type == dJointTypeHinge ? DMX_JOINT_HINGE : DMX_JOINT_BALL;
+            // (the batch's enum does not take ODE's numbering: kind 7 stays refused there)
+            a.kind = j->type == dJointTypeHinge ? DMX_JOINT_HINGE : j->type == dJointTypeSlider ? DMX_JOINT_SLIDER :
+                     j->type == dJointTypeFixed ? DMX_JOINT_FIXED : DMX_JOINT_BALL;
             a.body1 = j->b1 ? j->b1->slot : -1;
             a.body2 = j->b2 ? j->b2->slot : -1;
             for (int k = 0; k < 3; k++) { a.anchor1[k] = j->anchor1[k]; a.anchor2[k] = j->anchor2[k]; a.axis1[k] = j->axis1[k]; a.axis2[k] = j->axis2[k]; }
@@ -331,10 +334,12 @@ static int world_step(dWorldID w, dReal h, int stepper)
             dmxHingeLimot l;
             l.lo_stop = j->lo_stop; l.hi_stop = j->hi_stop; l.vel = j->vel; l.fmax = j->fmax;
             for (int k = 0; k < 4; k++) l.qrel0[k] = j->qrel0[k];
-            if (j->type == dJointTypeHinge && dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax)) any = true;
+            if ((j->type == dJointTypeHinge || j->type == dJointTypeSlider) && dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax)) any = true;
+            if (j->type == dJointTypeSlider || j->type == dJointTypeFixed) any = true;      // (their zero pose is part of their rows)
             w->al.push_back(l);
         }
-        // (a world none of whose hinges has a limit or a motor hands the batch nothing: its ticks are what they were without them)
+        // (a world without sliders and fixed joints none of whose hinges has a limit or a motor hands the batch nothing: its ticks
+        //  are what they were without them)
         if (any) { DMX_MUST(dmxBatchSetHingeLimots(w->batch, (int64_t)w->al.size(), w->al.data())); w->limots_sent = true; }
         else if (w->limots_sent) { DMX_MUST(dmxBatchSetHingeLimots(w->batch, 0, nullptr)); w->limots_sent = false; }
         w->limot_dirty = false;
@@ -877,14 +882,14 @@ extern "C" void dJointAttach(dJointID j, dBodyID b1, dBodyID b2)
     if (!j) return;
     j->b1 = b1; j->b2 = b2;
     if (j->type != dJointTypeContact) {
-        // a ball or a hinge attached as (0, body): ODE exchanges the two, so that body 1 is the body [ODE-recall dJointAttach, dJOINT_REVERSE]
+        // an articulation joint attached as (0, body): ODE exchanges the two, so that body 1 is the body [ODE-recall dJointAttach, dJOINT_REVERSE]
         j->rev = !j->b1 && j->b2;
         if (j->rev) { j->b1 = j->b2; j->b2 = nullptr; }
         if (j->world) j->world->art_dirty = true;
     }
 }
 
-// ================================================================================ ball and hinge joints
+// ================================================================================ ball, hinge, slider and fixed joints
 namespace {
 
 dJointID create_art(dWorldID w, dJointGroupID g, int type)
@@ -925,7 +930,7 @@ void given_sides(const dxJoint *j, const dxBody *&g1, const dxBody *&g2, dmx::Q4
 // "this pose is angle zero" [ODE-recall dxJointHinge::computeInitialRelativeRotation, from dJointSetHingeAnchor / Axis]
 void take_zero_pose(dJointID j)
 {
-    if (j->type != dJointTypeHinge) return;
+    if (j->type != dJointTypeHinge && j->type != dJointTypeSlider && j->type != dJointTypeFixed) return;
     const dxBody *g1, *g2;
     dmx::Q4<double> q1, q2;
     given_sides(j, g1, g2, q1, q2);
@@ -994,29 +999,27 @@ extern "C" void dJointGetHingeAxis(dJointID j, dVector3 r)
 // ---- a hinge's limit, motor, angle and rate.  dParamLoStop / HiStop / Vel / FMax are honoured (include/dmx_batch.h,
 // dmxBatchSetHingeLimots: fudge factor 1, no bounce, the world's ERP / CFM at the stops); the other parameters say so once each
 // call and are ignored.
-extern "C" void dJointSetHingeParam(dJointID j, int parameter, dReal value)
+static void set_limot_param(dJointID j, const char *fn, int parameter, dReal value)
 {
-    if (!j || j->type != dJointTypeHinge) return;
     const double v = (double)value;
     const bool finite = v > -__builtin_huge_val() && v < __builtin_huge_val();
     switch (parameter) {
     case dParamLoStop: case dParamHiStop:
-        if (v != v) { fprintf(stderr, "libode_mi355: dJointSetHingeParam: a stop that is not a number; ignored\n"); return; }
+        if (v != v) { fprintf(stderr, "libode_mi355: %s: a stop that is not a number; ignored\n", fn); return; }
         (parameter == dParamLoStop ? j->lo_stop : j->hi_stop) = v;
         break;
     case dParamVel: case dParamFMax:
-        if (!finite) { fprintf(stderr, "libode_mi355: dJointSetHingeParam: dParamVel / dParamFMax must be finite; ignored\n"); return; }
+        if (!finite) { fprintf(stderr, "libode_mi355: %s: dParamVel / dParamFMax must be finite; ignored\n", fn); return; }
         (parameter == dParamVel ? j->vel : j->fmax) = v;
         break;
     default:
-        fprintf(stderr, "libode_mi355: dJointSetHingeParam: parameter %d is not supported (dParamLoStop, HiStop, Vel, FMax are); ignored\n", parameter);
+        fprintf(stderr, "libode_mi355: %s: parameter %d is not supported (dParamLoStop, HiStop, Vel, FMax are); ignored\n", fn, parameter);
         return;
     }
     if (j->world) j->world->limot_dirty = true;
 }
-extern "C" dReal dJointGetHingeParam(dJointID j, int parameter)
+static dReal get_limot_param(const dxJoint *j, int parameter)
 {
-    if (!j || j->type != dJointTypeHinge) return 0;
     switch (parameter) {
     case dParamLoStop: return (dReal)j->lo_stop;
     case dParamHiStop: return (dReal)j->hi_stop;
@@ -1025,6 +1028,11 @@ extern "C" dReal dJointGetHingeParam(dJointID j, int parameter)
     default: return 0;
     }
 }
+extern "C" void dJointSetHingeParam(dJointID j, int parameter, dReal value)
+{
+    if (j && j->type == dJointTypeHinge) set_limot_param(j, "dJointSetHingeParam", parameter, value);
+}
+extern "C" dReal dJointGetHingeParam(dJointID j, int parameter) { return j && j->type == dJointTypeHinge ? get_limot_param(j, parameter) : 0; }
 // the hinge axis of the sides as attached, in the world frame: u = R_1 axis1
 static void given_axis(const dxJoint *j, double u[3])
 {
@@ -1069,6 +1077,97 @@ extern "C" void dJointAddHingeTorque(dJointID j, dReal torque)
     const double t = (double)torque;
     if (g1) dBodyAddTorque(const_cast<dxBody *>(g1), (dReal)(t * u[0]), (dReal)(t * u[1]), (dReal)(t * u[2]));
     if (g2) dBodyAddTorque(const_cast<dxBody *>(g2), (dReal)(-t * u[0]), (dReal)(-t * u[1]), (dReal)(-t * u[2]));
+}
+// ---- slider and fixed joints (include/dmx_batch.h, DMX_JOINT_SLIDER / DMX_JOINT_FIXED).  A slider's position, rate, stops, motor
+// and dJointAddSliderForce are those of the sides as attached, as a hinge's angle is.
+extern "C" dJointID dJointCreateSlider(dWorldID w, dJointGroupID g) { return create_art(w, g, dJointTypeSlider); }
+extern "C" dJointID dJointCreateFixed(dWorldID w, dJointGroupID g) { return create_art(w, g, dJointTypeFixed); }
+// the axis in world coordinates; the anchor is body 1's centre (body 2's when body 1 is the world: after the exchange that is
+// dJointGetBody(j, 0) either way); this pose is the zero pose and s = 0
+extern "C" void dJointSetSliderAxis(dJointID j, dReal x, dReal y, dReal z)
+{
+    if (!j || j->type != dJointTypeSlider) return;
+    const double l = sqrt((double)x * x + (double)y * y + (double)z * z);
+    if (!(l > 0)) return;
+    if (j->world) j->world->to_host();
+    const double a[3] = { x / l, y / l, z / l };
+    to_body(j->b1, a, false, j->axis1);
+    to_body(j->b2, a, false, j->axis2);
+    const double p[3] = { j->b1 ? (double)j->b1->pos[0] : 0.0, j->b1 ? (double)j->b1->pos[1] : 0.0, j->b1 ? (double)j->b1->pos[2] : 0.0 };
+    to_body(j->b1, p, true, j->anchor1);
+    to_body(j->b2, p, true, j->anchor2);
+    take_zero_pose(j);
+    if (j->world) j->world->art_dirty = true;
+}
+extern "C" void dJointGetSliderAxis(dJointID j, dVector3 r)
+{
+    if (!j) return;
+    if (j->world) j->world->to_host();
+    to_world(j->b1, j->axis1, false, r);
+}
+extern "C" void dJointSetSliderParam(dJointID j, int parameter, dReal value)
+{
+    if (j && j->type == dJointTypeSlider) set_limot_param(j, "dJointSetSliderParam", parameter, value);
+}
+extern "C" dReal dJointGetSliderParam(dJointID j, int parameter) { return j && j->type == dJointTypeSlider ? get_limot_param(j, parameter) : 0; }
+// s and s_dot of the sides as attached, through the function the device's position kernel and limot row use (slider_position)
+static void slider_state(const dxJoint *j, double &s, double &s_dot)
+{
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    auto v3 = [](const dReal *p) -> dmx::V3<double> { return { (double)p[0], (double)p[1], (double)p[2] }; };
+    auto d3 = [](const double *p) -> dmx::V3<double> { return { p[0], p[1], p[2] }; };
+    const dmx::V3<double> zero = { 0.0, 0.0, 0.0 };
+    dmx::slider_position<double>(g1 != nullptr, g1 ? v3(g1->pos) : zero, q1, g1 ? v3(g1->lvel) : zero, g1 ? v3(g1->avel) : zero,
+                                 g2 != nullptr, g2 ? v3(g2->pos) : zero, q2, g2 ? v3(g2->lvel) : zero, g2 ? v3(g2->avel) : zero,
+                                 d3(j->rev ? j->anchor2 : j->anchor1), d3(j->rev ? j->anchor1 : j->anchor2), d3(j->rev ? j->axis2 : j->axis1), s, s_dot);
+}
+extern "C" dReal dJointGetSliderPosition(dJointID j)
+{
+    if (!j || j->type != dJointTypeSlider || !j->b1) return 0;
+    if (j->world) j->world->to_host();
+    double s, sd;
+    slider_state(j, s, sd);
+    return (dReal)s;
+}
+extern "C" dReal dJointGetSliderPositionRate(dJointID j)
+{
+    if (!j || j->type != dJointTypeSlider || !j->b1) return 0;
+    if (j->world) j->world->to_host();
+    double s, sd;
+    slider_state(j, s, sd);
+    return (dReal)sd;
+}
+// +f u on body 1 and -f u on body 2 (the sides as attached), both at p_2: the limot row's J^T f, so the pair's momentum and angular
+// momentum are untouched
+extern "C" void dJointAddSliderForce(dJointID j, dReal force)
+{
+    if (!j || j->type != dJointTypeSlider || !j->b1) return;
+    if (j->world) j->world->to_host();
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    double u[3];
+    given_axis(j, u);
+    dReal p2[4];
+    to_world(g2, j->rev ? j->anchor1 : j->anchor2, true, p2);
+    for (int side = 0; side < 2; side++) {
+        dxBody *b = const_cast<dxBody *>(side ? g2 : g1);
+        if (!b) continue;
+        const double f = side ? -(double)force : (double)force;
+        const double r[3] = { (double)p2[0] - (double)b->pos[0], (double)p2[1] - (double)b->pos[1], (double)p2[2] - (double)b->pos[2] };
+        dBodyAddForce(b, (dReal)(f * u[0]), (dReal)(f * u[1]), (dReal)(f * u[2]));
+        dBodyAddTorque(b, (dReal)(f * (r[1] * u[2] - r[2] * u[1])), (dReal)(f * (r[2] * u[0] - r[0] * u[2])), (dReal)(f * (r[0] * u[1] - r[1] * u[0])));
+    }
+}
+// welds the two bodies as they are now: the anchor at body 2's centre (body 1's when body 2 is the world), this pose the zero pose
+extern "C" void dJointSetFixed(dJointID j)
+{
+    if (!j || j->type != dJointTypeFixed) return;
+    if (j->world) j->world->to_host();
+    const dxBody *c = (!j->rev && j->b2) ? j->b2 : j->b1;
+    set_anchor(j, c ? c->pos[0] : 0, c ? c->pos[1] : 0, c ? c->pos[2] : 0);
 }
 // is there a joint between the two bodies (dAreConnectedExcluding: one whose type is not joint_type)?
 extern "C" int dAreConnectedExcluding(dBodyID b1, dBodyID b2, int joint_type)
