@@ -219,6 +219,17 @@ int dmxBatchSetElision(dmxBatchID b, int mask);
  * dmxBatchDevicePtr call, and any stepping call made while the batch's stream is being captured into a HIP graph, end it for the
  * batch's lifetime.  Same results bit for bit.  Default on (DMX_ELIDE_LOADS=0 in the environment, read at dmxBatchCreate: off). */
 int dmxBatchSetLoadElision(dmxBatchID b, int on);
+/* Arithmetic the contact-free tick does not need: a body whose torque is exactly zero -- no force accumulators in the launch, no
+ * gyroscopic torque (gyro mode 0, or an isotropic inertia) -- gets w += Iw^-1 (h * 0) = w + (+0) from the general tick, so a launch
+ * whose mass and inertia are uniform (DMX_ELIDE_CONSTANTS active), whose h is finite and positive and whose every 1/I.k is finite
+ * and at most the largest finite number / 1024 steps a wavefront with the short tick, which builds neither the rotation matrix nor
+ * the world-frame inverse inertia, whenever every lane's quaternion has |q.k| <= 2; any other wavefront runs the general tick in the
+ * same kernel (csrc/dmx_torque_free.hpp has the rule).  Same results bit for bit.  Default on (DMX_TORQUE_FREE=0 in the
+ * environment, read at dmxBatchCreate: off -- the launches are then the ones they always were). */
+int dmxBatchSetTorqueFree(dmxBatchID b, int on);
+/* for tests and diagnostics: [0] contact-free launches so far that took a kernel with the short tick built in (the rule said on),
+ * [1] those that took the general kernel.  Which wavefronts of a launch pass the quaternion guard is not counted. */
+int dmxBatchTorqueFreeStats(dmxBatchID b, int64_t out[2]);
 /* for tests and diagnostics, never on a hot path (takes the counts, then settles the batch -- which, like every observer, breaks
  * the chain: that break shows in the next call's count -- and reads the words back): [0] launches that established the
  * words, [1] lean launches, [2] times the chain was broken, [3] 1 once ended for good, [4] / [5] tiles of the active range whose

@@ -24,7 +24,7 @@ BATCH_SYMBOLS = [
     "dmxBatchChunkBegin", "dmxBatchChunkTick", "dmxBatchCheckZonesOnStream", "dmxBatchChunkEnd",
     "dmxBatchChunkCommit", "dmxBatchChunkRollback", "dmxBatchExactTick", "dmxBatchRefreshGhostsOnStream", "dmxBatchSetConvexHull", "dmxBatchChunkTicks", "dmxBatchSetTicksPerLaunch",
     "dmxBatchSetSnapshotMode", "dmxBatchSetStaticBoxes", "dmxBatchSetStepper", "dmxBatchSetConvexHullFaces",
-    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision", "dmxBatchSetLoadElision", "dmxBatchLoadElisionStats",
+    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision", "dmxBatchSetLoadElision", "dmxBatchSetTorqueFree", "dmxBatchTorqueFreeStats", "dmxBatchLoadElisionStats",
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
@@ -109,6 +109,8 @@ def load():
     sig("dmxBatchSetSnapshotMode", I, P, I)
     sig("dmxBatchSetElision", I, P, I)
     sig("dmxBatchSetLoadElision", I, P, I)
+    sig("dmxBatchSetTorqueFree", I, P, I)
+    sig("dmxBatchTorqueFreeStats", I, P, P)
     sig("dmxBatchLoadElisionStats", I, P, P)
     sig("dmxBatchSetExactPipeline", I, P, I)
     sig("dmxBatchSetStaticPath", I, P, I)

@@ -361,6 +361,17 @@ class BatchWorld:
         only while bit 0 of set_elision is on; include/dmx_batch.h).  Same results bit for bit."""
         _check(self.lib.dmxBatchSetLoadElision(self.h, 1 if on else 0), "dmxBatchSetLoadElision")
 
+    def set_torque_free(self, on=True):
+        """contact-free launches with uniform mass / inertia, no force accumulators and no gyroscopic torque take the short tick
+        that builds no rotation matrix and no inverse inertia (default on; include/dmx_batch.h).  Same results bit for bit."""
+        _check(self.lib.dmxBatchSetTorqueFree(self.h, 1 if on else 0), "dmxBatchSetTorqueFree")
+
+    def torque_free_stats(self):
+        """dict: contact-free launches that took a kernel with the short tick built in / the general kernel"""
+        out = (C.c_int64 * 2)()
+        _check(self.lib.dmxBatchTorqueFreeStats(self.h, out), "dmxBatchTorqueFreeStats")
+        return {"short": int(out[0]), "general": int(out[1])}
+
     def load_elision_stats(self):
         """dict: establish / lean launches, chain breaks, ended for good, tiles with x / z fixed.  Settles the batch."""
         out = (C.c_int64 * 6)()

@@ -90,6 +90,8 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
         b->elide = elide_default;
         static const bool loads_default = [] { const char *e = getenv("DMX_ELIDE_LOADS"); return !(e && atoi(e) == 0); }();
         b->fix.on = loads_default;
+        static const bool torque_free_default = [] { const char *e = getenv("DMX_TORQUE_FREE"); return !(e && atoi(e) == 0); }();
+        b->torque_free = torque_free_default;
     }
     b->prof_on = getenv("DMX_HOST_PROFILE") != nullptr;
     {
@@ -404,7 +406,7 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
         P.ticks = ext ? 1 : std::min(per, nsteps - s);
         T *S = (T *)b->slab + slab_ix(0, first);
         const int fix_mode = dmx_fix_next<T>(b, P, first, count, true, ext);
-        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev, fix_mode, b->fix_words));
+        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev, fix_mode, b->fix_words, b->torque_free, b->tf_stats));
         if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
         s += P.ticks;
     }
@@ -491,6 +493,21 @@ extern "C" int dmxBatchSetLoadElision(dmxBatchID b, int on)
     if (!b || (on != 0 && on != 1)) return DMX_EINVAL;
     SETTLE(b);
     b->fix.set_on(on != 0);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetTorqueFree(dmxBatchID b, int on)
+{
+    if (!b || (on != 0 && on != 1)) return DMX_EINVAL;
+    SETTLE(b);
+    b->torque_free = on != 0;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchTorqueFreeStats(dmxBatchID b, int64_t out[2])
+{
+    if (!b || !out) return DMX_EINVAL;
+    out[0] = b->tf_stats[0]; out[1] = b->tf_stats[1];
     return DMX_OK;
 }
 

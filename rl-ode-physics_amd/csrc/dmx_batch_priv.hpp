@@ -110,6 +110,10 @@ struct dmxBatch {
     // axis x, y, z fixed; `fix` says before each contact-free launch whether the words may be used (dmx_fixed.hpp has the rule).
     dmx::FixedChain fix;
     uint32_t *fix_words = nullptr;   // stride / 64 words
+    // integrate_free's short tick of a body without torque (dmxBatchSetTorqueFree; DMX_TORQUE_FREE=0 in the environment switches it
+    // off): dmx_torque_free.hpp decides per launch whether it applies.  Off, the launches are the ones they always were.
+    bool torque_free = true;
+    int64_t tf_stats[2] = { 0, 0 };  // contact-free launches with / without the short tick built in (dmxBatchTorqueFreeStats)
     bool stepped_with_plane = false;
     // general island path (explicit contact joints)
     uint8_t *bflags = nullptr;                 // device, per-slot BF_* flags

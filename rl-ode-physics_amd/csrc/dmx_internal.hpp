@@ -229,9 +229,13 @@ struct StepDiag {
 // dmx_batch_priv.hpp hands out alternating ones); the kernels of ticks with contacts take no notice of it.
 // fix_mode / fix_words: what dmx_fixed.hpp's record said about a contact-free launch (FIX_OFF = 0: the launch it always was),
 // and the batch's word per tile; a launch that does not reach integrate_free must come with FIX_OFF.
+// torque_free: the batch's switch for the short tick of a body without torque (dmx_torque_free.hpp decides per launch whether it
+// applies); off, the launch is the one it always was.  tf_stats: two counters of the caller's, [0] contact-free launches that took an
+// instantiation with the short tick, [1] those that did not (dmxBatchTorqueFreeStats).
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st, int rev, int fix_mode = 0, uint32_t *fix_words = nullptr);
+                       StepDiag *diag, hipStream_t st, int rev, int fix_mode = 0, uint32_t *fix_words = nullptr, bool torque_free = false,
+                       int64_t *tf_stats = nullptr);
 // does launch_step take these parameters to integrate_free (no plane, no static geometry with contact slots)?
 template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
 {

@@ -23,6 +23,7 @@
 #include "dmx_step_fused.hpp"
 #include "dmx_sweep.hpp"
 #include "dmx_fixed.hpp"
+#include "dmx_torque_free.hpp"
 
 namespace dmx {
 
@@ -50,6 +51,19 @@ namespace dmx {
 //              loads nor the ballots and stores of a fixed lateral axis (x, z), tests a clear axis as an establishing launch does
 //              and rewrites a word that changes (-0.0 -> +0.0 clears the bit in the tick where it happens).  The dropped scene
 //              then moves 9 reals in and 6 out = 15 per body-step.  Every other launch is the kernel without FIX, as it always was.
+//   TF         Short tick (dmx_torque_free.hpp has the rule, dmx_step_fused.hpp: free_body_step_torque_free the code): with OPT_UNI and
+//              without EXT the launch's torque can be known to be exactly (+0, +0, +0) -- no accumulators, no gyroscopic torque -- and
+//              then the general tick's w += Iw^-1 (h tacc) is w + (+0) for every finite Iw^-1.  `tf` (scalar arguments of their own,
+//              StepParams does not grow) says whether that holds for this launch and carries hm = h * (1 / m) and mg = m g, computed
+//              once on the host with the tick's own operations.  A launch for which it holds takes the instantiation with TF: a
+//              wavefront whose every active lane has |q.k| <= 2 (one ballot, one scalar branch; per tick in the many-ticks kernel)
+//              builds neither R nor R diag(1/Ib) R^T -- a quarter of the vector instructions the headline's tick executes; any other
+//              wavefront runs tick_head and tick_tail in the same kernel.  A template parameter and not a branch on tf.on alone: the
+//              general tick behind the join costs 18 more vector instructions than free_body_step, which a launch that can never
+//              take the short way measured as 0.3 us per tick at 1 Mi bodies (profiles/ab_torque_free_first_build.txt); every launch with
+//              tf.on = 0 is the kernel without TF, as it always was.  Same bits (tests/test_torque_free.py on the host over
+//              1 Mi bodies per precision, tests/test_gpu_torque_free.py on the device); registers as before
+//              (profiles/torque_free_resources.txt).
 // Sweep order (dmx_sweep.hpp): `rev` -- a scalar argument of its own, StepParams does not grow -- says in which direction this
 // launch walks the tiles; workgroup b works on tile group sweep_block(b, gridDim.x, rev).  The callers alternate it from one
 // contact-free launch to the next, so that the lines the last launch touched last, still in the XCDs' L2s, are read first.  The
@@ -70,12 +84,13 @@ template <class T> __device__ __forceinline__ bool bits_differ(T a, T b)
 // the tile's axis (x, y, z = 0, 1, 2) a state component belongs to for the fixed-axis words: pos and lvel; -1 for quat and avel
 __host__ __device__ constexpr int fix_axis_of(int k) { return k < C_QUAT ? k - C_POS : (k >= C_LVEL && k < C_AVEL) ? k - C_LVEL : -1; }
 
-template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0, bool FIX = false>
+template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0, bool FIX = false, bool TF = false>
 __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P, int rev, int fix_mode,
-                                                            uint32_t *fix_words)
+                                                            uint32_t *fix_words, TorqueFree<T> tf)
 {
     constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
     static_assert(!FIX || (ELIDE && !EXT && !MULTI), "the fixed-axis mode is built into the one-tick kernels with store elision only");
+    static_assert(!TF || (UNI && !EXT), "the short tick needs the constants as arguments and no force accumulators");
     constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
     // So = where the new state goes: S itself (in place) or the batch's other slab (the first launch of a
     // collision-proof chunk, which thereby leaves the chunk's start state behind as the rollback snapshot)
@@ -144,7 +159,12 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
                 facc = { f[0], f[1], f[2] };
                 tacc = { f[3], f[4], f[5] };
             }
-            free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
+            if constexpr (TF) {
+                // the short tick for a wavefront whose every active lane it is proven for, the general one for any other
+                free_body_step_torque_free(x, q, v, w, mass, Ib, P.g, P.h, P.gyro, tf.on, tf.hm, V3<T>{ tf.mg[0], tf.mg[1], tf.mg[2] });
+            } else {
+                free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
+            }
             if (s == nticks - 1) pack_boundary(P, i, x, q, v, w);
             c[C_POS] = x.x; c[C_POS + 1] = x.y; c[C_POS + 2] = x.z;
             c[C_QUAT] = q.w; c[C_QUAT + 1] = q.x; c[C_QUAT + 2] = q.y; c[C_QUAT + 3] = q.z;
@@ -557,7 +577,7 @@ constexpr int64_t kOneLaunchBodies = 256 * 4 * 64;
 
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st, int rev, int fix_mode, uint32_t *fix_words)
+                       StepDiag *diag, hipStream_t st, int rev, int fix_mode, uint32_t *fix_words, bool torque_free, int64_t *tf_stats)
 {
     if (P.n_static > 0 && P.sbuf != nullptr) {
         // bodies at static geometry: narrowphase against the plane and the static boxes, then the fused solve + integrate
@@ -597,17 +617,24 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
         constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
         const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0);
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1, fix_mode, fix_words); };
+        // the short tick of a body without torque (dmx_torque_free.hpp has the rule): on -- the instantiations with TF -- or off, with the
+        // launch's constants
+        const T tf_Ib[3] = { P.uni_inertia.x, P.uni_inertia.y, P.uni_inertia.z }, tf_g[3] = { P.g.x, P.g.y, P.g.z };
+        const TorqueFree<T> tf = torque_free_plan<T>(torque_free, (opt & OPT_UNI) != 0, ext, P.gyro, P.uni_mass, tf_Ib, P.h, tf_g);
+        if (tf_stats != nullptr) tf_stats[tf.on ? 0 : 1]++;      // contact-free launches with / without the short tick built in
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1, fix_mode, fix_words, tf); };
         // an establishing or lean launch (dmx_fixed.hpp; the caller has asked the batch's record) is one of the two instantiations
         // with the fixed-axis mode built in; every other launch is the kernel it always was
         if (fix_mode != FIX_OFF) {
             if (P.ticks > 1 || ext || !(opt & OPT_ELIDE) || fix_words == nullptr || P.skip != nullptr || P.gate != nullptr) return hipErrorInvalidValue;
             // a lean launch has not loaded every pos.x / pos.z: it cannot fill another slab, test safe zones or pack the boundary
             if (fix_mode == FIX_LEAN && (So != S || P.bp_check != 0 || P.pack_out != nullptr)) return hipErrorInvalidValue;
-            if (opt == 3) launch(integrate_free<T, false, MWU, false, 3, true>);
+            if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, true, true>);
+            else if (opt == 3) launch(integrate_free<T, false, MWU, false, 3, true>);
             else launch(integrate_free<T, false, 1, false, 1, true>);
         } else if (P.ticks > 1) {
-            if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
+            if ((opt & OPT_UNI) && tf.on) launch(integrate_free<T, false, 1, true, OPT_UNI, false, true>);
+            else if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
             else launch(integrate_free<T, false, 1, true, 0>);
         } else if (ext) {
             if (opt == 3) launch(integrate_free<T, true, 1, false, 3>);
@@ -615,7 +642,9 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
             else if (opt == 1) launch(integrate_free<T, true, 1, false, 1>);
             else launch(integrate_free<T, true, 1, false, 0>);
         } else {
-            if (opt == 3) launch(integrate_free<T, false, MWU, false, 3>);
+            if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, false, true>);
+            else if (opt == 2 && tf.on) launch(integrate_free<T, false, MWU, false, 2, false, true>);
+            else if (opt == 3) launch(integrate_free<T, false, MWU, false, 3>);
             else if (opt == 2) launch(integrate_free<T, false, MWU, false, 2>);
             else if (opt == 1) launch(integrate_free<T, false, 1, false, 1>);
             else launch(integrate_free<T, false, 1, false, 0>);
@@ -718,7 +747,7 @@ hipError_t launch_soa_to_aos(const T *S, int64_t stride, int comp0, int k, int64
 
 #define DMX_INSTANTIATE(T)                                                                                         \
     template hipError_t launch_step<T>(T *, T *, const uint8_t *, int64_t, int64_t, const StepParams<T> &, bool,   \
-                                       StepDiag *, hipStream_t, int, int, uint32_t *);                                            \
+                                       StepDiag *, hipStream_t, int, int, uint32_t *, bool, int64_t *);                                      \
     template hipError_t launch_pack_transforms<T>(const T *, int64_t, int64_t, int64_t, T *, hipStream_t);         \
     template hipError_t launch_gather<T>(const T *, int64_t, const int32_t *, int64_t, T *, hipStream_t);          \
     template hipError_t launch_scatter<T>(T *, int64_t, const int32_t *, int64_t, const T *, hipStream_t);         \
@@ -746,6 +775,8 @@ hipError_t dmx_touch_kernels(int real_bytes)
         touch((const void *)&integrate_free<float, false, 1, false>);
         touch((const void *)&integrate_free<float, false, 7, false, 3>);
         touch((const void *)&integrate_free<float, false, 7, false, 3, true>);
+        touch((const void *)&integrate_free<float, false, 7, false, 3, false, true>);
+        touch((const void *)&integrate_free<float, false, 7, false, 3, true, true>);
         touch((const void *)&step_plane<float, false, 2, 4>);
         touch((const void *)&step_contacts<float, false, 1, 8, true>);
         touch((const void *)&check_zones<float>);
@@ -754,6 +785,8 @@ hipError_t dmx_touch_kernels(int real_bytes)
         touch((const void *)&integrate_free<double, false, 1, false>);
         touch((const void *)&integrate_free<double, false, 1, false, 3>);
         touch((const void *)&integrate_free<double, false, 1, false, 3, true>);
+        touch((const void *)&integrate_free<double, false, 1, false, 3, false, true>);
+        touch((const void *)&integrate_free<double, false, 1, false, 3, true, true>);
         touch((const void *)&step_plane<double, false, 1, 4>);
         touch((const void *)&step_contacts<double, false, 1, 8, true>);
         touch((const void *)&check_zones<double>);

@@ -199,6 +199,30 @@ template <class T> DMX_HD void integrate_quat(Q4<T> &q, const V3<T> &w, T h)
     normalize(q);
 }
 
+// The last statements of every body's tick: v += hm f ; w += dw ; x += h v ; q += h/2 (0,w) q, renormalised.  The general tick
+// (dmx_step_fused.hpp: tick_tail) comes here with hm = h * (1 / m), f = the force accumulator and dw = Iw^-1 (h tacc).
+template <class T> DMX_HD void tick_integrate(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T hm, const V3<T> &f, const V3<T> &dw, T h)
+{
+    v.x = fma_(hm, f.x, v.x); v.y = fma_(hm, f.y, v.y); v.z = fma_(hm, f.z, v.z);
+    w.x += dw.x; w.y += dw.y; w.z += dw.z;
+    x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
+    integrate_quat(q, w, h);
+}
+// The tick of a body without rows and without torque (dmx_torque_free.hpp has the rule and the proof): hm = h * (1 / m) and
+// mg.k = fma(m, g.k, 0) are the general tick's own values, computed once per launch; dw = (+0, +0, +0) is what the general tick's
+// Iw^-1 (h * (+0, +0, +0)) comes to for a finite Iw^-1 (w + (+0) turns -0 into +0 and quiets a signalling NaN: the add stays).
+template <class T> DMX_HD void torque_free_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T hm, const V3<T> &mg, T h)
+{
+    tick_integrate(x, q, v, w, hm, mg, V3<T>{ T(0), T(0), T(0) }, h);
+}
+// ... and the bodies it is proven for: |q.k| <= 2 in all four components, so that quat_to_R is finite (entries <= 17).  A NaN fails.
+DMX_HD float  fabs_(float x)  { return __builtin_fabsf(x); }
+DMX_HD double fabs_(double x) { return __builtin_fabs(x); }
+template <class T> DMX_HD bool torque_free_admits(const Q4<T> &q)
+{
+    return fabs_(q.w) <= T(2) && fabs_(q.x) <= T(2) && fabs_(q.y) <= T(2) && fabs_(q.z) <= T(2);
+}
+
 // two unit vectors orthogonal to unit n and to each other
 template <class T> DMX_HD void plane_space(const V3<T> &n, V3<T> &p, V3<T> &q)
 {

@@ -82,18 +82,45 @@ __device__ __forceinline__ void tick_head(const Q4<T> &q, const V3<T> &w, T mass
     }
 }
 
-// v += h M^-1 f ; w += Iw^-1 (h tacc) ; integrate
+// what the tail adds: hm = h / m, by which facc enters v, and dw = Iw^-1 (h tacc), which enters w
+template <class T>
+__device__ __forceinline__ void tick_tail_terms(T invMass, const M3<T> &invIw, V3<T> tacc, T h, T &hm, V3<T> &dw)
+{
+    hm = h * invMass;
+    tacc.x *= h; tacc.y *= h; tacc.z *= h;
+    dw = mulv(invIw, tacc);
+}
+
+// v += h M^-1 f ; w += Iw^-1 (h tacc) ; integrate (dmx_math.hpp: tick_integrate, which the host can compile)
 template <class T>
 __device__ __forceinline__ void tick_tail(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T invMass, const M3<T> &invIw,
                                           const V3<T> &facc, V3<T> tacc, T h)
 {
-    const T hm = h * invMass;
-    v.x = fma_(hm, facc.x, v.x); v.y = fma_(hm, facc.y, v.y); v.z = fma_(hm, facc.z, v.z);
-    tacc.x *= h; tacc.y *= h; tacc.z *= h;
-    const V3<T> dw = mulv(invIw, tacc);
-    w.x += dw.x; w.y += dw.y; w.z += dw.z;
-    x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
-    integrate_quat(q, w, h);
+    T hm;
+    V3<T> dw;
+    tick_tail_terms(invMass, invIw, tacc, h, hm, dw);
+    tick_integrate(x, q, v, w, hm, facc, dw, h);
+}
+
+// A body without rows in a launch that may take the short tick (dmx_torque_free.hpp has the rule, dmx_math.hpp the proof's guard):
+// for a wavefront whose every active lane has |q.k| <= 2 the tail's dw is (+0, +0, +0), and hm and facc are the launch's tf_hm and
+// tf_mg, computed once on the host with the head's and the tail's operations; neither R nor the inverse inertia is built.  Any other wavefront runs
+// head and tail as free_body_step does.  One ballot and one scalar branch; both ways meet in the one tick_integrate, which keeps the
+// kernels at the registers they had (profiles/torque_free_resources.txt).
+template <class T>
+__device__ __forceinline__ void free_body_step_torque_free(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T mass, const V3<T> &Ib,
+                                                           const V3<T> &g, T h, int gyro, int tf_on, T tf_hm, const V3<T> &tf_mg)
+{
+    T hm = tf_hm;
+    V3<T> facc = tf_mg, dw = { T(0), T(0), T(0) };
+    if (!(tf_on && __ballot(!torque_free_admits(q)) == 0ull)) {
+        M3<T> invIw;
+        V3<T> tacc = { T(0), T(0), T(0) };
+        facc = { T(0), T(0), T(0) };
+        tick_head(q, w, mass, Ib, facc, tacc, g, h, gyro, invIw);
+        tick_tail_terms(T(1) / mass, invIw, tacc, h, hm, dw);
+    }
+    tick_integrate(x, q, v, w, hm, facc, dw, h);
 }
 
 // a body without rows: head and tail, nothing between them
