@@ -474,6 +474,34 @@ int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate);
  * inactive joints report 0); either array may be NULL */
 int dmxBatchSliderPositions(dmxBatchID b, double *pos, double *rate);
 
+/* ---- feedback: the force and torque every joint and contact joint applied in the last tick (dJointSetFeedback).
+ * A constraint with rows r = 0..m-1 in canonical sides has, per row, the Jacobian J_r = [ Jl1, Ja1 | Jl2, Ja2 ] at the tick's start,
+ * unscaled, as the definitions above give it, and the multiplier lambda_r as the solve left it, after clamping -- a force: both
+ * steppers solve A lambda = c/h - J (v/h + M^-1 f).  Its feedback is
+ *     f1 = sum lambda_r Jl1_r,  t1 = sum lambda_r Ja1_r,  f2 = sum lambda_r Jl2_r,  t2 = sum lambda_r Ja2_r:
+ * the force and the torque about each body's centre that the constraint applied to body 1 and body 2 during the tick.
+ *   sides      as the caller gave them: an internal exchange of sides swaps the pairs back (as the angle and position getters do).
+ *   world      a world side reports zeros.   kinematic: a kinematic side reports its J^T lambda like any other (its block of J
+ *              exists although its inverse mass is zero).
+ *   joints     a joint's feedback is the sum over all its units (a slider: lock + linear + limot).  At a stop the limot row's
+ *              lambda includes the motor's shifted bound g: it is reported as part of the joint, as the row is defined.  Force or
+ *              torque added to the bodies' accumulators by hand is no part of it.
+ *   contacts   the normal row and, when mu > 0, the two friction rows.
+ *   zeros      inactive joints, and contact joints the stepper dropped (no live dynamic body, or twice the same body).
+ * Off by default; off, every tick stages, launches and stores exactly what it does without this section.  On, every
+ * dmxBatchStepJoints tick leaves its feedback on the device (one more small launch on the general path, none in the single-launch
+ * tick, which writes it to host-mapped memory); the bodies' state is bit-identical with it on and off.  The getters return
+ * DMX_EINVAL with one line on stderr while feedback is off, before the first dmxBatchStepJoints tick made with it on, after any
+ * other tick or write of body state (dmxBatchStep and its siblings produce none), after dmxBatchSetJoints (the last tick's
+ * feedback belongs to the joints of the old set), and for an n that does not match: nothing stale is ever returned. */
+typedef struct dmxJointFeedback { double f1[3], t1[3], f2[3], t2[3]; } dmxJointFeedback;
+int dmxBatchSetFeedback(dmxBatchID b, int on);                        /* default 0 */
+int dmxBatchJointFeedback(dmxBatchID b, dmxJointFeedback *out);       /* one per joint of the set */
+/* one per contact joint of the last dmxBatchStepJoints tick, in the order given; n must equal that tick's n_joints */
+int dmxBatchContactFeedback(dmxBatchID b, int64_t n, dmxJointFeedback *out);
+/* device arrays of 12 reals per entry (f1, t1, f2, t2) in the batch's precision, valid until the next tick; either may be NULL */
+int dmxBatchFeedbackDevice(dmxBatchID b, const void **joints_dev, const void **contacts_dev);
+
 /* per-body flags for the island path: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes */
 enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };
 int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64_t first, int64_t count);

@@ -239,6 +239,17 @@ void dJointSetSliderParam(dJointID, int parameter, dReal value);
 dReal dJointGetSliderParam(dJointID, int parameter);
 void dJointAddSliderForce(dJointID, dReal force);
 void dJointSetFixed(dJointID);
+/* The force and torque a joint applied to its two bodies during the last dWorldStep / dWorldQuickStep, about each body's centre,
+ * in world coordinates (ODE's layout and meaning; include/dmx_batch.h at dmxBatchSetFeedback has the definition).  The struct is
+ * the caller's; a step fills it before it returns, for ball, hinge, slider and fixed joints and for contact joints created in the
+ * near callback.  f1 / t1 belong to dJointGetBody(j, 0) and f2 / t2 to dJointGetBody(j, 1) -- after dJointAttach(j, 0, body) on an
+ * articulation joint that is the body and the world; a side without a body reports zeros, a kinematic body its share.  A joint
+ * that took no part in the step (a side destroyed, both sides the same) reports zeros.  Force or torque added by hand
+ * (dJointAddHingeTorque, dJointAddSliderForce) is no part of it.  dJointSetFeedback(j, 0) forgets the struct; dJointDestroy and
+ * dJointGroupEmpty do so too.  A world none of whose joints has a struct steps exactly as it does without this. */
+typedef struct dJointFeedback { dVector3 f1, t1, f2, t2; } dJointFeedback;
+void dJointSetFeedback(dJointID, dJointFeedback *);
+dJointFeedback *dJointGetFeedback(dJointID);
 int dAreConnected(dBodyID, dBodyID);
 int dAreConnectedExcluding(dBodyID body1, dBodyID body2, int joint_type);
 

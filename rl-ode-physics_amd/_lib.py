@@ -28,6 +28,7 @@ BATCH_SYMBOLS = [
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
+    "dmxBatchSetFeedback", "dmxBatchJointFeedback", "dmxBatchContactFeedback", "dmxBatchFeedbackDevice",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -145,5 +146,9 @@ def load():
     sig("dmxBatchHingeLimotInit", I, P, P, P)
     sig("dmxBatchHingeAngles", I, P, P, P)
     sig("dmxBatchSliderPositions", I, P, P, P)
+    sig("dmxBatchSetFeedback", I, P, I)
+    sig("dmxBatchJointFeedback", I, P, P)
+    sig("dmxBatchContactFeedback", I, P, L, P)
+    sig("dmxBatchFeedbackDevice", I, P, C.POINTER(P), C.POINTER(P))
     _lib = lib
     return lib

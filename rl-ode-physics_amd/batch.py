@@ -214,6 +214,7 @@ class BatchWorld:
         j = np.ascontiguousarray(np.asarray(joints).astype(CONTACT_JOINT_DTYPE, copy=False))
         _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
                "dmxBatchStepJoints")
+        self._last_n_joints = int(j.shape[0])
 
     # -- articulation joints: ball, hinge, slider and fixed (dJointCreateBall / Hinge / Slider / Fixed), a set that persists
     #    between ticks --
@@ -276,6 +277,33 @@ class BatchWorld:
         s, rate = np.zeros(n), np.zeros(n)
         _check(self.lib.dmxBatchSliderPositions(self.h, s.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchSliderPositions")
         return s, rate
+
+    # -- feedback: what every joint and contact joint applied in the last tick (dJointSetFeedback) --
+    def set_feedback(self, on):
+        """on: every later step_joints tick leaves the force and torque each joint and contact joint applied (default off)"""
+        _check(self.lib.dmxBatchSetFeedback(self.h, int(bool(on))), "dmxBatchSetFeedback")
+
+    def joint_feedback(self):
+        """-> [n, 4, 3] float64: f1, t1, f2, t2 per joint of the set, in the sides as given (include/dmx_batch.h)"""
+        n = self.joint_count()
+        out = np.zeros((n, 4, 3))
+        _check(self.lib.dmxBatchJointFeedback(self.h, out.ctypes.data if n else None), "dmxBatchJointFeedback")
+        return out
+
+    def contact_feedback(self, n=None):
+        """-> [n, 4, 3] float64: f1, t1, f2, t2 per contact joint of the last step_joints tick, in the order given; n = how
+        many that tick was given (default: what this object's last step_joints call was given)"""
+        n = int(getattr(self, "_last_n_joints", 0) if n is None else n)
+        out = np.zeros((n, 4, 3))
+        _check(self.lib.dmxBatchContactFeedback(self.h, n, out.ctypes.data if n else None), "dmxBatchContactFeedback")
+        return out
+
+    def feedback_device(self):
+        """-> (joints, contacts): device addresses of the last tick's feedback, 12 reals per entry in the batch's precision,
+        valid until the next tick"""
+        a, c = C.c_void_p(), C.c_void_p()
+        _check(self.lib.dmxBatchFeedbackDevice(self.h, C.byref(a), C.byref(c)), "dmxBatchFeedbackDevice")
+        return a.value, c.value
 
     def set_stepper(self, stepper):
         """STEPPER_QUICK (dWorldQuickStep, default) / STEPPER_EXACT (dWorldStep) for step_joints"""

@@ -2,7 +2,8 @@
 // (dmxBatchSetJoints), a joint from world-frame anchor and axis at the bodies' current poses (dmxBatchJointFromWorld), and the
 // joints' position / axis errors from the current state, computed on the device (dmxBatchJointErrors); the hinges' limits and
 // motors (dmxBatchSetHingeLimots, dmxBatchHingeLimotInit) and their angles and rates, computed on the device (dmxBatchHingeAngles),
-// and the sliders' positions and rates (dmxBatchSliderPositions).
+// and the sliders' positions and rates (dmxBatchSliderPositions); the feedback of a tick's joints and contact joints (dmxBatchSetFeedback,
+// dmxBatchJointFeedback, dmxBatchContactFeedback, dmxBatchFeedbackDevice) and the general path's kernel for it.
 // The rows themselves are built by joint_unit_rows (dmx_island_rows.hpp) inside the island kernels; the host side of a tick is in
 // dmx_joints.cpp.
 #include <hip/hip_runtime.h>
@@ -144,7 +145,103 @@ __global__ __launch_bounds__(256) void slider_positions(const T *__restrict__ S,
     if (rate != nullptr) rate[k] = (double)sd;
 }
 
+// Feedback on the general path, behind the tick's solves on the tick's stream: one lane per entry of the contact arrays; the lane
+// of a joint's first entry sums the joint's entries (they are adjacent), puts the sides back as given and writes the joint's 12
+// reals.  Reads the row table and the tick's tables, writes F.fb; no atomics.  (The single-launch tick calls the same
+// joint_feedback from inside its one kernel.)
+template <class T>
+__global__ __launch_bounds__(256) void joint_feedback_rows(IslandSet<T> I, StepParams<T> P, FeedbackSet<T> F, int n_entries)
+{
+    const int d = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (d >= n_entries) return;
+    const int o = F.out[d];
+    if (o < 0) return;
+    const T *rows = I.rows + (size_t)I.row_off[F.isl[d]] * RW_COUNT;
+    T out[12];
+    joint_feedback(I, P, rows, d, F.info[d], F.mode == FB_SCALED, out);
+#pragma unroll
+    for (int j = 0; j < 12; j++) F.fb[(size_t)12 * o + j] = out[j];
+}
+
+template <class T>
+hipError_t launch_feedback(const IslandSet<T> &I, const StepParams<T> &P, const FeedbackSet<T> &F, int n_entries, hipStream_t st)
+{
+    if (n_entries <= 0 || F.mode == FB_OFF) return hipSuccess;
+    hipLaunchKernelGGL((joint_feedback_rows<T>), dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, st, I, P, F, n_entries);
+    return hipGetLastError();
+}
+template hipError_t launch_feedback<float>(const IslandSet<float> &, const StepParams<float> &, const FeedbackSet<float> &, int, hipStream_t);
+template hipError_t launch_feedback<double>(const IslandSet<double> &, const StepParams<double> &, const FeedbackSet<double> &, int, hipStream_t);
+
 }  // namespace dmx
+
+extern "C" int dmxBatchSetFeedback(dmxBatchID b, int on)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if ((on != 0) != b->fb_on) b->fb_valid = false;        // (switched on: no tick yet; switched off: nothing to serve)
+    b->fb_on = on != 0;
+    return DMX_OK;
+}
+
+// what the getters share: may the last tick's feedback be served at all?
+static int feedback_ready(dmxBatch *b, const char *who)
+{
+    const char *why = !b->fb_on ? "feedback is off (dmxBatchSetFeedback)"
+                    : !b->fb_valid ? "no dmxBatchStepJoints tick made with feedback on has run since the last other tick or dmxBatchSetJoints" : nullptr;
+    if (why) { fprintf(stderr, "libode_mi355: %s: %s\n", who, why); return DMX_EINVAL; }
+    return DMX_OK;
+}
+static int feedback_fetch(dmxBatch *b, int64_t first, int64_t count, dmxJointFeedback *out)
+{
+    if (count == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));              // (the small tick's one wait, or the general path's kernel)
+    const size_t rs = b->rsize;
+    const void *src = b->fb_host ? (const void *)((const char *)b->fb_host + (size_t)12 * first * rs) : nullptr;
+    if (!src) {
+        b->fb_tmp.resize((size_t)12 * count * rs);
+        HIP_TRY(hipMemcpy(b->fb_tmp.data(), (const char *)b->fb_devp + (size_t)12 * first * rs, (size_t)12 * count * rs, hipMemcpyDeviceToHost));
+        src = b->fb_tmp.data();
+    }
+    double *o = (double *)out;
+    static_assert(sizeof(dmxJointFeedback) == 12 * sizeof(double), "12 doubles, no padding");
+    if (b->precision == DMX_F32) for (int64_t k = 0; k < 12 * count; k++) o[k] = (double)((const float *)src)[k];
+    else memcpy(o, src, (size_t)12 * count * sizeof(double));
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchJointFeedback(dmxBatchID b, dmxJointFeedback *out)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    { const int rc = feedback_ready(b, "dmxBatchJointFeedback"); if (rc != DMX_OK) return rc; }
+    if (b->fb_nj > 0 && !out) return DMX_EINVAL;
+    return feedback_fetch(b, 0, b->fb_nj, out);
+}
+
+extern "C" int dmxBatchContactFeedback(dmxBatchID b, int64_t n, dmxJointFeedback *out)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    { const int rc = feedback_ready(b, "dmxBatchContactFeedback"); if (rc != DMX_OK) return rc; }
+    if (n != b->fb_nc) {
+        fprintf(stderr, "libode_mi355: dmxBatchContactFeedback: n = %lld, but the last tick was given %lld contact joints\n", (long long)n, (long long)b->fb_nc);
+        return DMX_EINVAL;
+    }
+    if (n > 0 && !out) return DMX_EINVAL;
+    return feedback_fetch(b, b->fb_nj, n, out);
+}
+
+extern "C" int dmxBatchFeedbackDevice(dmxBatchID b, const void **joints_dev, const void **contacts_dev)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    { const int rc = feedback_ready(b, "dmxBatchFeedbackDevice"); if (rc != DMX_OK) return rc; }
+    if (joints_dev) *joints_dev = b->fb_devp;
+    if (contacts_dev) *contacts_dev = (const char *)b->fb_devp + (size_t)12 * b->fb_nj * b->rsize;
+    return DMX_OK;
+}
 
 extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints)
 {
@@ -154,6 +251,7 @@ extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints
     { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
     b->art.assign(joints, joints + n);
     b->limot.clear();                    // (they were entries of the old set's joints)
+    b->fb_valid = false;                 // (so was the last tick's feedback: fb_nj of them, not joint_count())
     return DMX_OK;
 }
 

@@ -208,6 +208,15 @@ struct dmxBatch {
     // the hinges' limits and motors (dmxBatchSetHingeLimots): empty, or one entry per joint of `art`
     std::vector<dmxHingeLimot> limot;
     DevBuf limot_dev;
+    // feedback (dmxBatchSetFeedback): fb_valid = the last tick was a dmxBatchStepJoints tick made with it on (every other writer of
+    // body state clears it: dmx_state_stepped); 12 reals per result in the batch's precision, the set's joints first, then the
+    // tick's contact joints: on the device at fb_devp -- fb_dev on the general path, behind a small tick's tables in its host-mapped
+    // staging otherwise, where fb_host is the host's address of the same memory
+    bool fb_on = false, fb_valid = false;
+    int64_t fb_nj = 0, fb_nc = 0;
+    DevBuf fb_dev;
+    const void *fb_devp = nullptr, *fb_host = nullptr;
+    std::vector<char> fb_tmp;
     int64_t last_units = 0;                        // units the last dmxBatchStepJoints tick carried among its contact entries
 };
 inline bool dmx_limot_present(const dmxHingeLimot &l) { return dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax); }
@@ -239,7 +248,7 @@ inline void dmx_note_capture(dmxBatch *b)
 }
 // a stepping call of the C ABI is about to advance the bodies: what dmx_state_written does, but the fixed-axis chain stands --
 // the launches themselves tell the record what they are (dmx_fix_next)
-inline void dmx_state_stepped(dmxBatch *b) { b->sm_mirror_valid = false; b->state_version++; }
+inline void dmx_state_stepped(dmxBatch *b) { b->sm_mirror_valid = false; b->state_version++; b->fb_valid = false; }
 // called by everything else that changes body state in the slab other than the single-launch tick
 inline void dmx_state_written(dmxBatch *b) { dmx_state_stepped(b); b->fix.brk(); }
 

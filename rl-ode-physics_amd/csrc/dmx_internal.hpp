@@ -93,6 +93,20 @@ template <class T> struct IslandSet {
     // cmu = UNIT_*_MU; within an island they come before its contacts.  0: contacts only
     int has_units = 0;
 };
+// dmxBatchSetFeedback: what a tick made with feedback on carries beside its IslandSet.  Such a tick launches the island kernels'
+// FB instantiations (launch_islands, launch_small_tick), which are kernels of their own: a tick without feedback runs the code
+// it would run if feedback did not exist, and takes no FeedbackSet's worth of arguments it never reads into account.
+// mode: FB_UNSCALED: the rows' J is as built (dWorldStep's solves); FB_SCALED: row_setup<T, true, true> multiplied it by Ad and
+// left Ad in the row's slot RW_UNSCALE.  Per entry of the contact arrays: out = the result's index (a joint of the set: its
+// index; a contact joint: the set's size + its index in the caller's list) when the entry is the first of its joint, else -1;
+// info = 2 x (entries of the joint, which are adjacent) + (1: the sides were exchanged); isl = the entry's island (read by the
+// general path's kernel only).  fb: 12 reals per result (f1, t1, f2, t2 in the sides as given), zeroed before the tick.
+enum : int { FB_OFF = 0, FB_UNSCALED = 1, FB_SCALED = 2 };
+template <class T> struct FeedbackSet {
+    int mode = FB_OFF;
+    const int *out = nullptr, *info = nullptr, *isl = nullptr;
+    T *fb = nullptr;
+};
 // a unit's marker in IslandSet::cmu: a negative number (for the first three minus the row count; a contact's mu is never negative there when has_units is set)
 // (UNIT_LIMOT: a hinge's limit / motor row, dmxBatchSetHingeLimots -- the one unit whose row can clamp)
 // (UNIT_LOCK: the three angular rows of a slider or a fixed joint; UNIT_SLIDER2: a slider's two linear rows; UNIT_SLIMOT: a slider's
@@ -243,7 +257,10 @@ template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
 }
 template <class T>
 hipError_t launch_islands(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
-                          StepDiag *diag, hipStream_t st);
+                          StepDiag *diag, hipStream_t st, bool feedback = false);      // (feedback: the kernels' FB instantiations)
+// feedback of a dmxBatchStepJoints tick on the general path (dmx_artic.hip): one lane per entry, behind the tick's solves
+template <class T>
+hipError_t launch_feedback(const IslandSet<T> &I, const StepParams<T> &P, const FeedbackSet<T> &F, int n_entries, hipStream_t st);
 // dWorldStep: solve_islands for the islands without rows only (those with rows: launch_lcp_lds / lcp_grid_solve, dmx_lcp.hpp)
 template <class T>
 hipError_t launch_islands_without_rows(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,

@@ -14,6 +14,8 @@ namespace dmx {
 //  16-byte pieces -- eight requests that touch one line instead of 29 that touch two: a large island's sweeps are bound by how many
 //  cache-line look-ups its lanes' scattered rows cost the compute unit's one L1, see row_load)
 enum : int { RW_J = 0, RW_IMJ = 12, RW_RHS = 24, RW_AD = 25, RW_LO = 26, RW_HI = 27, RW_LAM = 28, RW_COUNT = ISLAND_ROW_REALS };
+// the first of the three spare reals: in a tick made with feedback on (the FB instantiations) QuickStep's row_setup leaves the factor Ad it scaled J by here
+enum : int { RW_UNSCALE = 29 };
 static_assert(RW_COUNT >= 29 && RW_COUNT % 4 == 0, "a row is read in 16-byte pieces");
 // per island-body scratch layout (reals)
 enum : int { BW_INVI = 0, BW_FACC = 9, BW_TACC = 12, BW_INVM = 15, BW_FC = 16, BW_TMP = 22, BW_COUNT = 28 };
@@ -21,7 +23,7 @@ enum : int { BW_INVI = 0, BW_FACC = 9, BW_TACC = 12, BW_INVM = 15, BW_FC = 16, B
 // (host too: tests/harness/joint_rows_harness.cpp runs joint_unit_rows on the CPU)
 template <class T> DMX_HD V3<T> ld3(const T *p) { return { p[0], p[1], p[2] }; }
 template <class T> DMX_HD void st3(T *p, const V3<T> &v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
-template <class T> __device__ __forceinline__ T dot3p(const T *a, const V3<T> &b) { return fma_(a[2], b.z, fma_(a[1], b.y, a[0] * b.x)); }
+template <class T> DMX_HD T dot3p(const T *a, const V3<T> &b) { return fma_(a[2], b.z, fma_(a[1], b.y, a[0] * b.x)); }
 template <class T> DMX_HD V3<T> ldS(const T *S, int64_t stride, int c0, int s)
 {
     return { S[slab_ix(c0 + 0, s)], S[slab_ix(c0 + 1, s)], S[slab_ix(c0 + 2, s)] };
@@ -513,8 +515,11 @@ __device__ __forceinline__ void body_tmp(const T *S, int64_t stride, T *b, int s
 
 // ---- row i: rhs = c/h - J (v/h + M^-1 f); cfm /= h; iMJ = M^-1 J^T; Ad = w/(J iMJ + cfm); J *= Ad; rhs *= Ad; Ad *= cfm
 // SOR = false (the exact solve of dWorldStep): stop after iMJ -- J and rhs stay unscaled, row[RW_AD] = cfm / h
-template <class T, bool SOR = true>
-__device__ __forceinline__ void row_setup(T *rows, const int *jb, const T *bs, int i, T hinv, T sor_w)
+// FB (a launch made with feedback on: its own instantiation, so that the others are compiled as if it did not exist): the scaled form
+// also stores Ad in the spare slot RW_UNSCALE, for entry_feedback
+// (host too: tests/harness/feedback_rows_harness.cpp)
+template <class T, bool SOR = true, bool FB = false>
+DMX_HD void row_setup(T *rows, const int *jb, const T *bs, int i, T hinv, T sor_w)
 {
     T *row = rows + (size_t)i * RW_COUNT;
     T *J = row + RW_J, *iMJ = row + RW_IMJ;
@@ -550,6 +555,36 @@ __device__ __forceinline__ void row_setup(T *rows, const int *jb, const T *bs, i
     for (int j = 0; j < 12; j++) J[j] *= ad;
     row[RW_RHS] *= ad;
     row[RW_AD] = ad * cfm;
+    if (FB) row[RW_UNSCALE] = ad;
+}
+
+// ---- feedback (dmxBatchSetFeedback; the definition: include/dmx_batch.h) ---------------------------------------------------------
+// acc[0..12) += sum over the rows of entry ci (a contact, or a unit of an articulation joint) of lambda_r J_r, J_r as the builders
+// made it: [Jl1, Ja1 | Jl2, Ja2] in the entry's own (canonical) sides.  rows = the island's rows; the entry's first row is
+// crow[ci], its row count comes from its kind.  scaled: the rows went through QuickStep's row_setup<T, true, FB = true> -- J holds J Ad
+// and RW_UNSCALE holds Ad, so lambda_r J_r = (lambda_r / Ad) (J_r Ad).  Neither M^-1 J^T (zero for a kinematic body) nor
+// RW_AD (Ad cfm: cfm may be zero) could give J back.  A world side's block is zero as built.
+template <class T>
+DMX_HD void entry_feedback(const IslandSet<T> &I, const StepParams<T> &P, const T *rows, int ci, bool scaled, T *acc)
+{
+    const T mu = I.cmu != nullptr ? I.cmu[ci] : P.mu;
+    const int n = (I.has_units && mu < 0) ? unit_rows_of(mu) : (mu > 0 ? 3 : 1);
+    const T *row = rows + (size_t)I.crow[ci] * RW_COUNT;
+    for (int r = 0; r < n; r++, row += RW_COUNT) {
+        const T l = scaled ? row[RW_LAM] / row[RW_UNSCALE] : row[RW_LAM];
+        for (int j = 0; j < 12; j++) acc[j] = fma_(l, row[RW_J + j], acc[j]);
+    }
+}
+// The feedback of the joint whose first entry is ci: the sum over its entries (info >> 1 of them, adjacent), in the sides AS GIVEN
+// (info & 1: the entry's sides are the given ones exchanged) -> out[0..12) = f1, t1, f2, t2.
+template <class T>
+DMX_HD void joint_feedback(const IslandSet<T> &I, const StepParams<T> &P, const T *rows, int ci, int info, bool scaled, T *out)
+{
+    T acc[12];
+    for (int j = 0; j < 12; j++) acc[j] = T(0);
+    for (int u = 0; u < (info >> 1); u++) entry_feedback(I, P, rows, ci + u, scaled, acc);
+    const int sw = (info & 1) ? 6 : 0;
+    for (int j = 0; j < 6; j++) { out[j] = acc[j + sw]; out[6 + j] = acc[6 + j - sw]; }
 }
 
 // ---- one SOR row update; returns |delta lambda| -----------------------------------------------------------------

@@ -303,7 +303,9 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
 }
 
 // ================================================================================ one lane per island
-template <class T>
+// FB: a tick made with feedback on (dmxBatchSetFeedback) -- row_setup also leaves what entry_feedback needs.  An instantiation of
+// its own, here and in solve_island_wg_body, so that a tick without feedback runs the code it ran before feedback existed.
+template <class T, bool FB = false>
 __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                    int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                    StepDiag *__restrict__ diag, int isl)
@@ -328,7 +330,7 @@ __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint
     double resid = 0.0;
     if (m > 0) {
         for (int k = 0; k < nb; k++) body_tmp(S, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], hinv);
-        for (int i = 0; i < m; i++) row_setup(rows, jb, bs, i, hinv, P.sor_w);
+        for (int i = 0; i < m; i++) row_setup<T, true, FB>(rows, jb, bs, i, hinv, P.sor_w);
         for (int it = 0; it < P.iters; it++) {
             const bool last = (it == P.iters - 1);
             const int *ord = I.order != nullptr ? I.order + (size_t)(it >> 3) * I.order_stride + r0 : nullptr;
@@ -707,7 +709,7 @@ constexpr int FC_LDS_BYTES = 48 * 1024;     // islands of up to 2048 (f32) / 102
 
 // REGS: islands of up to WG x 12 (f32) / WG x 6 (f64) rows keep them in registers for the sweeps (wg_island_sweeps); a separate
 // instantiation, so that the streaming forms keep their register budget
-template <class T, int WG, bool REGS>
+template <class T, int WG, bool REGS, bool FB = false>
 __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                      int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                      StepDiag *__restrict__ diag, int lds_bodies, const ExactCounts *__restrict__ dc,
@@ -742,6 +744,7 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
             by_contact = __syncthreads_and(all3) != 0;
         }
         by_contact = by_contact && (nc <= 64 || sizeof(T) == 4);      // (a contact's rows are 90 reals of registers: two per lane in f32)
+        by_contact = by_contact && !FB;                              // (feedback reads the row table: the rows are built there, by the row form)
     }
 
     for (int k = tid; k < nb; k += WG) stage_body(S, bflags, stride, I, P, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], k);
@@ -751,7 +754,7 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
     for (int k = tid; k < nb; k += WG) body_tmp(S, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], hinv);
     __syncthreads();
     if (!by_contact) {
-        for (int i = tid; i < m; i += WG) row_setup(rows, jb, bs, i, hinv, P.sor_w);
+        for (int i = tid; i < m; i += WG) row_setup<T, true, FB>(rows, jb, bs, i, hinv, P.sor_w);
         __syncthreads();
     }
 

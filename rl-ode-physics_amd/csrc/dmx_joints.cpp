@@ -64,6 +64,10 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                                      const uint8_t *include, const DevGeometry *geo)
 {
     const int n = (int)b->n;
+    // feedback (dmxBatchSetFeedback): for dmxBatchStepJoints' own ticks only -- the ticks that find their contacts themselves come
+    // here with a subset or with device geometry, and produce none.  Off, nothing below stages, launches or stores anything new.
+    const bool fb = b->fb_on && !include && !geo;
+    b->fb_valid = false;                    // (set again where the tick has been enqueued whole)
     bool exact = b->stepper_exact;          // dWorldStep: islands solved exactly (decided per tick: see the row limit below)
     // per-slot scratch that persists between ticks: parent = identity, island = -1, last = -1 outside a tick
     if ((int)b->sc_parent.size() != n) {
@@ -366,17 +370,21 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // int staging: body_off[ni+1] bodies[nlive] con_off[ni+1] row_off[ni+1] cb1[nc] cb2[nc] cmode[nc] csrc[nc] crow[nc]
     //              big[ni] big_list[n_big] lev_count[n_big] lev_off[..] lev_rows[..]
     const size_t n_int = (size_t)3 * (ni + 1) + (size_t)nlive + (size_t)5 * nc + (size_t)ni + (size_t)2 * n_big +
-                         lev_off_h.size() + 2 * lev_rows_h.size();      // ... lev_rows[..] row_level[..]
+                         lev_off_h.size() + 2 * lev_rows_h.size() +      // ... lev_rows[..] row_level[..]
+                         (fb ? (size_t)3 * nc : 0);                     // feedback: fb_out[nc] fb_info[nc] fb_isl[nc]
+    // feedback: 12 reals per joint of the set and per contact joint given; a small tick keeps them behind its tables' reals
+    const size_t n_fb = fb ? (size_t)12 * (b->art.size() + (size_t)nj_in) : 0;
     // real staging: cpos[3nc] cnormal[3nc] cdepth cmu cbounce cbounce_vel csoft_erp csoft_cfm [nc each]
     const size_t n_real = (size_t)12 * nc;
     int rc;
     int *hi; T *hr;
     const int sp = b->sm_parity;
     const size_t sm_real_at = ((n_int * sizeof(int) + 64 + 255) / 256) * 256;      // the reals' offset in a small tick's staging buffer
+    const size_t sm_fb_at = ((sm_real_at + n_real * sizeof(T) + 64 + 255) / 256) * 256;      // ... and the feedback's, when it is on
     if (small) {
         // host-mapped staging buffer `sp`: last read by the small tick before the previous one
         if (b->sm_ev_pending[sp]) { HIP_TRY(hipEventSynchronize(b->sm_ev[sp])); b->sm_ev_pending[sp] = false; }
-        if ((rc = ensure_mapped(&b->sm_stage[sp], &b->sm_stage_dev[sp], &b->sm_stage_bytes[sp], sm_real_at + n_real * sizeof(T) + 64)) != DMX_OK) return rc;
+        if ((rc = ensure_mapped(&b->sm_stage[sp], &b->sm_stage_dev[sp], &b->sm_stage_bytes[sp], fb ? sm_fb_at + n_fb * sizeof(T) + 64 : sm_real_at + n_real * sizeof(T) + 64)) != DMX_OK) return rc;
         hi = (int *)b->sm_stage[sp];
         hr = (T *)((char *)b->sm_stage[sp] + sm_real_at);
         // the general path's own pinned staging keeps pace with the world (a compare per tick while it is large enough): a tick
@@ -398,6 +406,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     int *cb1 = row_off + (ni + 1), *cb2 = cb1 + nc, *cmode = cb2 + nc, *csrc = cmode + nc, *crow = csrc + nc;
     int *big = crow + nc, *big_list = big + ni, *lev_count = big_list + n_big, *lev_off = lev_count + n_big;
     int *lev_rows = lev_off + lev_off_h.size();
+    int *fb_out = lev_rows + 2 * lev_rows_h.size(), *fb_info = fb_out + nc, *fb_isl = fb_info + nc;      // (feedback on only)
     if (nc) memcpy(crow, crow_h.data(), (size_t)nc * sizeof(int));
     if (ni) memcpy(big, big_h.data(), (size_t)ni * sizeof(int));
     if (n_big) { memcpy(big_list, big_list_h.data(), (size_t)n_big * sizeof(int)); memcpy(lev_count, lev_count_h.data(), (size_t)n_big * sizeof(int)); }
@@ -504,6 +513,22 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         });
     }
 
+    if (fb) {
+        // which entries begin a joint, how many entries it has (a joint's units are adjacent: emitted back to back, stable sort)
+        // and where its result goes: the set's joints first, then the caller's contact joints in the order given
+        const int n_art = (int)b->art.size();
+        for (int d = 0; d < nc; d++) {
+            const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
+            fb_isl[d] = island_of[(size_t)c.b1];
+            if (!c.unit) { fb_out[d] = n_art + (int)(c.j - joints); fb_info[d] = 2 + (c.rev ? 1 : 0); continue; }
+            const bool head = d == 0 || !cj[(size_t)con_sorted[(size_t)d - 1]].unit || cj[(size_t)con_sorted[(size_t)d - 1]].art != c.art;
+            fb_out[d] = -1; fb_info[d] = 0;
+            if (!head) continue;
+            int cnt = 1;
+            while (d + cnt < nc && cj[(size_t)con_sorted[(size_t)d + cnt]].unit && cj[(size_t)con_sorted[(size_t)d + cnt]].art == c.art) cnt++;
+            fb_out[d] = c.art; fb_info[d] = 2 * cnt + (c.rev ? 1 : 0);
+        }
+    }
     for (int s : slots) { b->sc_parent[(size_t)s] = s; island_of[(size_t)s] = -1; }     // scratch back to its idle state
 
     // ---- device buffers -----------------------------------------------------------------------------------
@@ -539,6 +564,27 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     I.cbounce = I.cmu + nc; I.cbounce_vel = I.cbounce + nc; I.csoft_erp = I.cbounce_vel + nc; I.csoft_cfm = I.csoft_erp + nc;
     I.rows = (T *)b->jd_rows.p; I.rowjb = (int *)b->jd_rowjb.p; I.bscr = (T *)b->jd_bscr.p; I.local = (int *)b->jd_local.p;
     I.singles = (exact || ode_order) ? 0 : 1;
+    FeedbackSet<T> F;
+    if (fb) {
+        // every solve must leave lambda in the row table: the one-body forms keep their rows in registers, so their islands take
+        // solve_islands' row form (held bit-identical to them by tests/test_gpu_static.py and tests/test_gpu_parity.py)
+        I.singles = 0;
+        F.mode = exact ? FB_UNSCALED : FB_SCALED;
+        F.out = di + (fb_out - hi); F.info = di + (fb_info - hi); F.isl = di + (fb_isl - hi);
+        if (small) {
+            T *fbh = (T *)((char *)b->sm_stage[sp] + sm_fb_at);
+            for (size_t k = 0; k < n_fb; k++) fbh[k] = T(0);      // (inactive and dropped joints report zeros)
+            F.fb = (T *)((char *)b->sm_stage_dev[sp] + sm_fb_at);
+            b->fb_host = fbh;
+        } else {
+            if ((rc = dmx_ensure_dev(b->fb_dev, n_fb * sizeof(T) + 64)) != DMX_OK) return rc;
+            HIP_TRY(hipMemsetAsync(b->fb_dev.p, 0, n_fb * sizeof(T) + 64, b->stream));
+            F.fb = (T *)b->fb_dev.p;
+            b->fb_host = nullptr;
+        }
+        b->fb_devp = F.fb;
+        b->fb_nj = (int64_t)b->art.size(); b->fb_nc = nj_in;
+    }
     I.has_units = n_units > 0 ? 1 : 0;
     b->last_units = n_units;               // (the kernels count an island's entries: dmxBatchLastContactCount takes these off)
     I.order = nullptr; I.order_stride = 0;
@@ -602,7 +648,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         } else {
             lds = small_tick_sor_lds((int)sizeof(T), big_max_bodies, &K.lds_bodies);
         }
-        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, exact, lds, b->stream));
+        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream));
         HIP_TRY(hipEventRecord(b->sm_ev[sp], b->stream));
         b->sm_ev_pending[sp] = true;
         b->sm_parity = sp ^ 1;
@@ -613,6 +659,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         b->last_islands = true;
         b->ext_pending = false;
         b->stepped_with_plane = true;     // diagnostics are valid
+        b->fb_valid = fb;
         return DMX_OK;
     }
     dmx_state_written(b);
@@ -688,10 +735,13 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             lcp_grid_end_tick(b);
             HIP_TRY(hipStreamSynchronize(b->stream));
         }
+        if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
     } else {
-        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream));
+        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb));
+        if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
         if (ode_order) HIP_TRY(hipStreamSynchronize(b->stream));      // the order table came from pageable host memory
     }
+    b->fb_valid = fb;
     b->last_islands = true;
     b->ext_pending = false;
     b->stepped_with_plane = true;     // diagnostics are valid

@@ -99,6 +99,7 @@ struct dxJoint {
     bool rev = false;
     double lo_stop = -__builtin_huge_val(), hi_stop = __builtin_huge_val(), vel = 0, fmax = 0;
     double qrel0[4] = { 1, 0, 0, 0 };
+    dJointFeedback *fb = nullptr;      // dJointSetFeedback: the caller's struct, filled by every step while it is set
 };
 
 struct dxJointGroup {
@@ -114,6 +115,9 @@ struct dxWorld {
     bool art_dirty = false;            // ... and changed since the batch last saw them
     bool limot_dirty = false;          // a hinge's limit / motor parameter or zero pose changed since the batch last saw them
     bool limots_sent = false;          // the batch holds limots (dmxBatchSetHingeLimots)
+    int n_feedback = 0;                // joints of the world with a feedback struct set (dJointSetFeedback)
+    bool feedback_sent = false;        // the batch's feedback is switched on (dmxBatchSetFeedback): only while n_feedback > 0
+    std::vector<dmxJointFeedback> fbuf;
     std::vector<dmxJoint> aj;
     std::vector<dmxHingeLimot> al;
     dReal g[3] = { 0, 0, 0 };
@@ -141,6 +145,7 @@ struct dxWorld {
         host_dirty = true;
         pushed_valid = false;          // a new batch has been told nothing yet
         art_dirty = !arts.empty();
+        feedback_sent = false;         // (a new batch's feedback is off: world_step switches it on again if a struct is set)
         // One read-back the general way into the buffer to_host() uses, now.  The runtime registers a pageable destination the
         // first time a device-to-host copy lands in it (8 ms, measured); a world whose ticks run on the single-launch path reads
         // its poses from the batch's host mirror and would meet that at the first tick that falls back -- a whole 120 Hz frame.
@@ -357,6 +362,9 @@ static int world_step(dWorldID w, dReal h, int stepper)
         c.soft_erp = ct.surface.soft_erp; c.soft_cfm = ct.surface.soft_cfm;
         w->cj.push_back(c);
     }
+    // feedback: on in the batch only while some joint of the world has a struct set -- a world without one ticks as it always did
+    const bool feedback = w->n_feedback > 0;
+    if (feedback != w->feedback_sent) { DMX_MUST(dmxBatchSetFeedback(w->batch, feedback ? 1 : 0)); w->feedback_sent = feedback; }
     {
         const int rc = dmxBatchStepJoints(w->batch, h, (int64_t)w->cj.size(), w->cj.data());
         // ball / hinge joints under DMX_ROW_ORDER=ode with QuickStep: the batch has said so on stderr; the step fails, the process lives
@@ -364,6 +372,30 @@ static int world_step(dWorldID w, dReal h, int stepper)
         if (rc != DMX_OK) fatal("dmxBatchStepJoints", rc);
     }
     w->dev_newer = true;
+    if (feedback) {
+        // the batch reports the sides as it was given them; f1 / t1 here belong to dJointGetBody(j, 0): an articulation joint
+        // attached as (0, body) was handed over as (world, body) and has the body as its body 1
+        auto fill = [](const dmxJointFeedback &s, bool exchange, dJointFeedback *d) {
+            const double *a = exchange ? s.f2 : s.f1, *b = exchange ? s.t2 : s.t1, *c = exchange ? s.f1 : s.f2, *e = exchange ? s.t1 : s.t2;
+            for (int k = 0; k < 3; k++) { d->f1[k] = (dReal)a[k]; d->t1[k] = (dReal)b[k]; d->f2[k] = (dReal)c[k]; d->t2[k] = (dReal)e[k]; }
+            d->f1[3] = d->t1[3] = d->f2[3] = d->t2[3] = 0;
+        };
+        bool arts = false, contacts = false;
+        for (const dxJoint *j : w->arts) arts = arts || j->fb;
+        for (const dxJoint *j : w->joints) contacts = contacts || j->fb;
+        if (arts) {
+            w->fbuf.resize(w->arts.size());
+            DMX_MUST(dmxBatchJointFeedback(w->batch, w->fbuf.data()));
+            for (size_t k = 0; k < w->arts.size(); k++)
+                if (w->arts[k]->fb) fill(w->fbuf[k], w->arts[k]->rev && w->arts[k]->b1 && !w->arts[k]->b2, w->arts[k]->fb);
+        }
+        if (contacts) {
+            w->fbuf.resize(w->joints.size());
+            DMX_MUST(dmxBatchContactFeedback(w->batch, (int64_t)w->joints.size(), w->fbuf.data()));
+            for (size_t k = 0; k < w->joints.size(); k++)
+                if (w->joints[k]->fb) fill(w->fbuf[k], false, w->joints[k]->fb);
+        }
+    }
     return 1;
 }
 // dWorldQuickStep: QuickStep's SOR sweeps.  dWorldStep -- what the reference calls, main.c:213 -- the same rows with
@@ -860,6 +892,7 @@ extern "C" void dJointGroupEmpty(dJointGroupID g)
             auto &v = j->type == dJointTypeContact ? j->world->joints : j->world->arts;
             v.erase(std::remove(v.begin(), v.end(), j), v.end());
             if (j->type != dJointTypeContact) j->world->art_dirty = true;
+            if (j->fb) j->world->n_feedback--;
         }
         delete j;
     }
@@ -966,10 +999,18 @@ extern "C" void dJointDestroy(dJointID j)
         auto &v = j->type == dJointTypeContact ? j->world->joints : j->world->arts;
         v.erase(std::remove(v.begin(), v.end(), j), v.end());
         if (j->type != dJointTypeContact) j->world->art_dirty = true;
+        if (j->fb) j->world->n_feedback--;
     }
     if (j->group) { auto &v = j->group->joints; v.erase(std::remove(v.begin(), v.end(), j), v.end()); }
     delete j;
 }
+extern "C" void dJointSetFeedback(dJointID j, dJointFeedback *f)
+{
+    if (!j) return;
+    if (j->world) j->world->n_feedback += (f ? 1 : 0) - (j->fb ? 1 : 0);
+    j->fb = f;
+}
+extern "C" dJointFeedback *dJointGetFeedback(dJointID j) { return j ? j->fb : nullptr; }
 extern "C" int dJointGetType(dJointID j) { return j ? j->type : dJointTypeNone; }
 extern "C" dBodyID dJointGetBody(dJointID j, int index) { return !j ? nullptr : index == 0 ? j->b1 : index == 1 ? j->b2 : nullptr; }
 extern "C" void dJointSetBallAnchor(dJointID j, dReal x, dReal y, dReal z) { if (j && j->type == dJointTypeBall) set_anchor(j, x, y, z); }

@@ -2,7 +2,9 @@
 fall onto the ground and lie there on sphere-ground contacts: 48 and 512 bodies, both steppers, both precisions.
 The contacts of a tick are made on the host from the poses read back (a sphere of radius 0.5 per link against y = 0), outside
 the timed region; timed is the step call up to the point where the new state can be read (step_joints + synchronize).
-usage: python scripts/time_joints.py [--bodies 48,512] [--settle 120] [--ticks 200] [--small-tick 0|1] [--mu 1.0] [--only f32:exact]"""
+--feedback 1 switches dmxBatchSetFeedback on; 2 also reads the joints' and the contacts' feedback back after every tick, inside the
+timed region.
+usage: python scripts/time_joints.py [--bodies 48,512] [--settle 120] [--ticks 200] [--small-tick 0|1] [--mu 1.0] [--only f32:exact] [--feedback 0|1|2]"""
 import argparse
 import os
 import sys
@@ -55,7 +57,7 @@ def contacts(pos, mu=1.0):
     return c
 
 
-def run(n, prec, stepper, settle, ticks, small, mu=1.0):
+def run(n, prec, stepper, settle, ticks, small, mu=1.0, feedback=0):
     w = B_.BatchWorld(n, prec)
     try:
         pos, quat = scene(n)
@@ -65,6 +67,8 @@ def run(n, prec, stepper, settle, ticks, small, mu=1.0):
         w.set_cfm(1e-5)
         w.set_small_tick(B_.SMALL_TICK_AUTO if small else B_.SMALL_TICK_OFF)
         w.set_joints(joints(w, n, pos))
+        if feedback:
+            w.set_feedback(True)
         times, rows = [], 0
         for t in range(settle + ticks):
             w.set_stepper(B_.STEPPER_EXACT if (stepper == "exact" and t >= settle) else B_.STEPPER_QUICK)
@@ -72,6 +76,8 @@ def run(n, prec, stepper, settle, ticks, small, mu=1.0):
             t0 = time.perf_counter()
             w.step_joints(H, c)
             w.synchronize()
+            if feedback == 2:
+                w.joint_feedback(), w.contact_feedback(len(c))
             if t >= settle:
                 times.append(time.perf_counter() - t0)
                 rows = max(rows, len(c))
@@ -79,7 +85,7 @@ def run(n, prec, stepper, settle, ticks, small, mu=1.0):
         pe, ae, mx = w.joint_errors()
         st = w.small_tick_stats()
         slow = int(np.sum(ms > 1.5 * ms.min()))
-        print(f"bodies={n:4d} {'f32' if prec == 'float32' else 'f64'} {stepper:5s} small_tick={int(small)} mu={mu:g}  median {np.median(ms):.4f} ms  "
+        print(f"bodies={n:4d} {'f32' if prec == 'float32' else 'f64'} {stepper:5s} small_tick={int(small)} mu={mu:g} feedback={feedback}  median {np.median(ms):.4f} ms  "
               f"min {ms.min():.4f}  p90 {np.percentile(ms, 90):.4f}  ({ticks} ticks, {w.joint_count()} joints, up to {rows} contacts, "
               f"{st['small']} small / {st['general']} general ticks, {slow} ticks above 1.5 x min, joint error {mx[0]:.2e})", flush=True)
     finally:
@@ -93,6 +99,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--small-tick", type=int, default=1)
     ap.add_argument("--mu", type=float, default=1.0, help="the ground contacts' friction coefficient (inf: rows that never clamp)")
+    ap.add_argument("--feedback", type=int, default=0, help="1: feedback on; 2: on, and read back after every tick")
     ap.add_argument("--only", default="", help="one precision and stepper, e.g. f32:exact")
     a = ap.parse_args()
     for n in [int(v) for v in a.bodies.split(",")]:
@@ -100,7 +107,7 @@ def main():
             for stepper in ("quick", "exact"):
                 if a.only and a.only != f"{'f32' if prec == 'float32' else 'f64'}:{stepper}":
                     continue
-                run(n, prec, stepper, a.settle, a.ticks, bool(a.small_tick), a.mu)
+                run(n, prec, stepper, a.settle, a.ticks, bool(a.small_tick), a.mu, a.feedback)
 
 
 if __name__ == "__main__":

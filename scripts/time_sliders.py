@@ -2,7 +2,9 @@
 island of 600 rows: QuickStep's workgroup form, dWorldStep's grid solve) and 24 cart-poles (48 bodies, 24 islands of 11 rows: the
 single-launch tick), both steppers, both precisions.  Timed is the step call up to the point where the new state can be read
 (step_joints + synchronize); median, min and max over the timed ticks' repeats.
-usage: python scripts/time_sliders.py [--ticks 200] [--repeats 5]"""
+--feedback 1 switches dmxBatchSetFeedback on (the ticks leave every joint's force and torque on the device), 2 also reads it back
+after every tick (joint_feedback), inside the timed region.
+usage: python scripts/time_sliders.py [--ticks 200] [--repeats 5] [--feedback 0|1|2]"""
 import argparse
 import os
 import sys
@@ -38,7 +40,7 @@ def scenes():
     yield "24 cart-poles (48 bodies)", B, art, lim
 
 
-def run(B, art, lim, prec, stepper, ticks):
+def run(B, art, lim, prec, stepper, ticks, feedback=0):
     w = B_.BatchWorld(B.n, prec)
     try:
         w.set_erp(0.2); w.set_cfm(1e-5)
@@ -49,6 +51,8 @@ def run(B, art, lim, prec, stepper, ticks):
         w.set_joints(to_c(art, B_.JOINT_DTYPE))
         w.set_hinge_limots(to_c(lim, B_.HINGE_LIMOT_DTYPE))
         none = np.zeros(0, B_.CONTACT_JOINT_DTYPE)
+        if feedback:
+            w.set_feedback(True)
         for _ in range(20):
             w.step_joints(H, none)
         w.synchronize()
@@ -56,6 +60,8 @@ def run(B, art, lim, prec, stepper, ticks):
         for _ in range(ticks):
             w.step_joints(H, none)
             w.synchronize()
+            if feedback == 2:
+                w.joint_feedback()
         dt = (time.perf_counter() - t0) / ticks
         st = w.small_tick_stats()
         return 1e3 * dt, "small tick" if st["small"] else "general path"
@@ -67,13 +73,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--feedback", type=int, default=0, help="1: feedback on; 2: on, and read back after every tick")
     a = ap.parse_args()
     for name, B, art, lim in scenes():
         for stepper in ("quick", "exact"):
             for prec in ("float32", "float64"):
-                r = [run(B, art, lim, prec, stepper, a.ticks) for _ in range(a.repeats)]
+                r = [run(B, art, lim, prec, stepper, a.ticks, a.feedback) for _ in range(a.repeats)]
                 ms = sorted(x[0] for x in r)
-                print(f"{name:28s} {stepper:5s} {prec}  median {ms[len(ms) // 2]:.4f} ms  min {ms[0]:.4f}  max {ms[-1]:.4f}  ({r[0][1]})", flush=True)
+                fb = f", feedback {a.feedback}" if a.feedback else ""
+                print(f"{name:28s} {stepper:5s} {prec}  median {ms[len(ms) // 2]:.4f} ms  min {ms[0]:.4f}  max {ms[-1]:.4f}  ({r[0][1]}{fb})", flush=True)
 
 
 if __name__ == "__main__":
