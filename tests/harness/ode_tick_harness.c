@@ -70,6 +70,7 @@ int main(void)
 {
     int steps, use_plane, n_static, n_body, i, k, s, up_front, every, readback, created, quick, exact_after;
     double dt, sink = 0, t_collide = 0, t_step = 0, t0, t1, t2;
+    double grav[3] = { 0.0, -9.8, 0.0 }, plane[4] = { 0.0, 1.0, 0.0, 0.0 };
     int time_from, timed = 0;
     struct spawn { int type; dReal size[3], pos[3]; dMatrix3 rm; } *spawn;
     dBodyID *bodies;
@@ -77,12 +78,21 @@ int main(void)
 
     dt = rd(); steps = (int)rd(); use_plane = (int)rd();
 
+    /* HARNESS_GRAVITY="gx gy gz", HARNESS_PLANE="a b c d": a world that is not y-up (ODE's own convention is z-up:
+     * dWorldSetGravity(w, 0, 0, -9.81), dCreatePlane(s, 0, 0, 1, 0)).  Unset: the reference's (main.c:96). */
+    if (getenv("HARNESS_GRAVITY") && sscanf(getenv("HARNESS_GRAVITY"), "%lf %lf %lf", &grav[0], &grav[1], &grav[2]) != 3) {
+        fprintf(stderr, "harness: bad HARNESS_GRAVITY\n"); return 2;
+    }
+    if (getenv("HARNESS_PLANE") && sscanf(getenv("HARNESS_PLANE"), "%lf %lf %lf %lf", &plane[0], &plane[1], &plane[2], &plane[3]) != 4) {
+        fprintf(stderr, "harness: bad HARNESS_PLANE\n"); return 2;
+    }
+
     dInitODE();
     world = dWorldCreate();
-    dWorldSetGravity(world, 0.0, -9.8, 0.0);
+    dWorldSetGravity(world, (dReal)grav[0], (dReal)grav[1], (dReal)grav[2]);
     space = dHashSpaceCreate(0);
     contactGroup = dJointGroupCreate(0);
-    if (use_plane) dCreatePlane(space, 0, 1, 0, 0);
+    if (use_plane) dCreatePlane(space, (dReal)plane[0], (dReal)plane[1], (dReal)plane[2], (dReal)plane[3]);
 
     n_static = (int)rd();
     for (i = 0; i < n_static; i++) {

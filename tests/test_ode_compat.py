@@ -26,8 +26,9 @@ def _build_harness(tmp, single):
     return exe
 
 
-def _scene_text(dt, steps, use_plane, statics, bodies):
-    ident = [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0]
+def _scene_text(dt, steps, use_plane, statics, bodies, body_R=None):
+    """body_R: the 3x4 rotation every body starts with (default: the identity, as the reference's spawner leaves it)"""
+    ident = [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0] if body_R is None else list(body_R)
     lines = [f"{dt!r} {steps} {int(use_plane)}", str(len(statics))]
     for size, pos, R in statics:
         lines.append(" ".join(repr(float(v)) for v in (*size, *pos, *R)))
@@ -38,25 +39,26 @@ def _scene_text(dt, steps, use_plane, statics, bodies):
 
 
 def _oracle_poses(dtype, dt, steps, use_plane, statics, bodies, up_front=None, every=0, exact=False, ode_order_seed=None,
-                  exact_after=None):
+                  exact_after=None, gravity=(0.0, -9.8, 0.0), plane=(0, 1, 0, 0), body_R=None):
+    """gravity, plane, body_R: the harness's HARNESS_GRAVITY, HARNESS_PLANE and _scene_text's body_R (defaults: the reference's)"""
     from oracle.orc_ctypes import Oracle
     import ctypes as C
     orc = Oracle(dtype)
     lib = orc.lib
-    ow = orc.world()
+    ow = orc.world(gravity=gravity)
     ow.set_stepper(exact)
     if ode_order_seed is not None:          # stock ODE's row order: joint-discovery numbering + the LCG shuffle every 8th sweep
         lib.orc_world_set_row_order(ow.w, 1)
         lib.orc_rand_seed(ode_order_seed)
     if use_plane:
-        ow.add_plane(0, 1, 0, 0)
+        ow.add_plane(*plane)
     for size, pos, R in statics:
         g = lib.orc_geom_create_box(ow.w, *size)
         lib.orc_geom_set_position(ow.w, g, *pos)
         _, rp = orc.arr(R)
         lib.orc_geom_set_rotation(ow.w, g, rp)
         lib.orc_geom_set_category_bits(ow.w, g, 0xFFFFFFFE)      # the double SetCategoryBits of main.c:751-752
-    ident = [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0]
+    ident = [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0] if body_R is None else list(body_R)
 
     def create(kind, size, pos):
         b = lib.orc_body_create(ow.w)
