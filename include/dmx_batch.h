@@ -502,7 +502,17 @@ int dmxBatchContactFeedback(dmxBatchID b, int64_t n, dmxJointFeedback *out);
 /* device arrays of 12 reals per entry (f1, t1, f2, t2) in the batch's precision, valid until the next tick; either may be NULL */
 int dmxBatchFeedbackDevice(dmxBatchID b, const void **joints_dev, const void **contacts_dev);
 
-/* per-body flags for the island path: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes */
+/* per-body flags: dBodyDestroy'ed slots, dBodySetKinematic (main.c:712), gravity / gyro modes.
+ * Honoured by dmxBatchStepJoints, in every solver form and for bodies without rows: a slot without DMX_BODY_ALIVE is not
+ * stepped and a joint that names it treats it as static; a KINEMATIC body keeps its velocities, moves with them and acts on
+ * its joints with infinite mass; NOGRAVITY / NOGYRO leave out gravity / the gyroscopic torque of that body.  Ray casts skip
+ * slots that are not alive.
+ * Refused by the ticks that find their own contacts -- dmxBatchStep, dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick,
+ * dmxBatchChunkTicks, dmxBatchExactTick: their fused kernels never read the flags while the islands they build do, so while
+ * any slot of [0, active count) has a byte other than DMX_BODY_ALIVE they return DMX_EINVAL, say so in one line on stderr
+ * and leave the state untouched (ghost slots do not count).  Nothing is silently ignored.
+ * dmxBatchFindPairs does not read the flags: a dead slot still takes part in the pair search unless its class is
+ * DMX_GEOM_NONE (dmxBatchUploadGeomType), which is how the ODE face retires a destroyed body. */
 enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };
 int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64_t first, int64_t count);
 

@@ -326,7 +326,9 @@ class BatchWorld:
         return dict(zip(SMALL_TICK_STATS, out))
 
     def upload_body_flags(self, flags, first=0):
-        """BODY_ALIVE / BODY_KINEMATIC / BODY_NOGRAVITY / BODY_NOGYRO per slot (uint8)"""
+        """BODY_ALIVE / BODY_KINEMATIC / BODY_NOGRAVITY / BODY_NOGYRO per slot (uint8).  step_joints honours them; step,
+        step_timed, step_range, chunk_tick(s) and exact_tick refuse (DmxError, DMX_EINVAL) while an active slot is not plain
+        BODY_ALIVE (include/dmx_batch.h)"""
         f = np.ascontiguousarray(flags, dtype=np.uint8)
         _check(self.lib.dmxBatchUploadBodyFlags(self.h, f.ctypes.data, first, f.shape[0]), "dmxBatchUploadBodyFlags")
 

@@ -360,7 +360,11 @@ extern "C" int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64
     SETTLE(b);
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
-    for (int64_t i = 0; i < count; i++) b->h_bflags[(size_t)(first + i)] = flags[i];
+    for (int64_t i = 0; i < count; i++) {
+        uint8_t &f = b->h_bflags[(size_t)(first + i)];
+        if (first + i < b->n_active) b->n_flagged += (int64_t)(flags[i] != BF_ALIVE) - (int64_t)(f != BF_ALIVE);
+        f = flags[i];
+    }
     b->state_version++;         // what rays can see has changed
     HIP_TRY(hipMemcpyAsync(b->bflags + first, b->h_bflags.data() + first, (size_t)count, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -419,6 +423,7 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
 {
     if (!b || !(h > 0) || nsteps < 0) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStep")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchStep")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -672,6 +677,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchChunkTick")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -681,6 +687,7 @@ extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_
 {
     if (!b || !(h > 0) || nticks < 0) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -741,6 +748,7 @@ extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
 {
     if (!b || !(h > 0)) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchExactTick")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchExactTick")) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
@@ -835,6 +843,8 @@ extern "C" int dmxBatchSetActiveCount(dmxBatchID b, int64_t n_active)
     SETTLE(b);
     if (n_active != b->n && n_active % 4 != 0) return DMX_EINVAL;   // the last 16 B pack must not reach into ghost slots
     b->n_active = n_active;
+    b->n_flagged = 0;
+    for (int64_t i = 0; i < n_active; i++) b->n_flagged += b->h_bflags[(size_t)i] != BF_ALIVE;
     return DMX_OK;
 }
 
@@ -842,6 +852,7 @@ extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t 
 {
     if (!b || !(h > 0) || first < 0 || count < 0 || first + count > b->n_active) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStepRange")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchStepRange")) return DMX_EINVAL;
     SETTLE(b);
     // lanes own 16 B packs of consecutive bodies: ranges must start on a pack and end on one (or at the end)
     const int64_t pack = 16 / (int64_t)b->rsize;
@@ -885,6 +896,7 @@ extern "C" int dmxBatchStepTimed(dmxBatchID b, double h, int nsteps, float *ms)
 {
     if (!b || !ms) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStepTimed")) return DMX_EINVAL;
+    if (dmx_refuse_flags(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     int rc = dmxBatchStep(b, h, nsteps);

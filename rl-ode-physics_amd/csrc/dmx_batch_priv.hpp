@@ -118,6 +118,7 @@ struct dmxBatch {
     // general island path (explicit contact joints)
     uint8_t *bflags = nullptr;                 // device, per-slot BF_* flags
     std::vector<uint8_t> h_bflags;             // host mirror
+    int64_t n_flagged = 0;                     // slots of [0, n_active) whose byte is not BF_ALIVE (dmx_refuse_flags)
     struct DevBuf { void *p = nullptr; size_t bytes = 0; };
     DevBuf jd_int, jd_real, jd_rows, jd_rowjb, jd_bscr, jd_local;   // device staging / scratch
     std::vector<int> sc_nbd_of, sc_grid_list; std::vector<std::pair<uint64_t, int>> sc_pair_ord;
@@ -226,6 +227,16 @@ inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
     if (b->art.empty()) return false;
     fprintf(stderr, "libode_mi355: %s does not honour articulation joints (dmxBatchSetJoints): %lld are set; use dmxBatchStepJoints\n",
             what, (long long)b->art.size());
+    return true;
+}
+// ... and neither do they know the per-body flags on their fast paths (the fused ticks never read them, the islands they hand to
+// launch_islands do): a kinematic body would fall while alone and stand while touched.  They refuse too, from a count kept on
+// the host by dmxBatchUploadBodyFlags and dmxBatchSetActiveCount; ghost slots do not count, nobody steps them
+inline bool dmx_refuse_flags(const dmxBatch *b, const char *what)
+{
+    if (b->n_flagged == 0) return false;
+    fprintf(stderr, "libode_mi355: %s does not honour per-body flags (dmxBatchUploadBodyFlags): %lld slot(s) carry a byte other than DMX_BODY_ALIVE; use dmxBatchStepJoints\n",
+            what, (long long)b->n_flagged);
     return true;
 }
 // A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later

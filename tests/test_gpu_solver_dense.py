@@ -121,26 +121,35 @@ def press_chain(m, rng):
     return B, np.array(out, ld.JOINT_DTYPE)
 
 
-def device_tick(prec, B, W, jts, stepper, ticks=1, between=None):
-    """-> list per tick of (pre-tick Bodies as the device held them, post-tick state (n,13), lcp stats after the tick)"""
+def device_tick(prec, B, W, jts, stepper, ticks=1, between=None, small=None):
+    """-> list per tick of (pre-tick Bodies as the device held them, the tick's joints, post-tick state (n,13), lcp stats after
+    the tick, with the small tick's counters under "tick").  `between(t, jts)` gives tick t's joints, or (joints, flags): the
+    flags are uploaded before the tick and are the ones the pre-tick Bodies carry from then on.  `small`: set_small_tick"""
     dt = np.dtype(prec)
     w = B_.BatchWorld(B.n, prec, gravity=tuple(W.gravity))
     try:
         w.set_erp(W.erp); w.set_cfm(W.cfm); w.set_quickstep(W.iters, W.sor_w); w.set_gyro_mode(W.gyro)
         w.set_stepper(B_.STEPPER_EXACT if stepper == "exact" else B_.STEPPER_QUICK)
+        if small is not None:
+            w.set_small_tick(small)
         w.upload(B_.POS, B.pos); w.upload(B_.QUAT_RAW, B.quat); w.upload(B_.LVEL, B.lvel); w.upload(B_.AVEL, B.avel)
         w.upload(B_.MASS, B.mass); w.upload(B_.INERTIA, B.inertia)
         w.upload_body_flags(B.flags)
         mass = w.download(B_.MASS).astype(np.float64).reshape(-1)
         inertia = w.download(B_.INERTIA).astype(np.float64)
         out = []
+        flags = B.flags
         for t in range(ticks):
             j = between(t, jts) if between else jts
+            if isinstance(j, tuple):
+                j, flags = j
+                w.upload_body_flags(flags)
             pre = w.download(B_.STATE).astype(np.float64)
-            Bp = ld.Bodies(pre[:, 0:3], pre[:, 3:7], pre[:, 7:10], pre[:, 10:13], mass, inertia, B.flags)
+            Bp = ld.Bodies(pre[:, 0:3], pre[:, 3:7], pre[:, 7:10], pre[:, 10:13], mass, inertia, flags)
             w.step_joints(W.h, j.astype(B_.CONTACT_JOINT_DTYPE))
             w.synchronize()
-            out.append((Bp, j, w.download(B_.STATE).astype(np.float64), w.lcp_stats()))
+            post = w.download(B_.STATE).astype(np.float64)
+            out.append((Bp, j, post, dict(w.lcp_stats(), tick=w.small_tick_stats())))
         return out
     finally:
         w.close()
@@ -159,10 +168,11 @@ def as_precision(prec, W, jts):
     return W2, j2
 
 
-def check(prec, B, W, jts, stepper, tol=None, ticks=1, between=None):
-    """run the device and compare every tick with the reference; -> list of (reference Result, lcp stats)"""
+def check(prec, B, W, jts, stepper, tol=None, ticks=1, between=None, small=None):
+    """run the device and compare every tick with the reference (from the device's pre-tick state, with the flags then in
+    force); -> list of (reference Result, lcp stats); the Result carries the device's post-tick state as `.device`"""
     res = []
-    for Bp, j, post, stats in device_tick(prec, B, W, jts, stepper, ticks, between):
+    for Bp, j, post, stats in device_tick(prec, B, W, jts, stepper, ticks, between, small):
         Wr, jr = as_precision(prec, W, j)
         r = ld.step(Bp, Wr, jr, stepper)
         f32 = np.dtype(prec).itemsize == 4
