@@ -24,6 +24,7 @@
 #include "dmx_sweep.hpp"
 #include "dmx_fixed.hpp"
 #include "dmx_torque_free.hpp"
+#include "dmx_launch_consts.hpp"
 
 namespace dmx {
 
@@ -37,7 +38,11 @@ namespace dmx {
 //              is stored is stored whole, for all 64 lanes.  An out-of-place launch (the first of a collision-proof
 //              chunk) stores all 13, as OPT = 0 does.
 //   OPT_UNI    mass and inertia are the same for every slot (dmx_uniform.hpp keeps track, host side): they arrive
-//              as kernel arguments (StepParams::uni_mass / uni_inertia) and components 13..16 are not loaded.
+//              as kernel arguments (StepParams::uni_mass / uni_inertia) and components 13..16 are not loaded.  What the tick
+//              computes from them and h alone -- 1 / Ib.k, 1 / h, the isotropy test; h * (1 / m) and m g -- comes with them, computed
+//              once on the host with the tick's own operations (`lc`, dmx_launch_consts.hpp; `tf`): left in the kernel, the compiler
+//              hoists it ahead of the loop, 75 vector instructions with five IEEE divisions in front of every wavefront's first
+//              load.  A launch whose constants the rule of dmx_launch_consts.hpp refuses (zero, inf, NaN) is one without OPT_UNI.
 // A dropped scene of unit-mass bodies under gravity along y (the reference's AddBody + dWorldSetGravity) then moves
 // 13 reals in and 6 out (pos.y, quat, lvel.y) = 19 per body-step; any other scene moves what it changes, up to the 30.
 // Same values into the same free_body_step either way: same bits.
@@ -86,7 +91,7 @@ __host__ __device__ constexpr int fix_axis_of(int k) { return k < C_QUAT ? k - C
 
 template <class T, bool EXT, int MINW, bool MULTI, int OPT = 0, bool FIX = false, bool TF = false>
 __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t n, StepParams<T> P, int rev, int fix_mode,
-                                                            uint32_t *fix_words, TorqueFree<T> tf)
+                                                            uint32_t *fix_words, TorqueFree<T> tf, LaunchConsts<T> lc)
 {
     constexpr bool ELIDE = (OPT & OPT_ELIDE) != 0, UNI = (OPT & OPT_UNI) != 0;
     static_assert(!FIX || (ELIDE && !EXT && !MULTI), "the fixed-axis mode is built into the one-tick kernels with store elision only");
@@ -94,12 +99,18 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
     constexpr int NLOAD = UNI ? C_MASS : C_SIDES;      // components read: the state, and the constants unless they are arguments
     // So = where the new state goes: S itself (in place) or the batch's other slab (the first launch of a
     // collision-proof chunk, which thereby leaves the chunk's start state behind as the rollback snapshot)
-    if (P.gate != nullptr && *P.gate == 0u) return;
+    // (FIX: launch_step refuses such a launch with a gate or a skip mask, and the kernel relies on it -- it reads neither pointer,
+    //  which spares the wavefront a scalar load and its wait ahead of everything else)
+    if constexpr (!FIX) {
+        if (P.gate != nullptr && *P.gate == 0u) return;
+    }
     const int nticks = MULTI ? P.ticks : 1;         // MULTI = false: the one-tick kernel, no loop
     const bool in_place = ELIDE && So == S;         // wave-uniform: two kernel arguments
     for (int64_t i = sweep_block(blockIdx.x, gridDim.x, rev) * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
+        if constexpr (!FIX) {
+            if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
+        }
         T c[NLOAD];
         uint32_t fixed = 0, seen = 0;       // FIX, lean launches: the tile's word as read, and its lateral axes (wave-uniform)
         if constexpr (FIX) {
@@ -159,9 +170,17 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
                 facc = { f[0], f[1], f[2] };
                 tacc = { f[3], f[4], f[5] };
             }
-            if constexpr (TF) {
-                // the short tick for a wavefront whose every active lane it is proven for, the general one for any other
-                free_body_step_torque_free(x, q, v, w, mass, Ib, P.g, P.h, P.gyro, tf.on, tf.hm, V3<T>{ tf.mg[0], tf.mg[1], tf.mg[2] });
+            if constexpr (UNI) {
+                // what the tick makes of the launch's constants alone arrives with them (dmx_launch_consts.hpp: the quotients;
+                // dmx_torque_free.hpp: hm and m g): nothing here divides, and nothing is left to compute ahead of the loop
+                const TickGiven<T, EXT> K = { { lc.inv_Ib[0], lc.inv_Ib[1], lc.inv_Ib[2] }, lc.iso != 0, lc.inv_h, tf.hm, mass,
+                                              { tf.mg[0], tf.mg[1], tf.mg[2] } };
+                if constexpr (TF) {
+                    // the short tick for a wavefront whose every active lane it is proven for, the general one for any other
+                    free_body_step_torque_free(x, q, v, w, Ib, P.g, P.h, P.gyro, tf.on, K);
+                } else {
+                    free_body_step_with(x, q, v, w, Ib, facc, tacc, P.g, P.h, P.gyro, K);
+                }
             } else {
                 free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
             }
@@ -614,24 +633,31 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
         // kernel (VALU-bound, one store per `ticks` ticks) keeps its unconditional stores: the copy of the loaded state would
         // cost it a wave per SIMD (78 -> 91 VGPRs, 6 -> 5 waves) for a store it rarely issues, while the constants as arguments
         // cost it none (78 -> 79); a build with the elision in it measured the same within the spread at 32 ticks per launch
-        // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.
+        // (profiles/ab_elision_multi.txt).  DESIGN.md section 3 has the table.  (Since the constants' quotients come from the host the
+        // f32 kernels with OPT_UNI need 65 to 68 VGPRs and the bound no longer binds them; it stays, and also holds the kernel with
+        // FIX that loads its constants, which without its gate and skip tests would take 73 -- profiles/launch_consts_resources.txt.)
         constexpr int MWU = sizeof(T) == 4 ? 7 : 1;
-        const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni ? OPT_UNI : 0);
+        // Constants as arguments come with their quotients (dmx_launch_consts.hpp), which the instantiations with OPT_UNI read where
+        // the others divide per lane.  Where the rule refuses them -- a zero, an infinity or a NaN among mass, inertia and h, or a
+        // reciprocal that is not finite -- the launch drops OPT_UNI and loads the constants per lane, as a batch with mixed ones does.
+        const T tf_Ib[3] = { P.uni_inertia.x, P.uni_inertia.y, P.uni_inertia.z }, tf_g[3] = { P.g.x, P.g.y, P.g.z };
+        const LaunchConsts<T> lc = launch_consts<T>(P.uni_mass, tf_Ib, P.h);
+        const int opt = (P.elide & OPT_ELIDE) | ((P.elide & OPT_UNI) && P.uni && lc.on ? OPT_UNI : 0);
         // the short tick of a body without torque (dmx_torque_free.hpp has the rule): on -- the instantiations with TF -- or off, with the
         // launch's constants
-        const T tf_Ib[3] = { P.uni_inertia.x, P.uni_inertia.y, P.uni_inertia.z }, tf_g[3] = { P.g.x, P.g.y, P.g.z };
         const TorqueFree<T> tf = torque_free_plan<T>(torque_free, (opt & OPT_UNI) != 0, ext, P.gyro, P.uni_mass, tf_Ib, P.h, tf_g);
         if (tf_stats != nullptr) tf_stats[tf.on ? 0 : 1]++;      // contact-free launches with / without the short tick built in
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1, fix_mode, fix_words, tf); };
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, S, So, n, P, rev & 1, fix_mode, fix_words, tf, lc); };
         // an establishing or lean launch (dmx_fixed.hpp; the caller has asked the batch's record) is one of the two instantiations
         // with the fixed-axis mode built in; every other launch is the kernel it always was
         if (fix_mode != FIX_OFF) {
+            // (no gate, no skip mask: the instantiations with FIX do not read either pointer and rely on this refusal)
             if (P.ticks > 1 || ext || !(opt & OPT_ELIDE) || fix_words == nullptr || P.skip != nullptr || P.gate != nullptr) return hipErrorInvalidValue;
             // a lean launch has not loaded every pos.x / pos.z: it cannot fill another slab, test safe zones or pack the boundary
             if (fix_mode == FIX_LEAN && (So != S || P.bp_check != 0 || P.pack_out != nullptr)) return hipErrorInvalidValue;
             if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, true, true>);
             else if (opt == 3) launch(integrate_free<T, false, MWU, false, 3, true>);
-            else launch(integrate_free<T, false, 1, false, 1, true>);
+            else launch(integrate_free<T, false, MWU, false, 1, true>);
         } else if (P.ticks > 1) {
             if ((opt & OPT_UNI) && tf.on) launch(integrate_free<T, false, 1, true, OPT_UNI, false, true>);
             else if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);

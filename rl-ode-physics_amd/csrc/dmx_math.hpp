@@ -162,7 +162,11 @@ template <class T> DMX_HD bool invert3(M3<T> &d, const M3<T> &a)
 // reference's every body (m = 1, I = identity: AddBody leaves ODE's default mass, main.c:695-733), for which the formulas below
 // would only add the rounding of R I R^T and of the 3 x 3 solve.  The oracle has the same early-out.
 template <class T> DMX_HD bool isotropic(const V3<T> &Ib) { return Ib.x == Ib.y && Ib.y == Ib.z; }
-template <class T> DMX_HD void add_gyro_torque(V3<T> &tacc, const M3<T> &Iw, const V3<T> &w, T h, int mode)
+// hinv_of() = 1 / h, asked for where the implicit form needs it: divided on the spot (HinvDivides), or handed in by a launch whose
+// constants are kernel arguments and which has divided once, on the host (HinvGiven; dmx_launch_consts.hpp)
+template <class T> struct HinvDivides { T h;    DMX_HD T operator()() const { return T(1) / h; } };
+template <class T> struct HinvGiven   { T hinv; DMX_HD T operator()() const { return hinv; } };
+template <class T, class HINV> DMX_HD void add_gyro_torque(V3<T> &tacc, const M3<T> &Iw, const V3<T> &w, T h, int mode, HINV hinv_of)
 {
     V3<T> L = mulv(Iw, w);
     if (mode == 1) {
@@ -178,7 +182,7 @@ template <class T> DMX_HD void add_gyro_torque(V3<T> &tacc, const M3<T> &Iw, con
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) It.m[i][j] = fma_(It.m[i][j], h, Iw.m[i][j]);
-    T hinv = T(1) / h;
+    T hinv = hinv_of();
     L.x *= hinv; L.y *= hinv; L.z *= hinv;
     M3<T> inv;
     if (!invert3(inv, It)) return;
@@ -186,6 +190,10 @@ template <class T> DMX_HD void add_gyro_torque(V3<T> &tacc, const M3<T> &Iw, con
     P.m[0][0] -= 1; P.m[1][1] -= 1; P.m[2][2] -= 1;
     V3<T> tau = mulv(P, L);
     tacc.x += tau.x; tacc.y += tau.y; tacc.z += tau.z;
+}
+template <class T> DMX_HD void add_gyro_torque(V3<T> &tacc, const M3<T> &Iw, const V3<T> &w, T h, int mode)
+{
+    add_gyro_torque(tacc, Iw, w, h, mode, HinvDivides<T>{ h });
 }
 
 // q += h * 1/2 (0,w) (x) q ; renormalise

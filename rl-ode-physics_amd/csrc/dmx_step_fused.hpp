@@ -59,36 +59,78 @@ __device__ __forceinline__ void pack_boundary(const StepParams<T> &P, int64_t i,
 
 // ---------------------------------------------------------------------------------------------
 // One body's tick around the constraint solve: integrate_free (through free_body_step), step_plane_body and step_contacts call
-// these two functions, so what the tick computes for a body without rows is defined here, once.  The callers compute 1/m themselves,
-// the fused kernels ahead of the head and free_body_step as the tail's argument: that is where the statements stood, and it keeps
-// every kernel's code as it was (profiles/fused_dedup_resources.txt).
+// these two functions, so what the tick computes for a body without rows is defined here, once.  The fused kernels compute 1/m
+// themselves, ahead of the head; free_body_step asks its source of constants for hm = h * (1/m) where the tail needs it: that is where the
+// statements stood, and it keeps every kernel's code as it was (profiles/fused_dedup_resources.txt, profiles/launch_consts_resources.txt).
 //   facc = fext + m g ; tacc = text + gyro                   (tick_head)
 //   [ rows, sweeps: v += h M^-1 J^T lambda ]                  (the caller's)
 //   v += (h/m) facc ; w += Iw^-1 (h tacc)                     (tick_tail)
 //   x += h v ; q += h/2 (0,w) q ; q /= |q|
 // ---------------------------------------------------------------------------------------------
-// gravity into facc, the gyroscopic torque into tacc; the world-frame inverse inertia for the tail and for whoever builds rows
-template <class T>
-__device__ __forceinline__ void tick_head(const Q4<T> &q, const V3<T> &w, T mass, const V3<T> &Ib, V3<T> &facc, V3<T> &tacc,
-                                          const V3<T> &g, T h, int gyro, M3<T> &invIw)
+// What the tick makes of mass, inertia, h and g alone -- 1 / Ib.k, the isotropy test, 1 / h, hm = h * (1 / m), m g -- comes from one
+// of two sources, each asked at the place where the tick needs the value: TickDivides computes it on the spot, per lane, as every
+// tick did; TickGiven hands in what a launch of integrate_free whose constants are kernel arguments computed once on the host,
+// with the same operations (dmx_launch_consts.hpp, dmx_torque_free.hpp), and holds in scalar registers.
+template <class T> DMX_HD void add_gravity(V3<T> &facc, T mass, const V3<T> &g)
+{
+    facc.x = fma_(mass, g.x, facc.x); facc.y = fma_(mass, g.y, facc.y); facc.z = fma_(mass, g.z, facc.z);
+}
+template <class T> struct TickDivides {
+    T mass; V3<T> Ib; T h;
+    DMX_HD V3<T> invIb() const { return { T(1) / Ib.x, T(1) / Ib.y, T(1) / Ib.z }; }
+    DMX_HD void gravity(V3<T> &facc, const V3<T> &g) const { add_gravity(facc, mass, g); }
+    DMX_HD bool iso() const { return isotropic(Ib); }
+    DMX_HD HinvDivides<T> hinv_of() const { return { h }; }
+    DMX_HD T hm() const { return h * (T(1) / mass); }
+};
+// ACC: facc may hold a force accumulator, and gravity is added to it per lane; without, facc is (+0, +0, +0) and gravity is the
+// launch's mg.k = fma(m, g.k, +0)
+template <class T, bool ACC> struct TickGiven {
+    V3<T> inv_Ib; bool is_iso; T hinv, h_m, mass; V3<T> mg;
+    DMX_HD V3<T> invIb() const { return inv_Ib; }
+    DMX_HD void gravity(V3<T> &facc, const V3<T> &g) const { if (ACC) add_gravity(facc, mass, g); else facc = mg; }
+    DMX_HD bool iso() const { return is_iso; }
+    DMX_HD HinvGiven<T> hinv_of() const { return { hinv }; }
+    DMX_HD T hm() const { return h_m; }
+};
+
+// The head, defined once for both sources K: gravity into facc, the gyroscopic torque into tacc; the world-frame inverse inertia
+// for the tail and for whoever builds rows.  The host can compile it (tests/harness/launch_consts_harness.cpp).
+template <class T, class K>
+DMX_HD void tick_head_with(const Q4<T> &q, const V3<T> &w, const V3<T> &Ib, const K &k, V3<T> &facc, V3<T> &tacc,
+                           const V3<T> &g, T h, int gyro, M3<T> &invIw)
 {
     const M3<T> R = quat_to_R(q);
-    const V3<T> invIb = { T(1) / Ib.x, T(1) / Ib.y, T(1) / Ib.z };
-    facc.x = fma_(mass, g.x, facc.x); facc.y = fma_(mass, g.y, facc.y); facc.z = fma_(mass, g.z, facc.z);
+    const V3<T> invIb = k.invIb();
+    k.gravity(facc, g);
     invIw = rotate_diag(R, invIb);
-    if (gyro != 0 && !isotropic(Ib)) {
+    if (gyro != 0 && !k.iso()) {
         const M3<T> Iw = rotate_diag(R, Ib);
-        add_gyro_torque(tacc, Iw, w, h, gyro);
+        add_gyro_torque(tacc, Iw, w, h, gyro, k.hinv_of());
     }
 }
 
-// what the tail adds: hm = h / m, by which facc enters v, and dw = Iw^-1 (h tacc), which enters w
+// (the dividing form; its callers take 1 / m themselves, see above)
 template <class T>
-__device__ __forceinline__ void tick_tail_terms(T invMass, const M3<T> &invIw, V3<T> tacc, T h, T &hm, V3<T> &dw)
+DMX_HD void tick_head(const Q4<T> &q, const V3<T> &w, T mass, const V3<T> &Ib, V3<T> &facc, V3<T> &tacc,
+                      const V3<T> &g, T h, int gyro, M3<T> &invIw)
+{
+    tick_head_with(q, w, Ib, TickDivides<T>{ mass, Ib, h }, facc, tacc, g, h, gyro, invIw);
+}
+
+// what the tail adds to w: dw = Iw^-1 (h tacc)
+template <class T> DMX_HD V3<T> tick_tail_dw(const M3<T> &invIw, V3<T> tacc, T h)
+{
+    tacc.x *= h; tacc.y *= h; tacc.z *= h;
+    return mulv(invIw, tacc);
+}
+
+// what the tail adds: hm = h / m, by which facc enters v, and dw, which enters w
+template <class T>
+DMX_HD void tick_tail_terms(T invMass, const M3<T> &invIw, V3<T> tacc, T h, T &hm, V3<T> &dw)
 {
     hm = h * invMass;
-    tacc.x *= h; tacc.y *= h; tacc.z *= h;
-    dw = mulv(invIw, tacc);
+    dw = tick_tail_dw(invIw, tacc, h);
 }
 
 // v += h M^-1 f ; w += Iw^-1 (h tacc) ; integrate (dmx_math.hpp: tick_integrate, which the host can compile)
@@ -107,31 +149,39 @@ __device__ __forceinline__ void tick_tail(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w
 // tf_mg, computed once on the host with the head's and the tail's operations; neither R nor the inverse inertia is built.  Any other wavefront runs
 // head and tail as free_body_step does.  One ballot and one scalar branch; both ways meet in the one tick_integrate, which keeps the
 // kernels at the registers they had (profiles/torque_free_resources.txt).
+// The fallback is the general tick with the launch's constants handed in (TickGiven): hm and facc stay the launch's -- the very
+// h * (1 / m) and fma(m, g.k, 0) the dividing tick would compute -- so a wavefront on the short way executes nothing on behalf of
+// the other, and nothing is left for the compiler to hoist ahead of the loads.
 template <class T>
-__device__ __forceinline__ void free_body_step_torque_free(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T mass, const V3<T> &Ib,
-                                                           const V3<T> &g, T h, int gyro, int tf_on, T tf_hm, const V3<T> &tf_mg)
+__device__ __forceinline__ void free_body_step_torque_free(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, const V3<T> &Ib, const V3<T> &g,
+                                                           T h, int gyro, int tf_on, const TickGiven<T, false> &k)
 {
-    T hm = tf_hm;
-    V3<T> facc = tf_mg, dw = { T(0), T(0), T(0) };
+    V3<T> facc = k.mg, dw = { T(0), T(0), T(0) };
     if (!(tf_on && __ballot(!torque_free_admits(q)) == 0ull)) {
         M3<T> invIw;
         V3<T> tacc = { T(0), T(0), T(0) };
-        facc = { T(0), T(0), T(0) };
-        tick_head(q, w, mass, Ib, facc, tacc, g, h, gyro, invIw);
-        tick_tail_terms(T(1) / mass, invIw, tacc, h, hm, dw);
+        tick_head_with(q, w, Ib, k, facc, tacc, g, h, gyro, invIw);
+        dw = tick_tail_dw(invIw, tacc, h);
     }
-    tick_integrate(x, q, v, w, hm, facc, dw, h);
+    tick_integrate(x, q, v, w, k.hm(), facc, dw, h);
 }
 
-// a body without rows: head and tail, nothing between them
-template <class T>
-__device__ __forceinline__ void free_body_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w,
-                                               T mass, const V3<T> &Ib, V3<T> facc, V3<T> tacc,
-                                               const V3<T> &g, T h, int gyro)
+// a body without rows: head and tail, nothing between them; K as above
+template <class T, class K>
+DMX_HD void free_body_step_with(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, const V3<T> &Ib, V3<T> facc, V3<T> tacc, const V3<T> &g,
+                                T h, int gyro, const K &k)
 {
     M3<T> invIw;
-    tick_head(q, w, mass, Ib, facc, tacc, g, h, gyro, invIw);
-    tick_tail(x, q, v, w, T(1) / mass, invIw, facc, tacc, h);
+    tick_head_with(q, w, Ib, k, facc, tacc, g, h, gyro, invIw);
+    tick_integrate(x, q, v, w, k.hm(), facc, tick_tail_dw(invIw, tacc, h), h);
+}
+// ... and the form that divides, per lane
+template <class T>
+DMX_HD void free_body_step(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w,
+                           T mass, const V3<T> &Ib, V3<T> facc, V3<T> tacc,
+                           const V3<T> &g, T h, int gyro)
+{
+    free_body_step_with(x, q, v, w, Ib, facc, tacc, g, h, gyro, TickDivides<T>{ mass, Ib, h });
 }
 
 template <class T> __device__ __forceinline__ T wave_sum(T x)
