@@ -67,6 +67,11 @@ enum { DMX_GYRO_OFF = 0, DMX_GYRO_EXPLICIT = 1, DMX_GYRO_IMPLICIT = 2 };
 
 /* dContactBounce etc: surface mode bits accepted by dmxBatchSetSurface */
 enum { DMX_CONTACT_BOUNCE = 0x004 };
+/* dContactApprox1_1 / _2 / both: friction that scales with the normal force -- see dmxContactJoint.  dmxBatchSetSurface accepts the
+ * bits, but the ticks that find their own contacts (dmxBatchStep, dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick(s),
+ * dmxBatchExactTick) have not learnt them: while the batch surface would make a pyramid row (a bit set and 0 < mu < inf) they
+ * return DMX_EINVAL, say why on stderr and leave the state untouched. */
+enum { DMX_CONTACT_APPROX1_1 = 0x1000, DMX_CONTACT_APPROX1_2 = 0x2000, DMX_CONTACT_APPROX1 = 0x3000 };
 
 /* ---- lifecycle: dInitODE/dWorldCreate/dHashSpaceCreate/dJointGroupCreate (main.c:94-98) */
 int dmxDeviceCount(void);                 /* >=1 or DMX_ENODEVICE; never touches a CPU path */
@@ -327,9 +332,28 @@ int dmxBatchSetRayForm(dmxBatchID b, int form);
 typedef struct dmxContactJoint {
     double pos[3], normal[3], depth;      /* dContactGeom */
     int32_t body1, body2;                 /* body slots, -1 = none */
-    int32_t mode;                         /* dContactBounce | dContactSoftERP | dContactSoftCFM */
+    int32_t mode;                         /* dContactBounce | dContactSoftERP | dContactSoftCFM | DMX_CONTACT_APPROX1_1 / _2 (below) */
     double mu, bounce, bounce_vel, soft_erp, soft_cfm;   /* dSurfaceParameters (main.c:684-687) */
 } dmxContactJoint;
+/* Friction (dContactApprox1).  By default a contact's friction rows are box-bounded, lo = -mu, hi = +mu: mu is a FORCE, ODE's
+ * default.  Friction row d (1 or 2) of a contact joint is a PYRAMID ROW when bit DMX_CONTACT_APPROX1_d of its mode is set and
+ * 0 < mu < +inf: its bound is mu times the contact's normal force, and mu is the friction coefficient.  Every other row is what it
+ * is without the bits: mu = +inf with a bit set is the unbounded row (ODE's |inf * 0| would be NaN), mu <= 0 still makes one row.
+ * Row count, row order (creation order, a contact's friction rows directly behind its normal row), island building and the set of
+ * rows that can never clamp depend on mu alone, not on the bits.  ODE's dContactApprox1_N (0x4000, rolling friction) has no meaning:
+ * there are no rolling rows; there is no field for dContactMu2 or dContactFDir1.
+ *   QuickStep (DMX_STEPPER_QUICK, DMX_ORDER_CREATION): when a sweep visits a pyramid row, hi = |mu lambda_n|, lo = -hi, lambda_n = the
+ *     CURRENT multiplier of the contact's normal row, already updated in this sweep (ODE's SOR_LCP); nothing else about the update
+ *     changes.  ODE moves such rows to the end of its row order; this library keeps creation order.  Under DMX_ORDER_ODE with
+ *     QuickStep a tick with a pyramid row returns DMX_EINVAL (one line on stderr, the state untouched), as with articulation joints.
+ *   dWorldStep (DMX_STEPPER_EXACT): this library's definition -- an island with a pyramid row is solved twice: pass A is the box LCP
+ *     with every pyramid row held at lo = hi = 0 and yields lambda^A; pass B is the box LCP with the pyramid rows bounded by
+ *     -/+ mu lambda^A_n and yields the lambda the tick and the feedback use.  (What ODE's Dantzig solver does for the first friction
+ *     row it adds -- the bound from the normal force of the friction-free solution -- made independent of the row order.)  Both
+ *     passes are positive definite box LCPs with unique solutions.  An island without a pyramid row is solved once, as before.
+ *   Feedback (dmxBatchContactFeedback) is J^T lambda of the final lambda.
+ *   The single-launch tick honours pyramid rows under QuickStep; under dWorldStep a tick with a pyramid row takes the general path,
+ *   whole, and counts under DMX_SMALL_TICK_STAT_LDS_FIT. */
 int dmxBatchStepJoints(dmxBatchID b, double h, int64_t n_joints, const dmxContactJoint *joints);
 /* Which of ODE's two steppers dmxBatchStepJoints is.  DMX_STEPPER_QUICK (default): dWorldQuickStep, QuickStep's SOR sweeps.
  * DMX_STEPPER_EXACT: dWorldStep, the reference's own call (main.c:213): every island's system
@@ -360,7 +384,9 @@ int dmxBatchLcpStats(dmxBatchID b, int64_t out[8]);
 #define DMX_SMALL_TICK_AUTO  1   /* default: when the tick is eligible */
 int dmxBatchSetSmallTick(dmxBatchID b, int mode);
 /* Counters since the batch was created: ticks on the single-launch path, ticks of dmxBatchStepJoints on the general path,
- * then per reason the ticks that were not eligible (a tick counts under the first reason that applies, in this order). */
+ * then per reason the ticks that were not eligible (a tick counts under the first reason that applies, in this order).
+ * DMX_SMALL_TICK_STAT_LDS_FIT also counts the dWorldStep ticks that have a pyramid row (DMX_CONTACT_APPROX1): their two passes are
+ * the general path's. */
 enum {
     DMX_SMALL_TICK_STAT_SMALL = 0, DMX_SMALL_TICK_STAT_GENERAL = 1, DMX_SMALL_TICK_STAT_MODE = 2, DMX_SMALL_TICK_STAT_ROW_ORDER = 3,
     DMX_SMALL_TICK_STAT_SUBSET = 4, DMX_SMALL_TICK_STAT_BODIES = 5, DMX_SMALL_TICK_STAT_ISLANDS = 6, DMX_SMALL_TICK_STAT_SOR_ROWS = 7,

@@ -23,6 +23,7 @@ STEPPER_QUICK, STEPPER_EXACT = 0, 1
 ORDER_CREATION, ORDER_ODE = 0, 1
 BODY_ALIVE, BODY_KINEMATIC, BODY_NOGRAVITY, BODY_NOGYRO = 1, 2, 4, 8
 CONTACT_SOFT_ERP, CONTACT_SOFT_CFM = 0x008, 0x010
+CONTACT_APPROX1_1, CONTACT_APPROX1_2, CONTACT_APPROX1 = 0x1000, 0x2000, 0x3000      # friction bounded by mu times the normal force
 # dmxContactJoint (include/dmx_batch.h): the C layout, padding included (tests/test_solver_dense.py checks it with offsetof)
 CONTACT_JOINT_DTYPE = np.dtype({
     "names": ["pos", "normal", "depth", "body1", "body2", "mode", "mu", "bounce", "bounce_vel", "soft_erp", "soft_cfm"],

@@ -424,6 +424,7 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
     if (!b || !(h > 0) || nsteps < 0) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStep")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStep")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchStep")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -678,6 +679,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
     if (!b || !(h > 0)) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchChunkTick")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -688,6 +690,7 @@ extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_
     if (!b || !(h > 0) || nticks < 0) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -749,6 +752,7 @@ extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
     if (!b || !(h > 0)) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchExactTick")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchExactTick")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchExactTick")) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
@@ -853,6 +857,7 @@ extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t 
     if (!b || !(h > 0) || first < 0 || count < 0 || first + count > b->n_active) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStepRange")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStepRange")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchStepRange")) return DMX_EINVAL;
     SETTLE(b);
     // lanes own 16 B packs of consecutive bodies: ranges must start on a pack and end on one (or at the end)
     const int64_t pack = 16 / (int64_t)b->rsize;
@@ -897,6 +902,7 @@ extern "C" int dmxBatchStepTimed(dmxBatchID b, double h, int nsteps, float *ms)
     if (!b || !ms) return DMX_EINVAL;
     if (dmx_refuse_joints(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStepTimed")) return DMX_EINVAL;
+    if (dmx_refuse_approx1(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     int rc = dmxBatchStep(b, h, nsteps);

@@ -239,6 +239,15 @@ inline bool dmx_refuse_flags(const dmxBatch *b, const char *what)
             what, (long long)b->n_flagged);
     return true;
 }
+// ... nor friction bounded by the normal force (DMX_CONTACT_APPROX1 in the batch surface, dmxBatchSetSurface): their fused kernels bound
+// friction rows by mu newtons.  While the surface would make a pyramid row -- a bit set and 0 < mu < inf -- they refuse.
+inline bool dmx_refuse_approx1(const dmxBatch *b, const char *what)
+{
+    if (!(b->surf_mode & DMX_CONTACT_APPROX1) || !(b->mu > 0 && b->mu < __builtin_huge_val())) return false;
+    fprintf(stderr, "libode_mi355: %s does not honour friction bounded by the normal force (DMX_CONTACT_APPROX1 in dmxBatchSetSurface, mu = %g); use dmxBatchStepJoints\n",
+            what, b->mu);
+    return true;
+}
 // A launch recorded into a HIP graph would bake the uniform constants' VALUES in, and replays would keep them after a later
 // upload of another mass while eager ticks use the new one: launches recorded during a capture read the constants from the
 // slab.  Asked once per stepping call of the C ABI (the entry points that can reach integrate_free), not per tick.

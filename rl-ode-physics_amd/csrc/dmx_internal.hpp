@@ -54,6 +54,8 @@ __host__ __device__ __forceinline__ bool classes_collide(int a, int b, uint32_t 
 }
 constexpr int CONVEX_MAXC = 8;      // contact slots per convex body per tick (the reference's MAX_CONTACTS, main.c:675)
 enum : int { SURF_BOUNCE = 0x004, SURF_SOFT_ERP = 0x008, SURF_SOFT_CFM = 0x010 };
+// DMX_CONTACT_APPROX1_1 / _2: friction row 1 / 2 is bounded by mu times the contact's normal force (include/dmx_batch.h)
+enum : int { SURF_APPROX1_1 = 0x1000, SURF_APPROX1_2 = 0x2000, SURF_APPROX1 = 0x3000 };
 // per-slot body flags (uint8 array)
 enum : int { BF_ALIVE = 1, BF_KINEMATIC = 2, BF_NOGRAVITY = 4, BF_NOGYRO = 8 };
 
@@ -257,7 +259,7 @@ template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
 }
 template <class T>
 hipError_t launch_islands(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
-                          StepDiag *diag, hipStream_t st, bool feedback = false);      // (feedback: the kernels' FB instantiations)
+                          StepDiag *diag, hipStream_t st, bool feedback = false, bool pyramid = false);      // (feedback, pyramid: the kernels' FB / APX instantiations)
 // feedback of a dmxBatchStepJoints tick on the general path (dmx_artic.hip): one lane per entry, behind the tick's solves
 template <class T>
 hipError_t launch_feedback(const IslandSet<T> &I, const StepParams<T> &P, const FeedbackSet<T> &F, int n_entries, hipStream_t st);

@@ -16,6 +16,10 @@ namespace dmx {
 enum : int { RW_J = 0, RW_IMJ = 12, RW_RHS = 24, RW_AD = 25, RW_LO = 26, RW_HI = 27, RW_LAM = 28, RW_COUNT = ISLAND_ROW_REALS };
 // the first of the three spare reals: in a tick made with feedback on (the FB instantiations) QuickStep's row_setup leaves the factor Ad it scaled J by here
 enum : int { RW_UNSCALE = 29 };
+// the other two, in a tick with pyramid rows (DMX_CONTACT_APPROX1; the APX instantiations, which alone write and read them): RW_FMU =
+// mu on a pyramid row, -1 on the normal row of a contact that has one, 0 on every other row; RW_FDIR = the pyramid row's direction
+// (1 or 2): its contact's normal row is that many rows before it
+enum : int { RW_FMU = 30, RW_FDIR = 31 };
 static_assert(RW_COUNT >= 29 && RW_COUNT % 4 == 0, "a row is read in 16-byte pieces");
 // per island-body scratch layout (reals)
 enum : int { BW_INVI = 0, BW_FACC = 9, BW_TACC = 12, BW_INVM = 15, BW_FC = 16, BW_TMP = 22, BW_COUNT = 28 };
@@ -31,7 +35,7 @@ template <class T> DMX_HD V3<T> ldS(const T *S, int64_t stride, int c0, int s)
 
 // ---- stage 0, body k of the island: gravity, world-frame inverse inertia, gyroscopic torque ---------------
 template <class T>
-__device__ __forceinline__ void stage_body(const T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I,
+DMX_HD void stage_body(const T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I,
                                            const StepParams<T> &P, T *b, int s, int k)
 {
     I.local[s] = k;
@@ -77,7 +81,7 @@ template <class T> __device__ __forceinline__ int contact_rpc(const IslandSet<T>
     if (I.has_units && mu < 0) return unit_rows_of(mu);
     return mu > 0 ? 3 : 1;
 }
-template <class T> __device__ __forceinline__ bool contact_is_unit(const IslandSet<T> &I, int ci)
+template <class T> DMX_HD bool contact_is_unit(const IslandSet<T> &I, int ci)
 {
     return I.has_units && I.cmu[ci] < 0;
 }
@@ -424,14 +428,20 @@ DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, co
 // ---- rows of contact ci (normal + 2 friction when mu > 0), written at island-relative row m -----------------
 // RPCK = 3: the caller knows the contact has friction rows (constant trip counts: a caller that hands in thread-local
 // arrays gets them in registers)
-template <class T, int RPCK = 0>
-__device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
+// APX (a tick with at least one pyramid row, DMX_CONTACT_APPROX1: its own instantiation, as FB is): friction row d of a contact whose
+// mode has DMX_CONTACT_APPROX1_d and whose mu is positive and finite is marked (RW_FMU, RW_FDIR) and built with lo = hi = 0 -- what
+// dWorldStep's pass A solves; QuickStep's sweeps and dWorldStep's pass B make its bounds from the normal row's multiplier -- and
+// every other row of the tick gets RW_FMU <= 0
+// (host too: tests/harness/friction_sweep_harness.cpp)
+template <class T, int RPCK = 0, bool APX = false>
+DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                              T *rows, int *jb, int ci, int m, T hinv)
 {
     if (RPCK == 0 && contact_is_unit(I, ci)) {
         if (I.cmu[ci] == T(UNIT_LIMOT_MU)) (void)limot_unit_row(S, I, P, rows, jb, ci, m, hinv);
         else if (I.cmu[ci] <= T(UNIT_SLIDER2_MU)) (void)slider_linear_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
         else (void)joint_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
+        if (APX) for (int r = 0; r < unit_rows_of(I.cmu[ci]); r++) rows[(size_t)(m + r) * RW_COUNT + RW_FMU] = T(0);
         return;
     }
     const int s1 = I.cb1[ci], s2 = I.cb2[ci];
@@ -455,6 +465,7 @@ __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const I
     V3<T> dir[3];
     dir[0] = normal;
     if (rpc == 3) plane_space(normal, dir[1], dir[2]);
+    const int pyr = (APX && rpc == 3 && mu < Limits<T>::inf()) ? (mode & SURF_APPROX1) : 0;      // bit SURF_APPROX1_d: row d is a pyramid row
 #pragma unroll
     for (int dnum = 0; dnum < rpc; dnum++) {
         T *row = rows + (size_t)(m + dnum) * RW_COUNT;
@@ -487,8 +498,14 @@ __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const I
                 }
             }
             row[RW_LO] = T(0); row[RW_HI] = Limits<T>::inf();
+            if (APX) row[RW_FMU] = pyr ? T(-1) : T(0);
         } else {
             row[RW_LO] = -mu; row[RW_HI] = mu;
+            if (APX) {
+                const bool p = (pyr & (SURF_APPROX1_1 << (dnum - 1))) != 0;
+                if (p) { row[RW_LO] = T(0); row[RW_HI] = T(0); }
+                row[RW_FMU] = p ? mu : T(0); row[RW_FDIR] = T(dnum);
+            }
         }
         row[RW_RHS] = cval;     // c for now
         row[RW_AD] = cfm;       // cfm for now
@@ -498,7 +515,7 @@ __device__ __forceinline__ void contact_rows(const T *S, int64_t stride, const I
 
 // ---- v/h + M^-1 f of body k ------------------------------------------------------------------------------------
 template <class T>
-__device__ __forceinline__ void body_tmp(const T *S, int64_t stride, T *b, int s, T hinv)
+DMX_HD void body_tmp(const T *S, int64_t stride, T *b, int s, T hinv)
 {
     const T im = b[BW_INVM];
     const V3<T> v = ldS(S, stride, C_LVEL, s), w = ldS(S, stride, C_AVEL, s);
@@ -588,8 +605,16 @@ DMX_HD void joint_feedback(const IslandSet<T> &I, const StepParams<T> &P, const 
 }
 
 // ---- one SOR row update; returns |delta lambda| -----------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ T row_sor(T *rows, const int *jb, T *bs, int i)
+// The bounds of a pyramid row (RW_FMU > 0) when a sweep visits it: -/+ |mu lambda_n|, lambda_n = the multiplier of its contact's normal
+// row as it stands (rows in creation order: already updated in this sweep).  One spelling for every SOR form.
+template <class T> DMX_HD void pyramid_bounds(T fmu, T lam_n, T &lo, T &hi)
+{
+    hi = tabs(fmu * lam_n);
+    lo = -hi;
+}
+// APX: see contact_rows (host too: tests/harness/friction_sweep_harness.cpp)
+template <class T, bool APX = false>
+DMX_HD T row_sor(T *rows, const int *jb, T *bs, int i)
 {
     T *row = rows + (size_t)i * RW_COUNT;
     const T *J = row + RW_J, *iMJ = row + RW_IMJ;
@@ -601,7 +626,11 @@ __device__ __forceinline__ T row_sor(T *rows, const int *jb, T *bs, int i)
     delta -= fma_(fc1[5], J[5], fma_(fc1[4], J[4], fma_(fc1[3], J[3], fma_(fc1[2], J[2], fma_(fc1[1], J[1], fc1[0] * J[0])))));
     if (fc2)
         delta -= fma_(fc2[5], J[11], fma_(fc2[4], J[10], fma_(fc2[3], J[9], fma_(fc2[2], J[8], fma_(fc2[1], J[7], fc2[0] * J[6])))));
-    const T lo = row[RW_LO], hi = row[RW_HI];
+    T lo = row[RW_LO], hi = row[RW_HI];
+    if (APX) {
+        const T fmu = row[RW_FMU];
+        if (fmu > T(0)) pyramid_bounds(fmu, rows[(size_t)(i - (int)row[RW_FDIR]) * RW_COUNT + RW_LAM], lo, hi);
+    }
     const T nl = old + delta;
     if (nl < lo) { delta = lo - old; row[RW_LAM] = lo; }
     else if (nl > hi) { delta = hi - old; row[RW_LAM] = hi; }
@@ -685,7 +714,7 @@ __device__ __forceinline__ T row_sor_lds(T *rows, RowRegs<T> &r, T *fc, bool eag
 
 // ---- body k: v += h cforce ; v += h M^-1 f ; integrate ; clear accumulators -------------------------------------
 template <class T>
-__device__ __forceinline__ void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b, int s, bool has_rows, T h)
+DMX_HD void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b, int s, bool has_rows, T h)
 {
     V3<T> x = ldS(S, stride, C_POS, s);
     Q4<T> q = { S[slab_ix(C_QUAT + 0, s)], S[slab_ix(C_QUAT + 1, s)],

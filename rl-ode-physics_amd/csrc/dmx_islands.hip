@@ -40,20 +40,20 @@ __global__ __launch_bounds__(64) void solve_singles_lds(T *__restrict__ S, const
     const int lanes = blockDim.x, lane = threadIdx.x;
     solve_singles_lds_body<T>(S, bflags, stride, I, P, diag, (int)(blockIdx.x * lanes + lane), lanes, lane);
 }
-template <class T, bool FB = false>
+template <class T, bool FB = false, bool APX = false>
 __global__ __launch_bounds__(64) void solve_islands(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                     int64_t stride, IslandSet<T> I, StepParams<T> P,
                                                     StepDiag *__restrict__ diag)
 {
-    solve_islands_body<T, FB>(S, bflags, stride, I, P, diag, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+    solve_islands_body<T, FB, APX>(S, bflags, stride, I, P, diag, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
-template <class T, int WG, bool REGS = false, bool FB = false>
+template <class T, int WG, bool REGS = false, bool FB = false, bool APX = false>
 __global__ __launch_bounds__(WG) void solve_island_wg(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                       int64_t stride, IslandSet<T> I, StepParams<T> P,
                                                       StepDiag *__restrict__ diag, int lds_bodies, const ExactCounts *__restrict__ dc,
                                                       int sched_ints)
 {
-    solve_island_wg_body<T, WG, REGS, FB>(S, bflags, stride, I, P, diag, lds_bodies, dc, sched_ints, blockIdx.x, gridDim.x);
+    solve_island_wg_body<T, WG, REGS, FB, APX>(S, bflags, stride, I, P, diag, lds_bodies, dc, sched_ints, blockIdx.x, gridDim.x);
 }
 // The tail of a small-scene exact tick in ONE launch: workgroups [0, max_big) are solve_island_wg<64>'s (speculative form: they ask
 // the device's record whether their island exists), the workgroups behind them step 64 bodies each of everyone else with the fused
@@ -85,14 +85,16 @@ hipError_t launch_islands_without_rows(T *S, const uint8_t *bflags, int64_t stri
 }
 
 // FB: a tick made with feedback on launches the FB instantiations (row_setup leaves Ad in the rows; I.singles is 0 then)
-template <class T, bool FB>
+// APX: a tick with pyramid rows (DMX_CONTACT_APPROX1) launches the APX instantiations, which are made with FB's store on and so
+// serve it with feedback on or off (I.singles is 0 then too: the one-body forms know box friction only)
+template <class T, bool FB, bool APX = false>
 static hipError_t launch_islands_fb(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                     StepDiag *diag, hipStream_t st)
 {
     if (I.n_islands <= 0) return hipSuccess;
     if (I.n_big < I.n_islands) {
         const unsigned grid = (unsigned)((I.n_islands + 63) / 64);
-        hipLaunchKernelGGL((solve_islands<T, FB>), dim3(grid), dim3(64), 0, st, S, bflags, stride, I, P, diag);
+        hipLaunchKernelGGL((solve_islands<T, FB, APX>), dim3(grid), dim3(64), 0, st, S, bflags, stride, I, P, diag);
         if (I.singles) {
             hipLaunchKernelGGL((solve_singles<T>), dim3(grid), dim3(64), 0, st, S, bflags, stride, I, P, diag);
             // islands of 5..8 contacts keep their rows' J and M^-1 J^T in LDS: 64 lanes x 24 rows x 12 fields (f32: 72 KB, two waves
@@ -126,11 +128,19 @@ static hipError_t launch_islands_fb(T *S, const uint8_t *bflags, int64_t stride,
             static const bool by_contact = [] { const char *e = getenv("DMX_REGS_BY_CONTACT"); return !(e && atoi(e) == 0); }();
             const int scratch = by_contact && sizeof(T) == 4 ? REGS_ROWS<T> / 3 : 0;
             lds += (size_t)scratch * sizeof(int);
-            if (regs_wg == 512 && sizeof(T) == 4 && I.big_max_rows > 1024)
-                hipLaunchKernelGGL((solve_island_wg<T, 512, true, FB>), dim3((unsigned)I.n_big), dim3(512), lds, st, S, bflags, stride, I, P, diag, lds_bodies,
+            // (a tick with pyramid rows takes the 256-thread form throughout: the 512-thread form's APX instantiation needs 256 VGPRs and
+            //  spills, and nothing has measured it; its one word per row of static LDS on top of the accumulators can pass the 64 KB a
+            //  launch gets unasked, hence the attribute)
+            if constexpr (APX) {
+                const hipError_t ea = hipFuncSetAttribute((const void *)&solve_island_wg<T, 256, true, FB, APX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (ea != hipSuccess) return ea;
+                hipLaunchKernelGGL((solve_island_wg<T, 256, true, FB, APX>), dim3((unsigned)I.n_big), dim3(256), lds, st, S, bflags, stride, I, P, diag, lds_bodies,
+                                   (const ExactCounts *)nullptr, scratch);
+            } else if (regs_wg == 512 && sizeof(T) == 4 && I.big_max_rows > 1024)
+                hipLaunchKernelGGL((solve_island_wg<T, 512, true, FB, APX>), dim3((unsigned)I.n_big), dim3(512), lds, st, S, bflags, stride, I, P, diag, lds_bodies,
                                    (const ExactCounts *)nullptr, scratch);
             else
-                hipLaunchKernelGGL((solve_island_wg<T, 256, true, FB>), dim3((unsigned)I.n_big), dim3(256), lds, st, S, bflags, stride, I, P, diag, lds_bodies,
+                hipLaunchKernelGGL((solve_island_wg<T, 256, true, FB, APX>), dim3((unsigned)I.n_big), dim3(256), lds, st, S, bflags, stride, I, P, diag, lds_bodies,
                                    (const ExactCounts *)nullptr, scratch);
         } else {
             // room for an island's level schedule behind the accumulators (offsets + row lists; big_rows_total bounds any one island's):
@@ -139,22 +149,23 @@ static hipError_t launch_islands_fb(T *S, const uint8_t *bflags, int64_t stride,
             int sched_ints = 0;
             if (sched > 0 && lds + sched * sizeof(int) <= (size_t)96 * 1024 && I.n_big <= 64) { sched_ints = (int)sched; lds += sched * sizeof(int); }
             if (lds > (size_t)64 * 1024) {
-                const void *fn = I.big_max_width <= 64 ? (const void *)&solve_island_wg<T, 64, false, FB> : (const void *)&solve_island_wg<T, 256, false, FB>;
+                const void *fn = I.big_max_width <= 64 ? (const void *)&solve_island_wg<T, 64, false, FB, APX> : (const void *)&solve_island_wg<T, 256, false, FB, APX>;
                 const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (ea != hipSuccess) return ea;
             }
             if (I.big_max_width <= 64)      // no level has more than 64 rows: one wavefront per island, barriers cost nothing
-                hipLaunchKernelGGL((solve_island_wg<T, 64, false, FB>), dim3((unsigned)I.n_big), dim3(64), lds, st, S, bflags, stride, I, P, diag, lds_bodies, (const ExactCounts *)nullptr, sched_ints);
+                hipLaunchKernelGGL((solve_island_wg<T, 64, false, FB, APX>), dim3((unsigned)I.n_big), dim3(64), lds, st, S, bflags, stride, I, P, diag, lds_bodies, (const ExactCounts *)nullptr, sched_ints);
             else
-                hipLaunchKernelGGL((solve_island_wg<T, 256, false, FB>), dim3((unsigned)I.n_big), dim3(256), lds, st, S, bflags, stride, I, P, diag, lds_bodies, (const ExactCounts *)nullptr, sched_ints);
+                hipLaunchKernelGGL((solve_island_wg<T, 256, false, FB, APX>), dim3((unsigned)I.n_big), dim3(256), lds, st, S, bflags, stride, I, P, diag, lds_bodies, (const ExactCounts *)nullptr, sched_ints);
         }
     }
     return hipGetLastError();
 }
 template <class T>
 hipError_t launch_islands(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
-                          StepDiag *diag, hipStream_t st, bool feedback)
+                          StepDiag *diag, hipStream_t st, bool feedback, bool pyramid)
 {
+    if (pyramid) return launch_islands_fb<T, true, true>(S, bflags, stride, I, P, diag, st);
     return feedback ? launch_islands_fb<T, true>(S, bflags, stride, I, P, diag, st) : launch_islands_fb<T, false>(S, bflags, stride, I, P, diag, st);
 }
 
@@ -203,9 +214,9 @@ template hipError_t launch_islands_without_rows<float>(float *, const uint8_t *,
 template hipError_t launch_islands_without_rows<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &,
                                                         const StepParams<double> &, StepDiag *, hipStream_t);
 template hipError_t launch_islands<float>(float *, const uint8_t *, int64_t, const IslandSet<float> &,
-                                          const StepParams<float> &, StepDiag *, hipStream_t, bool);
+                                          const StepParams<float> &, StepDiag *, hipStream_t, bool, bool);
 template hipError_t launch_islands<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &,
-                                           const StepParams<double> &, StepDiag *, hipStream_t, bool);
+                                           const StepParams<double> &, StepDiag *, hipStream_t, bool, bool);
 
 // HIP loads a translation unit's code object at the first launch of one of its kernels -- a couple of milliseconds each, which an
 // interactive caller would meet as a hitch at the first tick that needs the exact pipeline.  dmxBatchCreate asks for one

@@ -305,7 +305,10 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
 // ================================================================================ one lane per island
 // FB: a tick made with feedback on (dmxBatchSetFeedback) -- row_setup also leaves what entry_feedback needs.  An instantiation of
 // its own, here and in solve_island_wg_body, so that a tick without feedback runs the code it ran before feedback existed.
-template <class T, bool FB = false>
+// APX: a tick with pyramid rows (DMX_CONTACT_APPROX1) -- contact_rows marks them, row_sor makes their bounds from the normal row's
+// multiplier.  Again an instantiation of its own, here and in solve_island_wg_body; the host launches it with FB's store on, so one
+// kernel serves such a tick with feedback on or off.
+template <class T, bool FB = false, bool APX = false>
 __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                    int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                    StepDiag *__restrict__ diag, int isl)
@@ -324,7 +327,7 @@ __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint
     for (int k = 0; k < nb; k++) stage_body(S, bflags, stride, I, P, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], k);
     int m = 0;
     for (int c = 0; c < nc; c++) {
-        contact_rows(S, stride, I, P, rows, jb, c0 + c, m, hinv);
+        contact_rows<T, 0, APX>(S, stride, I, P, rows, jb, c0 + c, m, hinv);
         m += contact_rpc(I, P, c0 + c);
     }
     double resid = 0.0;
@@ -335,7 +338,7 @@ __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint
             const bool last = (it == P.iters - 1);
             const int *ord = I.order != nullptr ? I.order + (size_t)(it >> 3) * I.order_stride + r0 : nullptr;
             for (int i = 0; i < m; i++) {
-                const T d = row_sor(rows, jb, bs, ord != nullptr ? ord[i] : i);
+                const T d = row_sor<T, APX>(rows, jb, bs, ord != nullptr ? ord[i] : i);
                 if (last) resid += (double)d;
             }
         }
@@ -384,10 +387,31 @@ __device__ __forceinline__ bool assign_row_slots(int nrow, int lane, short *tab,
     return ok;
 }
 
+// Pyramid rows (DMX_CONTACT_APPROX1) in the forms that keep a row in its owner's registers: the normal row of a contact and its
+// friction rows share both bodies, so they sit on consecutive levels with a barrier between -- the normal row's owner leaves its
+// multiplier in one LDS word (lamn[its row]) after every update, and a pyramid row's owner makes its bounds from that word before
+// it updates its row: pyramid_bounds, row_sor's own spelling, then row_sor_lds as it is.  Per slot: fmu = RW_FMU of the row it holds,
+// nrow = the row of the contact's normal.  Only the APX instantiations have one.
+template <class T, int RPL> struct PyrSlots { T fmu[RPL]; int nrow[RPL]; T *lamn; };
+template <class T, int RPL>
+__device__ __forceinline__ void pyr_slot_load(PyrSlots<T, RPL> &p, int j, const T *rows, int r)
+{
+    p.fmu[j] = rows[(size_t)r * RW_COUNT + RW_FMU];
+    p.nrow[j] = p.fmu[j] > T(0) ? r - (int)rows[(size_t)r * RW_COUNT + RW_FDIR] : r;
+}
+template <class T, int RPL, bool APX>
+__device__ __forceinline__ T row_sor_slot(RowRegs<T> &r, T *fc, bool eager, const PyrSlots<T, RPL> *p, int j)
+{
+    if (APX) { if (p->fmu[j] > T(0)) pyramid_bounds(p->fmu[j], p->lamn[p->nrow[j]], r.lo, r.hi); }
+    const T d = row_sor_lds<T, false>(nullptr, r, fc, eager);
+    if (APX) { if (p->fmu[j] < T(0)) p->lamn[r.row] = r.lam; }
+    return d;
+}
+
 // One sweep of the wavefront's rows.  classed: slot lv mod RPL holds every row of level lv (assign_row_slots).
-template <class T, int RPL, bool LAST>
+template <class T, int RPL, bool LAST, bool APX = false>
 __device__ __forceinline__ void wave_sweep(RowRegs<T> (&mine)[RPL], const int (&my_level)[RPL], int nlev, bool classed, T *fc_lds, bool eager,
-                                           double &resid)
+                                           double &resid, const PyrSlots<T, RPL> *pyr = nullptr)
 {
     if (classed) {
         for (int lv0 = 0; lv0 < nlev; lv0 += RPL) {
@@ -395,7 +419,7 @@ __device__ __forceinline__ void wave_sweep(RowRegs<T> (&mine)[RPL], const int (&
             for (int j = 0; j < RPL; j++) {
                 if (lv0 + j < nlev) {
                     if (my_level[j] == lv0 + j) {
-                        const T d = row_sor_lds<T, false>(nullptr, mine[j], fc_lds, eager);
+                        const T d = row_sor_slot<T, RPL, APX>(mine[j], fc_lds, eager, pyr, j);
                         if (LAST) resid += (double)d;
                     }
                     __syncthreads();
@@ -407,7 +431,7 @@ __device__ __forceinline__ void wave_sweep(RowRegs<T> (&mine)[RPL], const int (&
 #pragma unroll
             for (int j = 0; j < RPL; j++)
                 if (my_level[j] == lv) {
-                    const T d = row_sor_lds<T, false>(nullptr, mine[j], fc_lds, eager);
+                    const T d = row_sor_slot<T, RPL, APX>(mine[j], fc_lds, eager, pyr, j);
                     if (LAST) resid += (double)d;
                 }
             __syncthreads();
@@ -418,9 +442,9 @@ __device__ __forceinline__ void wave_sweep(RowRegs<T> (&mine)[RPL], const int (&
 // The sweeps of a small island by one wavefront (the first, if the launch has four): every row is OWNED by a lane and stays
 // in that lane's registers, RPL rows per lane; a level step is "lanes whose row is in this level update it"; between two
 // barriers only the bodies' accumulators in LDS are touched.  Returns the lane's share of the last sweep's residual.
-template <class T, int RPL>
+template <class T, int RPL, bool APX = false>
 __device__ __forceinline__ double wave_island_sweeps(T *rows, const int *jb, const int *row_level, int m, int nlev, int iters, int tid,
-                                                     T *fc_lds, bool eager)
+                                                     T *fc_lds, bool eager, T *lamn = nullptr)
 {
     __shared__ short tab[RPL * 64];
     __shared__ int tab_classed;
@@ -441,8 +465,20 @@ __device__ __forceinline__ double wave_island_sweeps(T *rows, const int *jb, con
     }
     __syncthreads();
     double resid = 0.0;
+    if constexpr (APX) {
+        PyrSlots<T, RPL> pyr;
+        pyr.lamn = lamn;
+#pragma unroll
+        for (int j = 0; j < RPL; j++) {
+            pyr.fmu[j] = T(0); pyr.nrow[j] = 0;
+            if (my_level[j] >= 0) pyr_slot_load(pyr, j, rows, mine[j].row);
+        }
+        for (int it = 0; it + 1 < iters; it++) wave_sweep<T, RPL, false, true>(mine, my_level, nlev, classed, fc_lds, eager, resid, &pyr);
+        if (iters > 0) wave_sweep<T, RPL, true, true>(mine, my_level, nlev, classed, fc_lds, eager, resid, &pyr);
+    } else {
     for (int it = 0; it + 1 < iters; it++) wave_sweep<T, RPL, false>(mine, my_level, nlev, classed, fc_lds, eager, resid);
     if (iters > 0) wave_sweep<T, RPL, true>(mine, my_level, nlev, classed, fc_lds, eager, resid);      // the last sweep also sums its |delta lambda|
+    }
 #pragma unroll
     for (int j = 0; j < RPL; j++)
         if (my_level[j] >= 0) rows[(size_t)mine[j].row * RW_COUNT + RW_LAM] = mine[j].lam;
@@ -609,9 +645,9 @@ template <class T, int WG> constexpr int REGS_ROWS_PER_THREAD = REGS_ROWS<T> / W
 // general form -- makes every level step one L2 round trip long: 0.9 us in the reference's pen, 45 levels x 20 sweeps.)  A level's
 // rows are consecutive positions, so they sit in at most two of a thread's slots (one, if the level is no wider than what is
 // left of the slot): a wavefront runs one or two row updates per level, not RPL.  Returns the thread's share of the last sweep's residual.
-template <class T, int RPL, int WG>
+template <class T, int RPL, int WG, bool APX = false>
 __device__ __forceinline__ double wg_island_sweeps(T *rows, const int *jb, const int *row_level, const int *lev_rows, int m, int nlev, int iters,
-                                                   int tid, T *fc_lds)
+                                                   int tid, T *fc_lds, T *lamn = nullptr)
 {
     RowRegs<T> mine[RPL];
     int my_level[RPL];
@@ -622,13 +658,24 @@ __device__ __forceinline__ double wg_island_sweeps(T *rows, const int *jb, const
         if (t < m) { const int r = lev_rows[t]; row_load(rows, jb, r, mine[j]); my_level[j] = row_level[r]; }
     }
     double resid = 0.0;
+    PyrSlots<T, APX ? RPL : 1> pyr;
+    if constexpr (APX) {
+        pyr.lamn = lamn;
+#pragma unroll
+        for (int j = 0; j < RPL; j++) {
+            pyr.fmu[j] = T(0); pyr.nrow[j] = 0;
+            if (my_level[j] >= 0) pyr_slot_load(pyr, j, rows, mine[j].row);
+        }
+    }
     for (int it = 0; it < iters; it++) {
         const bool last = it + 1 == iters;
         for (int lv = 0; lv < nlev; lv++) {
 #pragma unroll
             for (int j = 0; j < RPL; j++)
                 if (my_level[j] == lv) {
-                    const T d = row_sor_lds<T, false>(nullptr, mine[j], fc_lds, true);
+                    T d;
+                    if constexpr (APX) d = row_sor_slot<T, RPL, true>(mine[j], fc_lds, true, &pyr, j);
+                    else d = row_sor_lds<T, false>(nullptr, mine[j], fc_lds, true);
                     if (last) resid += (double)d;
                 }
             lds_barrier();
@@ -709,7 +756,10 @@ constexpr int FC_LDS_BYTES = 48 * 1024;     // islands of up to 2048 (f32) / 102
 
 // REGS: islands of up to WG x 12 (f32) / WG x 6 (f64) rows keep them in registers for the sweeps (wg_island_sweeps); a separate
 // instantiation, so that the streaming forms keep their register budget
-template <class T, int WG, bool REGS, bool FB = false>
+// APX: see solve_islands_body.  Islands of such a tick take the row-unit forms (a lane that owns a whole contact would need the
+// markers in its ContactRegs, which are close to the register budget as they are), and those too large for a workgroup's registers
+// the form that sweeps the row table itself (row_sor), where the normal row's multiplier is simply there.
+template <class T, int WG, bool REGS, bool FB = false, bool APX = false>
 __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const uint8_t *__restrict__ bflags,
                                                      int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                                      StepDiag *__restrict__ diag, int lds_bodies, const ExactCounts *__restrict__ dc,
@@ -745,12 +795,18 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
         }
         by_contact = by_contact && (nc <= 64 || sizeof(T) == 4);      // (a contact's rows are 90 reals of registers: two per lane in f32)
         by_contact = by_contact && !FB;                              // (feedback reads the row table: the rows are built there, by the row form)
+        by_contact = by_contact && !APX;
+    }
+    T *lamn = nullptr;                                               // one word per row for the normal rows' multipliers (PyrSlots)
+    if constexpr (APX) {
+        __shared__ T lamn_s[REGS ? REGS_ROWS<T> : WAVE_ISLAND_ROWS];
+        lamn = lamn_s;
     }
 
     for (int k = tid; k < nb; k += WG) stage_body(S, bflags, stride, I, P, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], k);
     __syncthreads();
     if (!by_contact)
-        for (int c = tid; c < nc; c += WG) contact_rows(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
+        for (int c = tid; c < nc; c += WG) contact_rows<T, 0, APX>(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
     for (int k = tid; k < nb; k += WG) body_tmp(S, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], hinv);
     __syncthreads();
     if (!by_contact) {
@@ -780,9 +836,9 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
         auto build = [&](int v, ContactRegs<T> &c) { contact_build(S, stride, I, P, bs, c0 + v, hinv, c); };
         if (by_contact && nc <= 64) resid = wave_island_contact_sweeps<T, 1>(rows, row_level, I.crow + c0, nc, nlev, P.iters, tid, fc_lds, eager, false, build);
         else if (by_contact) resid = wave_island_contact_sweeps<T, sizeof(T) == 4 ? 2 : 1>(rows, row_level, I.crow + c0, nc, nlev, P.iters, tid, fc_lds, eager, false, build);
-        else if (m <= 64) resid = wave_island_sweeps<T, 1>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager);
-        else if (m <= 128) resid = wave_island_sweeps<T, 2>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager);
-        else resid = wave_island_sweeps<T, WAVE_ISLAND_ROWS / 64>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager);
+        else if (m <= 64) resid = wave_island_sweeps<T, 1, APX>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager, lamn);
+        else if (m <= 128) resid = wave_island_sweeps<T, 2, APX>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager, lamn);
+        else resid = wave_island_sweeps<T, WAVE_ISLAND_ROWS / 64, APX>(rows, jb, row_level, m, nlev, P.iters, tid, fc_lds, eager, lamn);
         for (int k = tid; k < nb; k += WG)
             for (int j = 0; j < 6; j++) bs[(size_t)k * BW_COUNT + BW_FC + j] = fc_lds[6 * k + j];
     } else if (REGS && use_lds && m <= REGS_ROWS<T>) {
@@ -795,7 +851,7 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
         constexpr int RMAX = REGS_ROWS_PER_THREAD<T, WG>;          // 6 (f32) / 3 (f64) at 512 threads, 12 / 6 at 256
         // three rows per contact throughout (the batch's surface with friction, or per-contact surfaces that all have it) and at
         // most two contacts a thread (a contact is 90 registers in f32): contacts as units
-        bool all3 = sizeof(T) == 4 && m == 3 * nc && nlev % 3 == 0 && nc <= 2 * WG && contact_scratch_ints >= nc && (I.cmu != nullptr || P.mu > 0);
+        bool all3 = !APX && sizeof(T) == 4 && m == 3 * nc && nlev % 3 == 0 && nc <= 2 * WG && contact_scratch_ints >= nc && (I.cmu != nullptr || P.mu > 0);
         if (all3 && I.cmu != nullptr) {
             int a3 = 1;
             for (int c = tid; c < nc; c += WG) a3 &= I.cmu[c0 + c] > 0 ? 1 : 0;
@@ -804,16 +860,16 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
         int *cfirst = reinterpret_cast<int *>(fc_lds + (size_t)6 * lds_bodies);
         if (all3 && nc <= WG) resid = wg_island_contact_sweeps<T, 1, WG>(rows, jb, row_level, lev_rows, lev_off, m, nlev, P.iters, tid, fc_lds, cfirst);
         else if (all3) resid = wg_island_contact_sweeps<T, sizeof(T) == 4 ? 2 : 1, WG>(rows, jb, row_level, lev_rows, lev_off, m, nlev, P.iters, tid, fc_lds, cfirst);
-        else if (m <= 2 * WG) resid = wg_island_sweeps<T, 2, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
-        else if (m <= 3 * WG || RMAX <= 3) resid = wg_island_sweeps<T, RMAX < 3 ? RMAX : 3, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
-        else if (m <= 4 * WG || RMAX <= 4) resid = wg_island_sweeps<T, RMAX < 4 ? RMAX : 4, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
-        else if (m <= 6 * WG || RMAX <= 6) resid = wg_island_sweeps<T, RMAX < 6 ? RMAX : 6, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
-        else if (m <= 8 * WG || RMAX <= 8) resid = wg_island_sweeps<T, RMAX < 8 ? RMAX : 8, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
-        else resid = wg_island_sweeps<T, RMAX, WG>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds);
+        else if (m <= 2 * WG) resid = wg_island_sweeps<T, 2, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
+        else if (m <= 3 * WG || RMAX <= 3) resid = wg_island_sweeps<T, RMAX < 3 ? RMAX : 3, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
+        else if (m <= 4 * WG || RMAX <= 4) resid = wg_island_sweeps<T, RMAX < 4 ? RMAX : 4, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
+        else if (m <= 6 * WG || RMAX <= 6) resid = wg_island_sweeps<T, RMAX < 6 ? RMAX : 6, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
+        else if (m <= 8 * WG || RMAX <= 8) resid = wg_island_sweeps<T, RMAX < 8 ? RMAX : 8, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
+        else resid = wg_island_sweeps<T, RMAX, WG, APX>(rows, jb, row_level, lev_rows, m, nlev, P.iters, tid, fc_lds, lamn);
         __syncthreads();
         for (int k = tid; k < nb; k += WG)
             for (int j = 0; j < 6; j++) bs[(size_t)k * BW_COUNT + BW_FC + j] = fc_lds[6 * k + j];
-    } else if (use_lds) {
+    } else if (use_lds && !APX) {
         for (int k = tid; k < nb; k += WG)
             for (int j = 0; j < 6; j++) fc_lds[6 * k + j] = bs[(size_t)k * BW_COUNT + BW_FC + j];
         // The schedule itself in LDS when the launch made room for it (sched_ints): a level step's row is found by two dependent
@@ -875,7 +931,7 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
             for (int lv = 0; lv < nlev; lv++) {
                 const int a = lev_off[lv], e = lev_off[lv + 1];
                 for (int t = a + tid; t < e; t += WG) {
-                    const T d = row_sor(rows, jb, bs, I.lev_rows[t]);
+                    const T d = row_sor<T, APX>(rows, jb, bs, I.lev_rows[t]);
                     if (last) resid += (double)d;
                 }
                 __syncthreads();                              // the next level reads the fc this one wrote

@@ -67,6 +67,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // feedback (dmxBatchSetFeedback): for dmxBatchStepJoints' own ticks only -- the ticks that find their contacts themselves come
     // here with a subset or with device geometry, and produce none.  Off, nothing below stages, launches or stores anything new.
     const bool fb = b->fb_on && !include && !geo;
+    const bool fb_was_valid = b->fb_valid;  // (a tick refused before it touches anything leaves the last tick's feedback served)
     b->fb_valid = false;                    // (set again where the tick has been enqueued whole)
     bool exact = b->stepper_exact;          // dWorldStep: islands solved exactly (decided per tick: see the row limit below)
     // per-slot scratch that persists between ticks: parent = identity, island = -1, last = -1 outside a tick
@@ -125,6 +126,10 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT; };
     auto rpc_of = [&](const CJ &c) { return c.unit ? ((c.unit == UNIT_HINGE2 || c.unit == UNIT_SLIDER2) ? 2 : is_limot(c.unit) ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
     auto nbd_rows_of = [&](const CJ &c) { return c.unit ? (is_limot(c.unit) ? 1 : 0) : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
+    // pyramid rows (DMX_CONTACT_APPROX1): friction row d of a contact whose mode has bit APPROX1_d and whose mu is positive and finite.
+    // A tick that has one launches the kernels' APX instantiations; a tick without one launches what it launched before they existed.
+    auto pyramid_bits = [](const dmxContactJoint &j) { return (j.mu > 0 && j.mu < __builtin_huge_val()) ? (j.mode & DMX_CONTACT_APPROX1) : 0; };
+    bool pyramid = false;
     for (int64_t k = 0; k < nj_in; k++) {
         const dmxContactJoint &j = joints[k];
         int b1 = live(j.body1) ? j.body1 : -1, b2 = live(j.body2) ? j.body2 : -1;
@@ -134,8 +139,21 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         if (b1 == b2) continue;
         DmxCanonicalJoint c; c.b1 = b1; c.b2 = b2; c.j = &j; c.rev = rev;
         cj.push_back(c);
+        if (pyramid_bits(j)) pyramid = true;
     }
     const int nc = (int)cj.size();
+    if (pyramid && b->row_order_ode && !exact) {
+        // ODE moves such rows to the end of its order; this library defines them in creation order only (include/dmx_batch.h)
+        fprintf(stderr, "libode_mi355: dmxBatchStepJoints under DMX_ORDER_ODE with QuickStep does not honour friction bounded by the normal force "
+                        "(DMX_CONTACT_APPROX1): use DMX_ORDER_CREATION\n");
+        b->fb_valid = fb_was_valid;
+        return DMX_EINVAL;
+    }
+    if (pyramid && (include || geo)) {          // (the ticks that find their own contacts refuse such a batch surface before they get here)
+        fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour DMX_CONTACT_APPROX1\n");
+        b->fb_valid = fb_was_valid;
+        return DMX_EINVAL;
+    }
 
     // ---- the bodies this tick steps, ascending: the caller's subset (`include`, with its list) or every live slot ----
     std::vector<int> &slots = b->sc_slots;
@@ -363,6 +381,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     else if (ni > SMALL_MAX_ISLANDS) why = DMX_SMALL_TICK_STAT_ISLANDS;
     else if (!exact && big_max_rows > WAVE_ISLAND_ROWS) why = DMX_SMALL_TICK_STAT_SOR_ROWS;            // (the one-wavefront form of solve_island_wg)
     else if (exact && !grid_list.empty()) why = DMX_SMALL_TICK_STAT_LDS_FIT;
+    else if (exact && pyramid) why = DMX_SMALL_TICK_STAT_LDS_FIT;      // (dWorldStep's two passes: the general path's kernels only)
     const bool small = why < 0;
     b->small_stats[small ? DMX_SMALL_TICK_STAT_SMALL : DMX_SMALL_TICK_STAT_GENERAL]++;
     if (!small) b->small_stats[why]++;
@@ -564,6 +583,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     I.cbounce = I.cmu + nc; I.cbounce_vel = I.cbounce + nc; I.csoft_erp = I.cbounce_vel + nc; I.csoft_cfm = I.csoft_erp + nc;
     I.rows = (T *)b->jd_rows.p; I.rowjb = (int *)b->jd_rowjb.p; I.bscr = (T *)b->jd_bscr.p; I.local = (int *)b->jd_local.p;
     I.singles = (exact || ode_order) ? 0 : 1;
+    if (pyramid) I.singles = 0;      // (the one-body forms know box friction only: solve_islands' row form takes their islands, as with feedback on)
     FeedbackSet<T> F;
     if (fb) {
         // every solve must leave lambda in the row table: the one-body forms keep their rows in registers, so their islands take
@@ -648,7 +668,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         } else {
             lds = small_tick_sor_lds((int)sizeof(T), big_max_bodies, &K.lds_bodies);
         }
-        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream));
+        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream, pyramid));
         HIP_TRY(hipEventRecord(b->sm_ev[sp], b->stream));
         b->sm_ev_pending[sp] = true;
         b->sm_parity = sp ^ 1;
@@ -667,7 +687,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     HIP_TRY(hipMemsetAsync(b->diag_isl, 0, sizeof(StepDiag), b->stream));
     if (exact) {
         HIP_TRY(launch_islands_without_rows<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream));
-        HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream));
+        HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream, pyramid));
         // Written for a copy from pageable host memory that is gone; but the grid solves' host loop below and the next tick's
         // rewrite of the host staging have run behind this wait ever since, and no test tells a missing wait from a present one.
         // Taking it out is a change of speed, to be made and measured on its own.
@@ -678,10 +698,12 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             lcp_grid_begin_tick(b);
             LcpIslandRows R;
             R.limots = n_limots > 0;
+            R.pyramid_tick = pyramid;
             std::vector<std::pair<uint64_t, int>> &ord = b->sc_pair_ord;
             for (int isl : grid_list) {
                 R.isl = isl; R.m = b->sc_iv[10][(size_t)isl]; R.row_base = 3 * con_start[(size_t)isl];
                 R.unbounded.assign((size_t)R.m, 0); R.key.assign((size_t)R.m, 0);
+                R.pyramid = false; R.pyramid_row.assign((size_t)R.m, 0);
                 const int d0 = con_start[(size_t)isl], d1 = con_start[(size_t)isl + 1];
                 ord.clear();
                 for (int d = d0; d < d1; d++) {
@@ -701,6 +723,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                         //  ordinal within the pair is stable while the set and the limots' presence are)
                         R.key[(size_t)(r + q)] = base | (uint64_t)(is_limot(c.unit) ? 1 : q);
                         R.unbounded[(size_t)(r + q)] = c.unit ? !is_limot(c.unit) : (q > 0 && !(c.j->mu < __builtin_huge_val()));
+                        if (!c.unit && q > 0 && (pyramid_bits(*c.j) & (DMX_CONTACT_APPROX1_1 << (q - 1)))) { R.pyramid_row[(size_t)(r + q)] = 1; R.pyramid = true; }
                     }
                 }
                 // every body's rows (creation order): counting sort over the island's contacts; local index = position among the
@@ -737,7 +760,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         }
         if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
     } else {
-        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb));
+        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb, pyramid));
         if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
         if (ode_order) HIP_TRY(hipStreamSynchronize(b->stream));      // the order table came from pageable host memory
     }

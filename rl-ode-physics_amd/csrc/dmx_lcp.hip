@@ -95,7 +95,8 @@ __device__ __forceinline__ double fast_rsqrt(double x)
 }
 
 // =========================================================================================================== 1. the island's rows
-template <class T>
+// APX: the tick has pyramid rows (DMX_CONTACT_APPROX1) -- contact_rows marks them and builds them with lo = hi = 0 (pass A)
+template <class T, bool APX = false>
 __global__ __launch_bounds__(512) void lcp_prepare(T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, IslandSet<T> I,
                                                    StepParams<T> P, int isl, T *__restrict__ tol_out, T tol_rel)
 {
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(512) void lcp_prepare(T *__restrict__ S, const uint
     const int m = nc > 0 ? I.crow[c0 + nc - 1] + contact_rpc(I, P, c0 + nc - 1) : 0;
     for (int k = tid; k < nb; k += WG) stage_body(S, bflags, stride, I, P, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], k);
     __syncthreads();
-    for (int c = tid; c < nc; c += WG) contact_rows(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
+    for (int c = tid; c < nc; c += WG) contact_rows<T, 0, APX>(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
     for (int k = tid; k < nb; k += WG) body_tmp(S, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], hinv);
     __syncthreads();
     T bmax = T(0);
@@ -326,6 +327,30 @@ __global__ __launch_bounds__(256) void lcp_bvec(const T *__restrict__ A, int ld,
     bprime[i] = A[(size_t)(nuP + i) * ld + mP];
     lo[i] = p >= 0 ? rows[(size_t)p * RW_COUNT + RW_LO] : -Limits<T>::inf();
     hi[i] = p >= 0 ? rows[(size_t)p * RW_COUNT + RW_HI] : Limits<T>::inf();
+}
+// Between the two passes of an island with pyramid rows (DMX_CONTACT_APPROX1): pass A's lambda of the bounded rows goes into the rows
+// (clamped as the final store clamps), then every pyramid row's bounds become -/+ mu lambda^A_n of its contact's normal row, in the
+// rows (lcp_forces reads them there) and in the reduced problem's lo / hi.  One workgroup.
+template <class T>
+__global__ __launch_bounds__(1024) void lcp_rebound(T *__restrict__ rows, const int *__restrict__ perm, int nuP, int nbd, const int *__restrict__ state,
+                                                    const T *__restrict__ lamB, T *__restrict__ lo, T *__restrict__ hi)
+{
+    for (int q = threadIdx.x; q < nbd; q += 1024) {
+        T l = lamB[q];
+        if (state[q] == ST_FREE) { if (l < lo[q]) l = lo[q]; if (l > hi[q]) l = hi[q]; }
+        rows[(size_t)perm[nuP + q] * RW_COUNT + RW_LAM] = l;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nbd; q += 1024) {
+        const int i = perm[nuP + q];
+        T *row = rows + (size_t)i * RW_COUNT;
+        const T fmu = row[RW_FMU];
+        if (!(fmu > T(0))) continue;
+        T l, h;
+        pyramid_bounds(fmu, rows[(size_t)(i - (int)row[RW_FDIR]) * RW_COUNT + RW_LAM], l, h);
+        row[RW_LO] = l; row[RW_HI] = h;
+        lo[q] = l; hi[q] = h;
+    }
 }
 // lambda_B at the start of a round: clamped rows at their bounds, free rows zero
 template <class T>
@@ -583,11 +608,11 @@ __global__ __launch_bounds__(1024) void lcp_forces(T *__restrict__ S, const uint
 }
 
 // small and medium islands, one workgroup each, the whole solve in LDS: dmx_lcp_lds.hpp
-template <class T, int WG>
+template <class T, int WG, bool APX = false>
 __global__ __launch_bounds__(WG) void lcp_island_lds(T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, IslandSet<T> I,
                                                      StepParams<T> P, StepDiag *__restrict__ diag, int murty_only, T tol_rel)
 {
-    lcp_island_lds_body<T, WG>(S, bflags, stride, I, P, diag, murty_only, tol_rel, blockIdx.x);
+    lcp_island_lds_body<T, WG, APX>(S, bflags, stride, I, P, diag, murty_only, tol_rel, blockIdx.x);
 }
 
 // =========================================================================================================== the volatile rows' problem
@@ -845,8 +870,9 @@ int lcp_grid_solve(dmxBatch *b, const IslandSet<T> &I, const StepParams<T> &P, c
     T *rows = I.rows + (size_t)R.row_base * RW_COUNT;
     const int *jb = I.rowjb + 2 * (size_t)R.row_base;
 
-    hipLaunchKernelGGL((lcp_prepare<T>), dim3(1), dim3(512), 0, st, (T *)b->slab, b->bflags, b->stride, I, P, isl, tol,
-                       (T)(g->tol_rel > 0 ? g->tol_rel : (sizeof(T) == 4 ? 1e-5 : 1e-11)));
+    const T tol_rel = (T)(g->tol_rel > 0 ? g->tol_rel : (sizeof(T) == 4 ? 1e-5 : 1e-11));
+    if (R.pyramid_tick) hipLaunchKernelGGL((lcp_prepare<T, true>), dim3(1), dim3(512), 0, st, (T *)b->slab, b->bflags, b->stride, I, P, isl, tol, tol_rel);
+    else hipLaunchKernelGGL((lcp_prepare<T>), dim3(1), dim3(512), 0, st, (T *)b->slab, b->bflags, b->stride, I, P, isl, tol, tol_rel);
     hipLaunchKernelGGL((lcp_assemble<T>), dim3((unsigned)(nt + 1), (unsigned)nt), dim3(256), 0, st, rows, jb, d_perm, nt, A, ld);
     {
         const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&lcp_panel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -907,6 +933,12 @@ int lcp_grid_solve(dmxBatch *b, const IslandSet<T> &I, const StepParams<T> &P, c
             }
         }
         state0 = state;
+        // an island with pyramid rows (DMX_CONTACT_APPROX1) comes through the pivoting twice: pass A with those rows at lo = hi = 0 as
+        // lcp_prepare<T, true> built them, then lcp_rebound, then pass B from pass A's active set with the pyramid rows set free
+        int pass = 0;
+        const bool classical0 = classical;
+    next_pass:
+        int single_pass = 0;      // single-flip rounds of THIS pass: pass B starts with block flips again, whatever pass A ended in
         int best = m + 1, patience = g->murty_only ? 0 : 3, passes = 0, l2_passes = 0;
         bool subset_mode = false;
         const int max_rounds = 20 * m + 100;
@@ -1037,15 +1069,26 @@ int lcp_grid_solve(dmxBatch *b, const IslandSet<T> &I, const StepParams<T> &P, c
                 in_v.assign((size_t)nbd, 0);           // too many for one workgroup: a classical round on all of them, V starts again
             }
             bool all = true;         // (single flips, once begun, to the end: see lds_pivot_rounds)
-            if (nviol < best) { best = nviol; if (!g->murty_only && single_rounds == 0) patience = 3; }
+            if (nviol < best) { best = nviol; if (!g->murty_only && single_pass == 0) patience = 3; }
             else if (patience > 0) patience--;
             else all = false;
-            if (g->murty_only || single_rounds > 0) all = false;
-            if (!all) single_rounds++;
+            if (g->murty_only || single_pass > 0) all = false;
+            if (!all) { single_rounds++; single_pass++; }
             for (int q = 0; q < nbd; q++) {
                 if (!h_viol[q] || (!all && q != top)) continue;
                 state[(size_t)q] = h_viol[q] == 1 ? ST_LO : h_viol[q] == 2 ? ST_HI : ST_FREE;
             }
+        }
+        if (R.pyramid && pass == 0) {
+            // (d_state, lamB, lo and hi on the device are the final round's; the next round's uploads are behind this launch on the stream)
+            hipLaunchKernelGGL((lcp_rebound<T>), dim3(1), dim3(1024), 0, st, rows, d_perm, nuP, nbd, d_state, lamB, lo, hi);
+            for (int q = 0; q < nbd; q++)
+                if (R.pyramid_row[(size_t)perm[(size_t)(nuP + q)]]) state[(size_t)q] = ST_FREE;
+            in_v.assign((size_t)nbd, 0);
+            classical = classical0;
+            pass = 1;
+            rounds++;
+            goto next_pass;
         }
         {
             static const int trace = [] { const char *e = getenv("DMX_LCP_TRACE"); return e ? atoi(e) : 0; }();
@@ -1110,18 +1153,20 @@ void lcp_lds_knobs(int real_bytes, int *murty_only, double *tol_rel)
 }
 template <class T>
 hipError_t launch_lcp_lds(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                          size_t lds_bytes, hipStream_t st)
+                          size_t lds_bytes, hipStream_t st, bool pyramid)
 {
     if (I.n_big <= 0) return hipSuccess;
     int murty; double tol_rel;
     lcp_lds_knobs((int)sizeof(T), &murty, &tol_rel);
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&lcp_island_lds<T, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    const void *fn = pyramid ? (const void *)&lcp_island_lds<T, 256, true> : (const void *)&lcp_island_lds<T, 256>;
+    const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL((lcp_island_lds<T, 256>), dim3((unsigned)I.n_big), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, murty, (T)tol_rel);
+    if (pyramid) hipLaunchKernelGGL((lcp_island_lds<T, 256, true>), dim3((unsigned)I.n_big), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, murty, (T)tol_rel);
+    else hipLaunchKernelGGL((lcp_island_lds<T, 256>), dim3((unsigned)I.n_big), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, murty, (T)tol_rel);
     return hipGetLastError();
 }
-template hipError_t launch_lcp_lds<float>(float *, const uint8_t *, int64_t, const IslandSet<float> &, const StepParams<float> &, StepDiag *, size_t, hipStream_t);
-template hipError_t launch_lcp_lds<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &, const StepParams<double> &, StepDiag *, size_t, hipStream_t);
+template hipError_t launch_lcp_lds<float>(float *, const uint8_t *, int64_t, const IslandSet<float> &, const StepParams<float> &, StepDiag *, size_t, hipStream_t, bool);
+template hipError_t launch_lcp_lds<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &, const StepParams<double> &, StepDiag *, size_t, hipStream_t, bool);
 size_t lcp_lds_need(int real_bytes, int m, int nbd) { return real_bytes == 4 ? lcp_lds_bytes<float>(m, nbd) : lcp_lds_bytes<double>(m, nbd); }
 
 void lcp_grid_stats(dmxBatch *b, int64_t out[8])

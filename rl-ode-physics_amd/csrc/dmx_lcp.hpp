@@ -27,6 +27,10 @@ struct LcpIslandRows {
     // some of the rows are hinges' limit / motor rows (dmxBatchSetHingeLimots): which of a row's bounds is infinite changes with
     // the hinge's angle, so a remembered LO / HI may name a bound that is not there this tick
     bool limots = false;
+    // DMX_CONTACT_APPROX1: pyramid_tick = some row of the tick is a pyramid row (the rows are built by the kernels' APX instantiations),
+    // pyramid = some row of THIS island is (it is solved in two passes), pyramid_row = which
+    bool pyramid_tick = false, pyramid = false;
+    std::vector<uint8_t> pyramid_row;
     // the rows of every body of the island, ascending: body k's (k = its index within the island) are bodyrows[boff[k] .. boff[k+1]),
     // each entry 2 * row + side (0: the body is the row's first, 1: its second)
     std::vector<int> boff, bodyrows;
@@ -54,6 +58,6 @@ size_t lcp_lds_need(int real_bytes, int m, int nbd);
 void lcp_lds_knobs(int real_bytes, int *murty_only, double *tol_rel);
 template <class T>
 hipError_t launch_lcp_lds(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                          size_t lds_bytes, hipStream_t st);
+                          size_t lds_bytes, hipStream_t st, bool pyramid = false);      // (pyramid: the kernel's APX instantiation)
 
 }  // namespace dmx

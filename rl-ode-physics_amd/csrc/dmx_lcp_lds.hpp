@@ -238,7 +238,11 @@ template <class T> __host__ __device__ inline size_t lcp_lds_bytes(int m, int nb
     return ((lcp_lds_reals(m, nbd) * sizeof(T) + 15) / 16) * 16 + ((size_t)3 * m + (size_t)3 * nbd + 16) * sizeof(int);
 }
 
-template <class T, int WG>
+// APX (a tick with pyramid rows, DMX_CONTACT_APPROX1: an instantiation of its own): contact_rows builds the pyramid rows with lo = hi = 0,
+// so the pivoting below is the definition's pass A; an island that has such a row then takes their bounds -/+ mu lambda^A_n from the
+// normal rows' multipliers and pivots again from the all-free set (pass B: same matrix, same factor of the never-clamping block --
+// pyramid rows are bounded rows).  An island without one is solved once.
+template <class T, int WG, bool APX = false>
 __device__ __forceinline__ void lcp_island_lds_body(T *__restrict__ S, const uint8_t *__restrict__ bflags, int64_t stride, const IslandSet<T> &I,
                                                     const StepParams<T> &P, StepDiag *__restrict__ diag, int murty_only, T tol_rel, unsigned bidx)
 {
@@ -255,7 +259,7 @@ __device__ __forceinline__ void lcp_island_lds_body(T *__restrict__ S, const uin
 
     for (int k = tid; k < nb; k += WG) stage_body(S, bflags, stride, I, P, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], k);
     __syncthreads();
-    for (int c = tid; c < nc; c += WG) contact_rows(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
+    for (int c = tid; c < nc; c += WG) contact_rows<T, 0, APX>(S, stride, I, P, rows, jb, c0 + c, I.crow[c0 + c], hinv);
     for (int k = tid; k < nb; k += WG) body_tmp(S, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], hinv);
     __syncthreads();
     __shared__ int s_cnt[2][WG / 64 + 1];
@@ -351,6 +355,28 @@ __device__ __forceinline__ void lcp_island_lds_body(T *__restrict__ S, const uin
     ldlt_steps<T, WG>(M, m, 0, nu, dinv, tol, tid);
     const int max_rounds = 20 * m + 100;
     (void)lds_pivot_rounds<T, WG>(M, m, nu, nbd, W, lam, wv, lo, hi, state, fidx, viol, z, tol, murty_only, max_rounds, tid);
+    if constexpr (APX) {
+        int has = 0;
+        for (int q = tid; q < nbd; q += WG) has |= rows[(size_t)perm[nu + q] * RW_COUNT + RW_FMU] > T(0) ? 1 : 0;
+        if (__syncthreads_or(has)) {
+            // lambda^A of the bounded rows (the normal rows are among them) into the rows, clamped as the final store clamps
+            for (int q = tid; q < nbd; q += WG) {
+                T l = lam[q];
+                if (state[q] == ST_FREE) { if (l < lo[q]) l = lo[q]; if (l > hi[q]) l = hi[q]; }
+                rows[(size_t)perm[nu + q] * RW_COUNT + RW_LAM] = l;
+            }
+            __syncthreads();
+            for (int q = tid; q < nbd; q += WG) {
+                const int i = perm[nu + q];
+                const T *row = rows + (size_t)i * RW_COUNT;
+                const T fmu = row[RW_FMU];
+                if (fmu > T(0)) pyramid_bounds(fmu, rows[(size_t)(i - (int)row[RW_FDIR]) * RW_COUNT + RW_LAM], lo[q], hi[q]);
+                state[q] = ST_FREE; lam[q] = T(0);
+            }
+            __syncthreads();
+            (void)lds_pivot_rounds<T, WG>(M, m, nu, nbd, W, lam, wv, lo, hi, state, fidx, viol, z, tol, murty_only, max_rounds, tid);
+        }
+    }
     // ---- lambda_U: L_UU^T x = D^-1 y_U - L_BU^T lambda_B
     for (int k = tid; k < nu; k += WG) {
         T acc = M[tri(m, k)];

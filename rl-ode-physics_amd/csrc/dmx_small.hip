@@ -40,7 +40,9 @@ template <class T> __device__ __forceinline__ void island_feedback(const IslandS
 
 // FB: a tick made with feedback on -- an instantiation of its own, so that the others are the kernels they were before feedback
 // existed (F is an argument they never read).
-template <class T, bool EXACT, bool FB = false>
+// APX: a QuickStep tick with pyramid rows (DMX_CONTACT_APPROX1): the island functions' APX instantiations, made with FB's store on --
+// F.mode says whether the tick reports feedback too.  (Under dWorldStep such a tick takes the general path.)
+template <class T, bool EXACT, bool FB = false, bool APX = false>
 __global__ __launch_bounds__(EXACT ? 256 : 64) void small_world_tick(T *S, const uint8_t *bflags, int64_t stride, IslandSet<T> I, StepParams<T> P,
                                                                      StepDiag *diag, SmallTick<T> K, FeedbackSet<T> F)
 {
@@ -49,22 +51,22 @@ __global__ __launch_bounds__(EXACT ? 256 : 64) void small_world_tick(T *S, const
     if (blockIdx.x == 0 && tid == 0) { K.diag_next->contacts = 0ull; K.diag_next->residual = 0.0; }
     if (blockIdx.x < (unsigned)I.n_big) {
         if (EXACT) lcp_island_lds_body<T, WG>(S, bflags, stride, I, P, diag, K.murty, K.tol_rel, blockIdx.x);
-        else solve_island_wg_body<T, WG, false, FB>(S, bflags, stride, I, P, diag, K.lds_bodies, (const ExactCounts *)nullptr, 0, blockIdx.x, (unsigned)I.n_big);
+        else solve_island_wg_body<T, WG, false, FB, APX>(S, bflags, stride, I, P, diag, K.lds_bodies, (const ExactCounts *)nullptr, 0, blockIdx.x, (unsigned)I.n_big);
         __syncthreads();
         const int isl = I.big_list[blockIdx.x];
-        if (FB) island_feedback(I, P, F, isl, tid, WG);                                       // (the rows' lambda is behind the barrier)
+        if (FB && (!APX || F.mode != FB_OFF)) island_feedback(I, P, F, isl, tid, WG);                                       // (the rows' lambda is behind the barrier)
         const int b0 = I.body_off[isl], nb = I.body_off[isl + 1] - b0;
         for (int k = tid; k < nb; k += WG) mirror_body(S, K.mirror, I.bodies[b0 + k]);      // (body k was finished by this thread)
     } else {
         constexpr int LANES = EXACT ? WG : SMALL_TAIL_LANES;
         const int isl = (int)(blockIdx.x - (unsigned)I.n_big) * LANES + tid;
         if (tid < LANES && isl < I.n_islands && I.big[isl] < 0) {
-            solve_islands_body<T, FB>(S, bflags, stride, I, P, diag, isl);        // (each of the three takes its own kind of island)
+            solve_islands_body<T, FB, APX>(S, bflags, stride, I, P, diag, isl);        // (each of the three takes its own kind of island)
             if (!EXACT && !FB) {                  // (feedback on: the row form above has taken them, I.singles = 0)
                 solve_singles_body<T>(S, bflags, stride, I, P, diag, isl);
                 solve_singles_lds_body<T>(S, bflags, stride, I, P, diag, isl, LANES, tid);
             }
-            if (FB) island_feedback(I, P, F, isl, 0, 1);
+            if (FB && (!APX || F.mode != FB_OFF)) island_feedback(I, P, F, isl, 0, 1);
             const int b0 = I.body_off[isl], nb = I.body_off[isl + 1] - b0;
             for (int k = 0; k < nb; k++) mirror_body(S, K.mirror, I.bodies[b0 + k]);
         }
@@ -83,35 +85,36 @@ size_t small_tick_sor_lds(int real_bytes, int max_bodies, int *lds_bodies)
     return std::max(wg, tail);
 }
 
-template <class T, bool FB>
+template <class T, bool FB, bool APX = false>
 static hipError_t launch_small_tick_fb(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
                                        const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st)
 {
     // (always at least one workgroup: an empty world's tick still rotates the diagnostics slots and may fill the mirror)
     const int lanes = exact ? 256 : SMALL_TAIL_LANES;
     const unsigned grid = (unsigned)I.n_big + (unsigned)std::max(1, (I.n_islands + lanes - 1) / lanes);
-    if (exact) {
+    if (exact && !APX) {
         if (lds_bytes > (size_t)64 * 1024) {
             const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&small_world_tick<T, true, FB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
             if (ea != hipSuccess) return ea;
         }
         hipLaunchKernelGGL((small_world_tick<T, true, FB>), dim3(grid), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
     } else {
-        hipLaunchKernelGGL((small_world_tick<T, false, FB>), dim3(grid), dim3(64), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
+        hipLaunchKernelGGL((small_world_tick<T, false, FB, APX>), dim3(grid), dim3(64), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
     }
     return hipGetLastError();
 }
 template <class T>
 hipError_t launch_small_tick(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st)
+                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid)
 {
+    if (pyramid) return exact ? hipErrorInvalidValue : launch_small_tick_fb<T, true, true>(S, bflags, stride, I, P, diag, K, F, false, lds_bytes, st);
     return F.mode != FB_OFF ? launch_small_tick_fb<T, true>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st)
                             : launch_small_tick_fb<T, false>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st);
 }
 template hipError_t launch_small_tick<float>(float *, const uint8_t *, int64_t, const IslandSet<float> &, const StepParams<float> &, StepDiag *,
-                                             const SmallTick<float> &, const FeedbackSet<float> &, bool, size_t, hipStream_t);
+                                             const SmallTick<float> &, const FeedbackSet<float> &, bool, size_t, hipStream_t, bool);
 template hipError_t launch_small_tick<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &, const StepParams<double> &, StepDiag *,
-                                              const SmallTick<double> &, const FeedbackSet<double> &, bool, size_t, hipStream_t);
+                                              const SmallTick<double> &, const FeedbackSet<double> &, bool, size_t, hipStream_t, bool);
 
 hipError_t dmx_touch_small(int real_bytes)
 {

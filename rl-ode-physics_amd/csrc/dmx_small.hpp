@@ -29,7 +29,7 @@ template <class T> struct SmallTick {
 
 template <class T>
 hipError_t launch_small_tick(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st);      // (F.mode: the kernel's FB instantiation)
+                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid = false);      // (F.mode: the kernel's FB instantiation; pyramid: its APX one, QuickStep only)
 // dynamic LDS of the QuickStep form for islands of up to max_bodies bodies (out: SmallTick::lds_bodies)
 size_t small_tick_sor_lds(int real_bytes, int max_bodies, int *lds_bodies);
 hipError_t dmx_touch_small(int real_bytes);
