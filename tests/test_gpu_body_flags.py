@@ -9,8 +9,8 @@ extra joints name -- one from the dead slot to the top link (the dead end is sta
 its one row counts among the island's m), one from the dead slot to static ground (dropped).
 
 The harness, tolerances and rules are those of tests/test_gpu_solver_dense.py, unchanged (`check`): 1e-10 float64 QuickStep,
-1e-8 float64 dWorldStep, 10 eps32 kappa(A) float32, dead slots bit for bit, and float32 QuickStep only where the reference's
-clamp margin is above 1e-3 of the island's largest |lambda| (asserted there).  The path a tick took is asserted wherever a
+1e-8 float64 dWorldStep, 10 eps32 kappa(A) float32 dWorldStep, the per-body band of tests/quick_band.py for float32 QuickStep
+(K eps32 M_v, rows at their bounds included), dead slots bit for bit.  The path a tick took is asserted wherever a
 counter says it: lcp_stats()["solves"] (the grid solve) and small_tick_stats() (the single-launch tick or the general path,
 with the reason).  Gyro modes: off and implicit everywhere; explicit on the small cases (it overflows on slender spinning
 boxes over many ticks, tests/test_gpu_fuzz.py)."""
@@ -165,8 +165,7 @@ def test_quickstep_above_the_register_form_f64(gyro):
 @pytest.mark.parametrize("gyro", GYROS)
 @pytest.mark.parametrize("m", [256, 257, 1025, 3072, 3073])
 def test_quickstep_forms_f32(m, gyro):
-    """the flagged press_chain keeps every clamp decision clear of float32 rounding (check asserts the reference's margin
-    against its 1e-3 rule; the margins are the reference's alone, found on the CPU)"""
+    """the flagged press_chain in float32, held to the band of tests/quick_band.py"""
     B, jts = flagged_press_chain(m, m)
     (r, st), = run("float32", B, world("float32", gyro=gyro), jts, "quick", both=m <= 256)
     the_island(r, m)
@@ -211,18 +210,26 @@ def test_exact_forms(prec, m, gyro):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # e. flags that change between ticks
-@pytest.mark.parametrize("prec,stepper", [("float64", "exact"), ("float32", "exact"), ("float64", "quick")])
-def test_flags_change_between_ticks(prec, stepper):
-    """six ticks of a resting stack of 80 bodies and 320 rows (dWorldStep: the grid solve, which carries its active set from tick
-    to tick); body 40 goes dynamic -> kinematic -> dynamic -> dead -> alive -> alive, every tick equals the reference
-    restarted from the device's state with the flags then in force.  The host's mirror of the flags decides which joints
-    live (csrc/dmx_joints.cpp), the device's copy how the bodies are staged: both must follow every upload"""
+def flags_change_case():
     rng = np.random.default_rng(61)
     B, jts = chain(80, 160, np.repeat([0.4, 0.0], 80), rng, speed=0.05)       # every link: one contact of 3 rows, one of 1
     spin(B, rng, 0.2)
     B.flags[1] |= ld.NOGRAVITY
     B.flags[26] |= ld.NOGYRO
-    mid = [ld.ALIVE, ld.ALIVE | ld.KINEMATIC, ld.ALIVE, 0, ld.ALIVE, ld.ALIVE]
+    return B, jts
+
+
+FLAGS_OF_BODY_40 = [ld.ALIVE, ld.ALIVE | ld.KINEMATIC, ld.ALIVE, 0, ld.ALIVE, ld.ALIVE]
+
+
+@pytest.mark.parametrize("prec,stepper", [("float64", "exact"), ("float32", "exact"), ("float64", "quick"), ("float32", "quick")])
+def test_flags_change_between_ticks(prec, stepper):
+    """six ticks of a resting stack of 80 bodies and 320 rows (dWorldStep: the grid solve, which carries its active set from tick
+    to tick); body 40 goes dynamic -> kinematic -> dynamic -> dead -> alive -> alive, every tick equals the reference
+    restarted from the device's state with the flags then in force.  The host's mirror of the flags decides which joints
+    live (csrc/dmx_joints.cpp), the device's copy how the bodies are staged: both must follow every upload"""
+    B, jts = flags_change_case()
+    mid = FLAGS_OF_BODY_40
 
     def between(t, j):
         f = B.flags.copy()
@@ -243,6 +250,15 @@ def test_flags_change_between_ticks(prec, stepper):
             grid = any(I.m > 256 for I in r.islands)
         general += grid
         assert st["tick"]["general"] == general and st["tick"]["small"] == t + 1 - general
+
+
+# every float32 QuickStep case of this file with rows: name -> () -> (Bodies, joints, World) of its first tick;
+# tests/test_quick_band.py runs the float32 emulation of the reference's sweeps over them (quick_band.MEASURED, population (b));
+# the later ticks of flags_change start from the device's state, and are emulated there from the reference's
+F32_QUICK_CASES = {"flags_change": lambda: (*flags_change_case(), world("float32", gyro=ld.GYRO_IMPLICIT))}
+for _m in (256, 257, 1025, 3072, 3073):
+    for _g in GYROS:
+        F32_QUICK_CASES[f"flagged_press_chain-{_m}-gyro{_g}"] = lambda m=_m, g=_g: (*flagged_press_chain(m, m), world("float32", gyro=g))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

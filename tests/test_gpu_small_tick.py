@@ -9,7 +9,8 @@ kernel calls the device functions the general path's kernels wrap, so the two pa
      device function is shared unchanged and runs in the same 256-thread workgroup shape, so no reduction order differs;
   3. same answer as the checkers: the oracle through the ODE API (QuickStep bit for bit, dWorldStep within 1e-5, what
      tests/test_ode_compat.py asserts for the general path), and tests/lcp_dense.py on synthetic joints with the tolerances
-     written at the top of tests/test_gpu_solver_dense.py (f64 QuickStep 1e-10, f64 dWorldStep 1e-8, f32 10 eps32 kappa);
+     written at the top of tests/test_gpu_solver_dense.py (f64 QuickStep 1e-10, f64 dWorldStep 1e-8, f32 dWorldStep 10 eps32
+     kappa, f32 QuickStep the per-body band of tests/quick_band.py, rows at their bounds included);
   4. the mirror is never stale; 5. eligibility falls back, never fails; 6. two worlds in one process.
 
 The DMX_* knobs are read once per process, so runs with DMX_SMALL_TICK=0 / DMX_ROW_ORDER go through the C harness
@@ -24,6 +25,7 @@ import numpy as np
 import pytest
 
 import lcp_dense as ld
+import quick_band as qb
 from __graft_entry__ import load_package
 from test_ode_compat import _build_harness, _scene_text, _oracle_poses, _rel
 
@@ -167,6 +169,9 @@ def _as_precision(prec, W, jts):
     return W2, j2
 
 
+DEVICE_WORST = {"contact": 0.0}          # the largest device deviation of this process, in eps32 M_v (printed by _dense)
+
+
 def _dense(prec, B, jts, stepper, W=None):
     """one step_joints tick on a fresh batch against tests/lcp_dense.py run from the device's own pre-tick state.
     -> (reference Result, post-tick state (n, 13), small_tick_stats, lcp_stats)"""
@@ -186,23 +191,22 @@ def _dense(prec, B, jts, stepper, W=None):
     Wr, jr = _as_precision(prec, W, jts)
     r = ld.step(Bp, Wr, jr, stepper)
     f32 = np.dtype(prec).itemsize == 4
-    if not f32:
-        t = 1e-10 if stepper == "quick" else 1e-8
-    else:
-        t = 10 * EPS32 * max([I.kappa() for I in r.islands] + [1.0])
-        if stepper == "quick":
-            for I, lam, margin in zip(r.islands, r.lams, r.margins):
-                if I.m:
-                    assert margin > 1e-3 * np.max(np.abs(lam)), "f32 QuickStep case too close to a clamp to compare"
     live = np.nonzero(Bp.flags & ld.ALIVE)[0]
-    scale = ld.velocity_scale(r.bodies, Wr, live)
-    err = ld.velocity_error(r.bodies, post[:, 7:10], post[:, 10:13], live)
-    assert err <= t * scale, f"velocity error {err:.3e} > {t:.1e} x {scale:.3e}"
-    eps = 4 * (EPS32 if f32 else 2.2e-16)
-    xerr = np.max(np.abs(post[live, 0:3] - r.bodies.pos[live]))
-    assert xerr <= t * scale * Wr.h + eps * max(1.0, np.max(np.abs(r.bodies.pos[live]))), f"position error {xerr:.3e}"
-    qerr = np.max(np.abs(post[live, 3:7] - r.bodies.quat[live]))
-    assert qerr <= t * scale * Wr.h + eps, f"quaternion error {qerr:.3e}"
+    if f32 and stepper == "quick":
+        worst = qb.assert_in_band(r, Wr, post, qb.K["contact"], live)
+        DEVICE_WORST["contact"] = max(DEVICE_WORST["contact"], worst)
+        print(f"f32 QuickStep, single-launch tick: {worst:.2f} eps32 M_v (K = {qb.K['contact']}; largest so far "
+              f"{DEVICE_WORST['contact']:.2f})")
+    else:
+        t = (1e-10 if stepper == "quick" else 1e-8) if not f32 else 10 * EPS32 * max([I.kappa() for I in r.islands] + [1.0])
+        scale = ld.velocity_scale(r.bodies, Wr, live)
+        err = ld.velocity_error(r.bodies, post[:, 7:10], post[:, 10:13], live)
+        assert err <= t * scale, f"velocity error {err:.3e} > {t:.1e} x {scale:.3e}"
+        eps = 4 * (EPS32 if f32 else 2.2e-16)
+        xerr = np.max(np.abs(post[live, 0:3] - r.bodies.pos[live]))
+        assert xerr <= t * scale * Wr.h + eps * max(1.0, np.max(np.abs(r.bodies.pos[live]))), f"position error {xerr:.3e}"
+        qerr = np.max(np.abs(post[live, 3:7] - r.bodies.quat[live]))
+        assert qerr <= t * scale * Wr.h + eps, f"quaternion error {qerr:.3e}"
     dead = np.nonzero(~(Bp.flags & ld.ALIVE).astype(bool))[0]
     if len(dead):
         assert np.array_equal(post[dead], pre[dead]), "a dead slot changed"
@@ -214,24 +218,26 @@ def _on_small_path(stats):
     assert stats["small"] == 1 and stats["general"] == 0 and sum(stats[k] for k in B_.SMALL_TICK_STATS[2:]) == 0, stats
 
 
-COMBOS = [("float64", "quick"), ("float64", "exact"), ("float32", "exact")]
+COMBOS = [("float64", "quick"), ("float64", "exact"), ("float32", "exact"), ("float32", "quick")]
+
+
+def _singles_case(nc):
+    rng = np.random.default_rng(100 + nc)
+    return _join([_chain(1, nc, np.inf, rng), _chain(1, 0, 0.0, rng)])
 
 
 @pytest.mark.parametrize("prec,stepper", COMBOS)
 @pytest.mark.parametrize("nc", range(1, 9))
 def test_dense_single_body_islands(prec, stepper, nc):
-    """one body with 1..8 contacts on static ground (QuickStep: the lane forms in the kernel's tail) beside a free body"""
-    rng = np.random.default_rng(100 + nc)
-    B, jts = _join([_chain(1, nc, np.inf, rng), _chain(1, 0, 0.0, rng)])
+    """one body with 1..8 contacts on static ground (QuickStep: the lane forms in the kernel's tail) beside a free body.  (nc = 1
+    under QuickStep has converged long before the last sweep: it cannot show a dropped sweep, the other seven can.)"""
+    B, jts = _singles_case(nc)
     r, post, stats, _ = _dense(prec, B, jts, stepper)
     _on_small_path(stats)
     assert sorted(I.m for I in r.islands) == [0, 3 * nc]
 
 
-@pytest.mark.parametrize("stepper", ["quick", "exact"])
-def test_dense_press_chain_f32(stepper):
-    """float32, both steppers, on a multi-body island whose rows all stay loaded (QuickStep in float32 is only comparable away
-    from clamps; asserted by _dense)"""
+def _press_chain_case():
     rng = np.random.default_rng(7)
     nb = 8
     pos = np.column_stack([np.zeros(nb), 0.5 + np.arange(nb), np.zeros(nb)])
@@ -244,12 +250,18 @@ def test_dense_press_chain_f32(stepper):
         d = np.array([np.cos(a), 0.0, np.sin(a)])
         out.append((np.array([0.0, float(k), 0.0]) + 0.3 * d, np.array([0.0, np.cos(0.6), 0.0]) + d * np.sin(0.6), 0.01, k, k - 1 if k else -1,
                     0, 0.0, 0, 0, 0, 0))
-    _, _, stats, _ = _dense("float32", B, np.array(out, ld.JOINT_DTYPE), stepper)
+    return B, np.array(out, ld.JOINT_DTYPE)
+
+
+@pytest.mark.parametrize("stepper", ["quick", "exact"])
+def test_dense_press_chain_f32(stepper):
+    """float32, both steppers, on a multi-body island whose rows all stay loaded"""
+    B, jts = _press_chain_case()
+    _, _, stats, _ = _dense("float32", B, jts, stepper)
     _on_small_path(stats)
 
 
-@pytest.mark.parametrize("prec,stepper", COMBOS)
-def test_dense_kinematic_body_under_a_stack(prec, stepper):
+def _kinematic_case(prec):
     rng = np.random.default_rng(21)
     B1, j1 = _chain(3, 9, 0.4, rng)
     n = 4
@@ -260,15 +272,18 @@ def test_dense_kinematic_body_under_a_stack(prec, stepper):
     jj["body1"] += 1; jj["body2"] = np.where(j1["body2"] >= 0, j1["body2"] + 1, 0)
     for f in ("pos", "quat", "lvel", "avel", "mass", "inertia"):
         setattr(B, f, getattr(B, f).astype(prec).astype(np.float64))
+    return B, jj
+
+
+@pytest.mark.parametrize("prec,stepper", COMBOS)
+def test_dense_kinematic_body_under_a_stack(prec, stepper):
+    B, jj = _kinematic_case(prec)
     r, post, stats, _ = _dense(prec, B, jj, stepper)
     _on_small_path(stats)
     assert np.array_equal(post[0, 7:13], np.concatenate([B.lvel[0], B.avel[0]]))          # the kinematic body keeps its velocity
 
 
-@pytest.mark.parametrize("prec,stepper", COMBOS)
-def test_dense_per_contact_surfaces_in_two_islands_sharing_a_static(prec, stepper):
-    """per-contact mu 0 / finite / inf, bounce on and off, soft ERP and soft CFM, in two islands that both rest on the static
-    ground"""
+def _surfaces_case():
     rng = np.random.default_rng(11)
     parts = []
     for k in range(2):
@@ -276,9 +291,25 @@ def test_dense_per_contact_surfaces_in_two_islands_sharing_a_static(prec, steppe
         j["mode"] = np.array([ld.CONTACT_BOUNCE, 0, ld.CONTACT_SOFT_ERP | ld.CONTACT_BOUNCE, ld.CONTACT_SOFT_CFM] * 3)
         j["bounce"], j["bounce_vel"], j["soft_erp"], j["soft_cfm"] = 0.7, 0.05, 0.8, 1e-3
         parts.append((B, j))
-    r, _, stats, _ = _dense(prec, *_join(parts), stepper)
+    return _join(parts)
+
+
+@pytest.mark.parametrize("prec,stepper", COMBOS)
+def test_dense_per_contact_surfaces_in_two_islands_sharing_a_static(prec, stepper):
+    """per-contact mu 0 / finite / inf, bounce on and off, soft ERP and soft CFM, in two islands that both rest on the static
+    ground"""
+    r, _, stats, _ = _dense(prec, *_surfaces_case(), stepper)
     _on_small_path(stats)
     assert sorted(I.m for I in r.islands) == [28, 28]
+
+
+# every float32 QuickStep case _dense runs: name -> () -> (Bodies, joints, World); tests/test_quick_band.py runs the float32
+# emulation of the reference's sweeps over them (population (b) of quick_band.MEASURED)
+F32_QUICK_CASES = {"press_chain": lambda: (*_press_chain_case(), ld.World(cfm=1e-5)),
+                   "kinematic": lambda: (*_kinematic_case("float32"), ld.World(cfm=1e-5)),
+                   "surfaces": lambda: (*_surfaces_case(), ld.World(cfm=1e-5))}
+for _nc in range(1, 9):
+    F32_QUICK_CASES[f"singles-{_nc}"] = lambda nc=_nc: (*_singles_case(nc), ld.World(cfm=1e-5))
 
 
 def _lds_fits(real_bytes, m, nbd, lim=150 * 1024):

@@ -2,6 +2,7 @@
 oracle's two steppers (oracle/orc_step.c) pinned by the reference.  The oracle and the HIP kernels were written by the same
 hand; the reference is a second route from the definitions (include/dmx_batch.h), so a mistake
 shared by the first two shows up here.  CPU only."""
+import functools
 import os
 import subprocess
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 import lcp_dense as ld
+import quick_band as qb
 from __graft_entry__ import load_package
 
 H = 1.0 / 60.0
@@ -250,6 +252,57 @@ def test_oracle_tick_equals_the_dense_reference(orc64, scene, mu, bounce, gyro, 
         lam_ref = r.normal_lambda(len(jts))
         lam_orc = np.array([x[5] for x in raw])
         assert np.max(np.abs(lam_orc - lam_ref)) <= 1e-10 * max(1.0, np.max(np.abs(lam_ref)))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_tick_f32(orc, scene, mu, bounce, gyro):
+    """one QuickStep tick of the float32 oracle at cfm 1e-5 and the reference built from the oracle's own float32 pre-tick
+    state, world parameters and joints (as tests/test_gpu_solver_dense.py as_precision does for a float32 batch).
+    -> (reference Result, World, oracle's post-tick state (n, 13), oracle's normal lambdas, joints); shared, unchanged,
+    by every test that needs it (tests/test_quick_band.py measures the band's K on these)"""
+    r32 = lambda x: np.asarray(x, np.float32).astype(np.float64)
+    w, mass, inertia = _oracle_world(orc, scene, seed=7)
+    orc.lib.orc_world_set_cfm(w.w, 1e-5)
+    mode = ld.CONTACT_BOUNCE if bounce else 0
+    orc.lib.orc_world_set_surface(w.w, mode, mu, 0.2, 0.1)
+    orc.lib.orc_world_set_gyro_mode(w.w, gyro)
+    w.set_stepper(False)
+    pos, quat, lv, av = [np.asarray(x, np.float64) for x in w.state()]
+    w.tick(H)
+    post = np.column_stack([np.asarray(x, np.float64) for x in w.state()])
+    raw = w.joints()
+    w.close()
+    assert raw, "the scene makes no contacts"
+    jts = np.array([(p, n, d, b1, b2, mode, float(r32(mu)), float(r32(0.2)), float(r32(0.1)), 0.0, 0.0)
+                    for b1, b2, p, n, d, _ in raw], ld.JOINT_DTYPE)
+    B = ld.Bodies(pos, quat, lv, av, r32(mass), r32(inertia))
+    W = ld.World(h=float(r32(H)), gravity=r32([0.0, -9.8, 0.0]), erp=float(r32(0.2)), cfm=float(r32(1e-5)),
+                 sor_w=float(r32(1.3)), gyro=gyro)
+    return ld.step(B, W, jts, "quick"), W, post, np.array([x[5] for x in raw], np.float64), jts
+
+
+@pytest.mark.parametrize("gyro", [ld.GYRO_OFF, ld.GYRO_EXPLICIT, ld.GYRO_IMPLICIT])
+@pytest.mark.parametrize("bounce", [False, True])
+@pytest.mark.parametrize("mu", [0.0, 0.3, np.inf])
+@pytest.mark.parametrize("scene", SCENES)
+def test_oracle_tick_equals_the_dense_reference_f32(orc32, scene, mu, bounce, gyro):
+    """the float32 oracle's QuickStep -- the arithmetic of every float32 kernel that collides for itself, bit for bit -- against
+    the float64 reference, clamps included: velocities, positions and quaternions per body within the band of
+    tests/quick_band.py (K eps32 M_v; no clamp-margin gate), and the normal lambda within K eps32 max |lambda| on the rows
+    whose own reference margin is above 1e-3 of the island's largest |lambda| (a row that sits at its bound may differ by a
+    flip; velocities may not)."""
+    r, W, post, lam_orc, jts = oracle_tick_f32(orc32, scene, mu, bounce, gyro)
+    K = qb.K["contact"]
+    worst = qb.assert_in_band(r, W, post, K, what=f"float32 oracle {scene}")
+    print(f"f32 oracle {scene} mu={mu} bounce={bounce} gyro={gyro}: {worst:.2f} eps32 M_v (K = {K})")
+    for I, lam in zip(r.islands, r.lams):
+        if not I.m:
+            continue
+        _, margins = qb.row_margins(I, W.iters, W.sor_w)
+        top = np.max(np.abs(lam))
+        ok = (I.row_kind == 0) & (margins > 1e-3 * top)
+        d = np.abs(lam_orc[I.row_joint[ok]] - lam[ok])
+        assert np.all(d <= K * qb.EPS32 * top), f"normal lambda off by {d.max() / (qb.EPS32 * top):.2f} eps32 max|lambda|"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
