@@ -201,6 +201,62 @@ def hanging_chain(n, spacing=1.0, horizontal=False, mass=1.0, bend=0.0):
     return B, art
 
 
+def plan_rows(rows, cycle, reserve=0):
+    """-> a list of (kind, rows) joints whose row counts and `reserve` sum to exactly `rows`: the entries of `cycle` in turn (each
+    a (kind, rows) pair; the kinds are dmxJoint's) while 8 or more rows remain, then a tail of balls (3 rows) and plain hinges (5),
+    which make every count from 8 on"""
+    plan, left, k = [], rows - reserve, 0
+    while left - cycle[k % len(cycle)][1] >= 8:
+        plan.append(cycle[k % len(cycle)])
+        left -= plan[-1][1]
+        k += 1
+    hinges = next(j for j in range(left // 5 + 1) if (left - 5 * j) % 3 == 0)
+    plan += [(HINGE, 5)] * hinges + [(BALL, 3)] * ((left - 5 * hinges) // 3)
+    assert sum(r for _, r in plan) + reserve == rows
+    return plan
+
+
+def chain(kinds, seed, spacing=1.0, bend=2.0):
+    """one body per entry of `kinds`, joint k of that kind between body k and body k - 1 (joint 0 to the world) where the two
+    links meet; the chain starts at the origin and turns by `bend` in all in the xy plane (hanging_chain's layout).  Random
+    rotations -- no R is exact in float32 --, velocities, masses and inertias, random axes.  The joints are made at these
+    poses, so their errors are zero: take the zero poses of the limots, then `disturb`.  -> (Bodies, joints)"""
+    rng = np.random.default_rng(seed)
+    n = len(kinds)
+    ang = bend * (np.arange(n) + 0.5) / n
+    d = np.column_stack([np.sin(ang), -np.cos(ang), np.zeros(n)]) * spacing
+    ends = np.vstack([np.zeros(3), np.cumsum(d, axis=0)])
+    quat = rng.normal(size=(n, 4))
+    quat /= np.linalg.norm(quat, axis=1)[:, None]
+    B = ld.Bodies(0.5 * (ends[:-1] + ends[1:]), quat, rng.normal(scale=0.3, size=(n, 3)), rng.normal(scale=0.3, size=(n, 3)),
+                  rng.uniform(0.5, 2.0, n), rng.uniform(0.3, 1.0, (n, 3)))
+    art = np.array([from_world(B, kind, k, k - 1, ends[k], rng.normal(size=3)) for k, kind in enumerate(kinds)], ART_DTYPE)
+    return B, art
+
+
+def disturb(B, seed, dist=2e-3, turn=2e-3):
+    """move every body by `dist` in a random direction and turn it by `turn` rad about a random axis, in place: every joint made
+    before has a position error of about `dist` and an axis / lock error of about `turn` to correct"""
+    rng = np.random.default_rng(seed + 1000)
+    u = rng.normal(size=(B.n, 3))
+    B.pos += dist * u / np.linalg.norm(u, axis=1)[:, None]
+    u = rng.normal(size=(B.n, 3))
+    u *= np.sin(0.5 * turn) / np.linalg.norm(u, axis=1)[:, None]
+    for s in range(B.n):
+        q = ld.quat_mul(np.concatenate([[np.cos(0.5 * turn)], u[s]]), B.quat[s])
+        B.quat[s] = q / np.linalg.norm(q)
+    return B
+
+
+def ball_hinge_chain(rows, seed=0):
+    """a chain of alternating ball and hinge joints whose one island has exactly `rows` rows, with errors to correct: slow to
+    converge under QuickStep -- a sweep dropped, or another sor_w, moves its velocities by far more than float32 rounding does.
+    (Errors of 5e-3 m: 1 % of ERP moves c by 1 % of (ERP / h) x the error, and the band allows K eps32 (ERP / h) (|a_1| + |a_2|)
+    with arms of 0.5 -- at 2e-3 m that is 170 / K bands, too near the 10 asked for)"""
+    B, art = chain([k for k, _ in plan_rows(rows, [(BALL, 3), (HINGE, 5)])], seed)
+    return disturb(B, seed, dist=5e-3), art
+
+
 def star(n, hub_mass=100.0, radius=2.0, seed=0):
     """n unit bodies ball-jointed to a hub (slot 0) of mass and inertia hub_mass, spread over a sphere of `radius` round it,
     the anchors midway; small random velocities"""

@@ -306,6 +306,19 @@ def doors(n, nfree=0, seed=7):
     return B, art, lim
 
 
+def hinge_limot_chain(rows, seed=0):
+    """joint_dense's slowly converging chain with a limot on every hinge, cycling through MODES -- every line of the table, the
+    motor-at-a-stop variants included -- and a ball after every second hinge; the zero poses are the poses the joints were made
+    at, then every body is disturbed (joint_dense.disturb): |theta| <= 4e-3 rad, 0.006 or more from every stop"""
+    plan = jd.plan_rows(rows, [(jd.HINGE, 6), (jd.HINGE, 6), (jd.BALL, 3)])
+    B, art = jd.chain([k for k, _ in plan], seed)
+    lim = limots(B, art)
+    names = list(MODES)
+    for n, k in enumerate(k for k, (_, r) in enumerate(plan) if r == 6):
+        set_mode(lim[k], names[n % len(names)])
+    return jd.disturb(B, seed), art, lim
+
+
 def small_world(seed=13):
     """48 bodies: 12 two-body pendulums (world - ball - body - hinge with a limot - body), 8 doors, 8 bodies on ground contacts
     and 8 free bodies"""

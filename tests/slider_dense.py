@@ -356,6 +356,37 @@ def all_kinds_chain(seed=11):
     return B, art, lim
 
 
+def mixed_chain(rows, seed=0, contacts=False):
+    """joint_dense's slowly converging chain over all four kinds -- hinge with a limot, ball, slider with a limot, fixed, plain
+    hinge, plain slider in turn -- whose one island has exactly `rows` rows; the limots cycle through MODES (every line of the
+    table, in radians on the hinges and metres on the sliders), their zero poses the poses the joints were made at, then every
+    body is disturbed: |theta| <= 4e-3 rad, |s| a few 1e-3 m, 0.006 or more from every stop at the sizes the tests use (the GPU
+    files assert 1e-3 per tick).
+    contacts: every eighth body also has a ground contact under it -- mu cycling through 0.5, inf and 0, every other one with
+    bounce -- and moves down or up in turn, so that normal rows end loaded and at 0 and friction rows at their bounds; the
+    contacts' rows count towards `rows`"""
+    cycle = [(HINGE, 6), (BALL, 3), (SLIDER, 6), (FIXED, 6), (HINGE, 5), (SLIDER, 5)]
+    mus, reserve = [], 0
+    if contacts:
+        nb = rows // 6                                     # (fewer bodies than the plan will have: it averages 5.2 rows a joint)
+        mus = [(0.5, np.inf, 0.0)[c % 3] for c in range(nb // 8)]
+        reserve = sum(3 if mu > 0 else 1 for mu in mus)
+    plan = jd.plan_rows(rows, cycle, reserve)
+    B, art = jd.chain([k for k, _ in plan], seed)
+    lim = limots(B, art)
+    names = list(MODES)
+    for n, k in enumerate(k for k, (_, r) in enumerate(plan) if r == 6 and plan[k][0] != FIXED):
+        set_mode(lim[k], names[n % len(names)])
+    jd.disturb(B, seed)
+    jts = []
+    for c, mu in enumerate(mus):
+        s = 8 * c + 3
+        B.lvel[s] = (0.3, -1.0 if c % 4 != 3 else 1.0, 0.2)
+        nrm = _unit((0.1 * (c % 3 - 1), 1.0, 0.15 * (c % 2)))
+        jts.append((B.pos[s] + (0.0, -0.5, 0.0), nrm, 0.01, s, -1, ld.CONTACT_BOUNCE if c % 2 else 0, mu, 0.7, 0.05, 0, 0))
+    return B, art, lim, np.array(jts, ld.JOINT_DTYPE) if jts else np.zeros(0, ld.JOINT_DTYPE)
+
+
 def star(n, seed=0, contacts=False):
     """joint_dense's star round a heavy hub, the spokes on sliders along random axes (k % 3 != 2) and welds (k % 3 == 2), given
     as (spoke, hub) and every fourth as (hub, spoke); the sliders' limots cycle through free motor, at the low stop, at the high

@@ -7,14 +7,24 @@ aim at the kernel choices an island makes once it holds joint rows: a one-body i
 kernels, islands without a single bounded row on the LDS solve and on the grid solve, mixed islands, the one-wavefront and
 workgroup SOR forms on either side of 256 rows, and many small islands next to free bodies and contact-only singles.
 
-Tolerances are that file's three rules (velocities, relative to max(|v_ref|, g h)): float64 QuickStep 1e-10, float64 dWorldStep
-1e-8, float32 10 eps32 kappa(A) with kappa from the reference; a case whose float32 tolerance exceeded 1e-3 would not be a test
-(asserted).  Topologies are chosen for that: 8-link chains (kappa ~ 1e2) and stars round a heavy hub (kappa ~ 3)."""
+Tolerances are that file's (velocities): float64 QuickStep 1e-10 and float64 dWorldStep 1e-8, relative to max(|v_ref|, g h);
+float32 dWorldStep 10 eps32 kappa(A) with kappa from the reference -- a case whose float32 tolerance exceeded 1e-3 would not be a
+test (asserted), and topologies are chosen for that: 8-link chains (kappa ~ 1e2) and stars round a heavy hub (kappa ~ 3); float32
+QuickStep the per-body band of tests/quick_band.py with the joint rows' term, K = quick_band.K["joint"] measured on the CPU
+(tests/test_quick_band.py), no gate and no admission rule -- and, so that no case is held to less than before, the old allowance
+10 eps32 kappa(A) as a second ceiling wherever the old rule admits the tick (quick_band.assert_in_old_allowance; it is no gate:
+a tick it does not admit is held to the band alone).  Every float32 QuickStep case is listed in F32_QUICK_CASES, which
+tests/test_quick_band.py runs the float32 emulation over; CHAIN_CASES are the ones a dropped sweep cannot pass."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 import joint_dense as jd
 import lcp_dense as ld
+import quick_band as qb
 from __graft_entry__ import load_package
 
 pkg = load_package()
@@ -26,6 +36,7 @@ EPS32 = float(np.finfo(np.float32).eps)
 PRECS = ["float64", "float32"]
 STEPPERS = ["quick", "exact"]
 EINVAL = -3
+DEVICE_WORST = {"joint": 0.0}            # the largest device deviation of this process, in eps32 M_v (printed by compare)
 
 
 def world(**kw):
@@ -93,16 +104,23 @@ def compare(run, Bp, post, jts):
     Wr, jr, ar = as_precision(prec, run.W, jts, run.art)
     r = jd.step(Bp, Wr, jr, ar, stepper)
     f32 = np.dtype(prec).itemsize == 4
+    live = np.nonzero(Bp.flags & ld.ALIVE)[0]
+    dead = np.nonzero(~(Bp.flags & ld.ALIVE).astype(bool))[0]
+    if len(dead):
+        assert np.array_equal(post[dead], np.column_stack([Bp.pos, Bp.quat, Bp.lvel, Bp.avel])[dead]), "a dead slot changed"
+    if f32 and stepper == "quick":
+        qb.attach_joint_term(r, Bp, Wr, jr, ar)
+        worst = qb.assert_in_band(r, Wr, post, qb.K["joint"], live)
+        DEVICE_WORST["joint"] = max(DEVICE_WORST["joint"], worst)
+        used = qb.assert_in_old_allowance(r, Wr, post, live)
+        print(f"f32 QuickStep on the device: {worst:.2f} eps32 M_v (K = {qb.K['joint']}; largest so far {DEVICE_WORST['joint']:.2f}); "
+              + ("the old rule does not admit the tick" if used is None else f"{used:.3f} of the old allowance"))
+        return r
     if not f32:
         t = 1e-10 if stepper == "quick" else 1e-8
     else:
         t = 10 * EPS32 * max([I.kappa() for I in r.islands] + [1.0])
         assert t <= 1e-3, f"float32 tolerance {t:.2e}: too ill-conditioned a case to be a test"
-        if stepper == "quick":
-            for I, lam, margin in zip(r.islands, r.lams, r.margins):
-                if I.m:
-                    assert margin > 1e-3 * np.max(np.abs(lam)), "f32 QuickStep case too close to a clamp to compare"
-    live = np.nonzero(Bp.flags & ld.ALIVE)[0]
     scale = ld.velocity_scale(r.bodies, Wr, live)
     err = ld.velocity_error(r.bodies, post[:, 7:10], post[:, 10:13], live)
     print(f"{prec} {stepper}: velocity error {err:.3e}, allowed {t:.1e} x {scale:.3e}")
@@ -112,9 +130,6 @@ def compare(run, Bp, post, jts):
     assert xerr <= t * scale * Wr.h + eps * max(1.0, np.max(np.abs(r.bodies.pos[live]))), f"position error {xerr:.3e}"
     qerr = np.max(np.abs(post[live, 3:7] - r.bodies.quat[live]))
     assert qerr <= t * scale * Wr.h + eps, f"quaternion error {qerr:.3e}"
-    dead = np.nonzero(~(Bp.flags & ld.ALIVE).astype(bool))[0]
-    if len(dead):
-        assert np.array_equal(post[dead], np.column_stack([Bp.pos, Bp.quat, Bp.lvel, Bp.avel])[dead]), "a dead slot changed"
     return r
 
 
@@ -296,6 +311,72 @@ def test_many_small_islands(prec, stepper):
     res, _, _, _ = check(prec, B, world(), art, stepper, jts)
     ms = sorted(I.m for I in res[0].islands)
     assert ms.count(8) == 40 and ms.count(0) == 5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Chains a wrong sweep cannot pass (joint_dense.ball_hinge_chain: rotated bodies, errors to correct, slow to converge), one island
+# each, on the QuickStep row forms an island with joint rows takes -- units keep an island off the contact-as-unit forms
+# (csrc/dmx_islands_dev.hpp, solve_island_wg_body): the lane-per-island form (a child process), the one-wavefront form up to
+# WAVE_ISLAND_ROWS = 256 rows on the single-launch tick and on the general path, and just past it the 256-thread register form.
+# tests/test_gpu_hinge_limot.py and tests/test_gpu_slider.py hold the forms further up.
+CHAIN_CASES = ["ball_hinge_chain-40", "ball_hinge_chain-256", "ball_hinge_chain-260"]
+FORM_CASES = {"lane per island": ["ball_hinge_chain-40"], "single-launch tick": ["ball_hinge_chain-256"],
+              "one wavefront": ["ball_hinge_chain-256"], "registers, 256 threads": ["ball_hinge_chain-260"]}
+
+
+@pytest.mark.parametrize("rows,small", [(256, B_.SMALL_TICK_AUTO), (256, B_.SMALL_TICK_OFF), (260, B_.SMALL_TICK_AUTO)])
+def test_quickstep_chain_of_balls_and_hinges_f32(rows, small):
+    """256 rows: the one-wavefront form, on the single-launch tick and on the general path; 260: the single-launch tick refuses
+    the island (more rows than one wavefront holds) and the general path runs the 256-thread register form"""
+    B, art = jd.ball_hinge_chain(rows)
+    (r,), _, st, _ = check("float32", B, world(), art, "quick", small=small)
+    assert [I.m for I in r.islands] == [rows] and r.islands[0].nbd == 0
+    on_small = small == B_.SMALL_TICK_AUTO and rows <= 256
+    assert (st["small"], st["general"]) == ((1, 0) if on_small else (0, 1)), st
+    if small == B_.SMALL_TICK_AUTO and not on_small:
+        assert st["sor_rows"] == 1, st
+
+
+def child_lane_per_island_chain_f32():
+    """(run by test_chain_on_the_lane_per_island_form_f32 under DMX_BIG_ISLAND_ROWS=64) a chain of 40 rows on 10 bodies with the
+    single-launch tick off: the general path gives an island a workgroup only from that many rows on, so this one is swept by
+    one lane (row_sor in solve_islands), as one-body islands on a joint always are"""
+    threshold = int(os.environ["DMX_BIG_ISLAND_ROWS"])
+    B, art = jd.ball_hinge_chain(40)
+    (r,), _, st, _ = check("float32", B, world(), art, "quick", small=B_.SMALL_TICK_OFF)
+    (I,) = r.islands
+    assert I.m == 40 < threshold and len(I.slots) == 10
+    assert (st["small"], st["general"]) == (0, 1), st
+
+
+def test_chain_on_the_lane_per_island_form_f32():
+    """DMX_BIG_ISLAND_ROWS is read once per process: a child"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r]; import test_gpu_joints as t; t.child_lane_per_island_chain_f32(); "
+            "print('CHILD-OK')") % (here, os.path.dirname(here))
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
+                       env={**os.environ, "DMX_BIG_ISLAND_ROWS": "64"})
+    assert p.returncode == 0 and "CHILD-OK" in p.stdout, (p.stdout[-2000:] + p.stderr[-3000:])
+
+
+# every float32 QuickStep case `compare` sees: name -> () -> (Bodies, World, contact joints, joints, limots (none here), ticks).
+# tests/test_quick_band.py runs the float32 emulation of a float32 batch's rows and sweeps over them (quick_band.MEASURED["joint"])
+def _case(B, art, jts=NO_CONTACTS, ticks=1):
+    return B, world(), jts, art, None, ticks
+
+
+F32_QUICK_CASES = {
+    "one_body-ball": lambda: _case(*one_body(jd.BALL)), "one_body-hinge": lambda: _case(*one_body(jd.HINGE)),
+    "two_bodies-plain": lambda: _case(*two_bodies(), ticks=2),
+    "two_bodies-body1_is_world": lambda: _case(*two_bodies(first_is_world_side=True), ticks=2),
+    "two_bodies-kinematic": lambda: _case(*two_bodies(kinematic=True), ticks=2),
+    "chain_on_ground": lambda: _case(*chain_on_ground()),
+    "star-64": lambda: _case(*jd.star(64)), "star-90": lambda: _case(*jd.star(90)),
+    "star_on_ground-100": lambda: _case(*star_on_ground(100)),
+    "pendulum_pairs": lambda: _case(*pendulum_pairs()),
+}
+for _rows in (40, 256, 260):
+    F32_QUICK_CASES[f"ball_hinge_chain-{_rows}"] = lambda rows=_rows: _case(*jd.ball_hinge_chain(rows))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

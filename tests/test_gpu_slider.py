@@ -4,17 +4,24 @@ with these joints (tests/slider_dense.py).
 
 Run and the tolerances are test_gpu_hinge_limot.py's: every case uploads a synthetic state, a set of joints with limots and a list
 of contact joints, takes a tick (or a few) and compares each with the reference restarted from the device's own pre-tick state.
-The three rules are that file's, unchanged (velocities, relative to max(|v_ref|, g h)): float64 QuickStep 1e-10, float64 dWorldStep
-1e-8, float32 10 eps32 kappa(A) with kappa from the reference, asserted <= 1e-3, plus the float32 QuickStep clamp-margin rule; and
-its THETA_MARGIN rule, here also in metres: every compared tick asserts that the reference's hinges and sliders are 1e-3 (rad, m) or
-more from their stops.  Scenes stay within a few metres of the origin, so that float32 cannot disagree about a slider's line.  The
-scenes' seeds are ones for which the reference meets these conditions, found on the CPU."""
+Velocities: float64 QuickStep 1e-10 and float64 dWorldStep 1e-8 relative to max(|v_ref|, g h), float32 dWorldStep 10 eps32 kappa(A)
+with kappa from the reference, asserted <= 1e-3, float32 QuickStep the per-body band of tests/quick_band.py with the joint rows' term
+at K = quick_band.K["joint"], no clamp-margin gate (the old allowance stays as a second ceiling where the old rule admits the tick:
+quick_band.assert_in_old_allowance); and that file's THETA_MARGIN rule, here also in metres: every compared tick
+asserts that the reference's hinges and sliders are 1e-3 (rad, m) or more from their stops.  Every float32 QuickStep case is listed
+in F32_QUICK_CASES (tests/test_quick_band.py runs the float32 emulation over them); CHAIN_CASES are the ones a dropped sweep cannot
+pass.  (tests/test_gpu_feedback.py takes `reference_tick` with the rules this file had before the band.)"""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 import joint_dense as jd
 import lcp_dense as ld
 import limot_dense as lm
+import quick_band as qb
 import slider_dense as sd
 import test_gpu_hinge_limot as hl
 from __graft_entry__ import load_package
@@ -32,16 +39,21 @@ THETA_MARGIN = hl.THETA_MARGIN
 NO_CONTACTS = hl.NO_CONTACTS
 Run, world, as_precision, to_c = hl.Run, hl.world, hl.as_precision, hl.to_c
 SMALL = [B_.SMALL_TICK_OFF, B_.SMALL_TICK_AUTO]
+DEVICE_WORST = {"joint": 0.0}            # the largest device deviation of this process, in eps32 M_v (printed by compare)
 
 
-def reference_tick(prec, stepper, W, Bp, jts, art, lim):
-    """the reference's tick of a batch of this precision, and the tolerance it allows by test_gpu_hinge_limot.compare's rules"""
+def reference_tick(prec, stepper, W, Bp, jts, art, lim, band=False):
+    """the reference's tick of a batch of this precision, and the tolerance it allows by test_gpu_hinge_limot.compare's rules.
+    band: float32 QuickStep is held to the band of tests/quick_band.py instead (tolerance None, the joint term attached); without it
+    the rule from before the band, 10 eps32 kappa(A) where the clamp-margin gate passes"""
     Wr, jr, ar, lr = as_precision(prec, W, jts, art, lim)
     r = sd.step(Bp, Wr, jr, ar, lr, stepper)
     tm = min(lm.theta_margin(r), sd.pos_margin(r))
     print(f"{prec} {stepper}: stop margin {tm:.3e}")
     assert tm >= THETA_MARGIN, f"a hinge or a slider is {tm:.2e} from a stop: too close for two precisions to agree on the row"
     f32 = np.dtype(prec).itemsize == 4
+    if f32 and stepper == "quick" and band:
+        return qb.attach_joint_term(r, Bp, Wr, jr, ar, lr), Wr, None
     if not f32:
         t = 1e-10 if stepper == "quick" else 1e-8
     else:
@@ -57,9 +69,16 @@ def reference_tick(prec, stepper, W, Bp, jts, art, lim):
 def compare(run, Bp, post, jts):
     """one device tick against the reference from the same pre-tick state; -> the reference's Result"""
     prec, stepper = run.prec, run.stepper
-    r, Wr, t = reference_tick(prec, stepper, run.W, Bp, jts, run.art, run.lim)
+    r, Wr, t = reference_tick(prec, stepper, run.W, Bp, jts, run.art, run.lim, band=True)
     f32 = np.dtype(prec).itemsize == 4
     live = np.nonzero(Bp.flags & ld.ALIVE)[0]
+    if t is None:
+        worst = qb.assert_in_band(r, Wr, post, qb.K["joint"], live)
+        DEVICE_WORST["joint"] = max(DEVICE_WORST["joint"], worst)
+        used = qb.assert_in_old_allowance(r, Wr, post, live)
+        print(f"f32 QuickStep on the device: {worst:.2f} eps32 M_v (K = {qb.K['joint']}; largest so far {DEVICE_WORST['joint']:.2f}); "
+              + ("the old rule does not admit the tick" if used is None else f"{used:.3f} of the old allowance"))
+        return r
     scale = ld.velocity_scale(r.bodies, Wr, live)
     err = ld.velocity_error(r.bodies, post[:, 7:10], post[:, 10:13], live)
     print(f"{prec} {stepper}: velocity error {err:.3e}, allowed {t:.1e} x {scale:.3e}")
@@ -260,6 +279,106 @@ def test_small_tick_and_general_path_agree_bit_for_bit(prec, stepper):
 def test_small_world_against_the_reference(prec, stepper):
     B, art, lim, jts = sd.small_world(WORLD_SEED)
     check(prec, B, world(), art, lim, stepper, jts)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Chains a wrong sweep cannot pass (slider_dense.mixed_chain: all four kinds, rotated bodies, errors to correct, limots on hinges and
+# sliders over every line of the table), one island each on either side of every boundary between the float32 QuickStep row forms
+# an island with joint rows takes -- units keep it off the contact-as-unit forms (csrc/dmx_islands_dev.hpp, solve_island_wg_body):
+#   up to WAVE_ISLAND_ROWS = 256 rows   one wavefront, the rows in registers; the single-launch tick takes such a world too
+#   257 .. 1 024                        the register form, 256 threads
+#   1 025 .. REGS_ROWS<float> = 3 072   the register form, 512 threads
+#   above                               the streamed form
+# and 40 rows on the lane-per-island form (a child process).  One more has ground contacts that clamp among the joint rows.
+CHAIN_FORMS = {256: "one wavefront", 260: "registers, 256 threads", 1024: "registers, 256 threads", 1028: "registers, 512 threads",
+               3072: "registers, 512 threads", 3076: "streamed"}
+CHAIN_CASES = ["mixed_chain-40"] + [f"mixed_chain-{rows}" for rows in CHAIN_FORMS] + ["mixed_chain_on_ground-1028"]
+FORM_CASES = {"lane per island": ["mixed_chain-40"], "single-launch tick": ["mixed_chain-256"]}
+for _rows, _form in CHAIN_FORMS.items():
+    FORM_CASES.setdefault(_form, []).append(f"mixed_chain-{_rows}")
+FORM_CASES["registers, 512 threads"].append("mixed_chain_on_ground-1028")
+
+
+def _chain_checks(r, rows, contacts=False):
+    (I,), (lam,) = r.islands, r.lams
+    assert I.m == rows and set(I.limot_lines) == {0, 1, 2, 3, 4}
+    at = [k for k in I.limot_rows if np.isfinite(I.lo[k]) or np.isfinite(I.hi[k])]
+    assert any(lam[k] in (I.lo[k], I.hi[k]) for k in at) and any(lam[k] not in (I.lo[k], I.hi[k]) for k in at)
+    if contacts:
+        fr = np.isfinite(I.hi) & (I.row_kind > 0)
+        assert np.any(lam[I.row_kind == 0] == 0) and np.any(lam[I.row_kind == 0] > 0), "normal rows: loaded and at 0"
+        assert np.any(lam[fr] == I.hi[fr]) and np.any(lam[fr] == I.lo[fr]), "friction rows at both bounds"
+        assert I.m - I.n_art_rows == np.sum(I.row_kind >= 0) > 20
+
+
+@pytest.mark.parametrize("rows", sorted(CHAIN_FORMS))
+def test_quickstep_chain_of_all_kinds_on_every_row_form_f32(rows):
+    B, art, lim, jts = sd.mixed_chain(rows)
+    (r,), _, st, _ = check("float32", B, world(), art, lim, "quick", jts, small=B_.SMALL_TICK_OFF)
+    _chain_checks(r, rows)
+    assert (st["small"], st["general"]) == (0, 1), st
+
+
+def test_quickstep_chain_of_all_kinds_on_the_single_launch_tick_f32():
+    B, art, lim, jts = sd.mixed_chain(256)
+    (r,), _, st, _ = check("float32", B, world(), art, lim, "quick", jts, small=B_.SMALL_TICK_AUTO)
+    _chain_checks(r, 256)
+    assert (st["small"], st["general"]) == (1, 0), st
+
+
+def test_quickstep_chain_with_ground_contacts_that_clamp_f32():
+    """1 028 rows, 512-thread register form: joint rows, limot rows and contact rows with friction in one island; normal rows end
+    loaded and at 0, friction rows at both bounds (asserted on the reference), and nothing gates them"""
+    B, art, lim, jts = sd.mixed_chain(1028, contacts=True)
+    (r,), _, st, _ = check("float32", B, world(), art, lim, "quick", jts, small=B_.SMALL_TICK_OFF)
+    _chain_checks(r, 1028, contacts=True)
+    assert (st["small"], st["general"]) == (0, 1), st
+
+
+def child_lane_per_island_chain_f32():
+    """(run by test_chain_on_the_lane_per_island_form_f32 under DMX_BIG_ISLAND_ROWS=64) 40 rows of all four kinds on 9 bodies with
+    the single-launch tick off: swept by one lane (row_sor in solve_islands)"""
+    threshold = int(os.environ["DMX_BIG_ISLAND_ROWS"])
+    B, art, lim, jts = sd.mixed_chain(40)
+    (r,), _, st, _ = check("float32", B, world(), art, lim, "quick", jts, small=B_.SMALL_TICK_OFF)
+    (I,) = r.islands
+    assert I.m == 40 < threshold and len(I.slots) > 1 and {sd.HINGE, sd.BALL, sd.SLIDER, sd.FIXED} <= set(art["kind"].tolist())
+    assert (st["small"], st["general"]) == (0, 1), st
+
+
+def test_chain_on_the_lane_per_island_form_f32():
+    """DMX_BIG_ISLAND_ROWS is read once per process: a child"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r]; import test_gpu_slider as t; t.child_lane_per_island_chain_f32(); "
+            "print('CHILD-OK')") % (here, os.path.dirname(here))
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
+                       env={**os.environ, "DMX_BIG_ISLAND_ROWS": "64"})
+    assert p.returncode == 0 and "CHILD-OK" in p.stdout, (p.stdout[-2000:] + p.stderr[-3000:])
+
+
+# every float32 QuickStep case `compare` sees: name -> () -> (Bodies, World, contact joints, joints, limots, ticks).
+# tests/test_quick_band.py runs the float32 emulation of a float32 batch's rows and sweeps over them (quick_band.MEASURED["joint"])
+def _case(B, art, lim, jts=NO_CONTACTS, ticks=1):
+    return B, world(), jts, art, lim, ticks
+
+
+F32_QUICK_CASES = {
+    "one_body_per_mode": lambda: _case(*sd.one_body_per_mode(False, MODE_SEED)),
+    "one_body_per_mode-swapped": lambda: _case(*sd.one_body_per_mode(True, MODE_SEED)),
+    "one_body_fixed": lambda: _case(*sd.one_body(None, False, MODE_SEED, kind=sd.FIXED), ticks=2),
+    "one_body_fixed-swapped": lambda: _case(*sd.one_body(None, True, MODE_SEED, kind=sd.FIXED), ticks=2),
+    "cart_pole": lambda: _case(*sd.cart_pole(), ticks=3),
+    "all_kinds_chain": lambda: _case(*sd.all_kinds_chain(CHAIN_SEED)),
+    "star_on_ground-8": lambda: _case(*sd.star(8, seed=STAR_GROUND_SEED, contacts=True)),
+    "small_world": lambda: _case(*sd.small_world(WORLD_SEED)),
+}
+for _n in (8, 40, 100):
+    F32_QUICK_CASES[f"star-{_n}"] = lambda n=_n: _case(*sd.star(n, seed=STAR_SEEDS[n]))
+for _kind, _mode in [(sd.SLIDER, "motor_free"), (sd.SLIDER, "low_stop_motor_into"), (sd.SLIDER, None), (sd.FIXED, None)]:
+    F32_QUICK_CASES[f"two_bodies-{_kind}-{_mode}"] = lambda k=_kind, m=_mode: _case(*sd.two_bodies(k, m, kinematic=True, seed=TWO_SEED), ticks=2)
+for _rows in [40] + sorted(CHAIN_FORMS):
+    F32_QUICK_CASES[f"mixed_chain-{_rows}"] = lambda rows=_rows: _case(*sd.mixed_chain(rows))
+F32_QUICK_CASES["mixed_chain_on_ground-1028"] = lambda: _case(*sd.mixed_chain(1028, contacts=True))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

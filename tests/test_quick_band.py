@@ -7,7 +7,11 @@
   2. The clamp-margin gate the band replaces refused 84 of the 90 oracle scenes; on those no float32 oracle deviation exceeds
      K -- the clamp is non-expansive, so a decision flipped next to a bound moves lambda by no more than the rounding did.
   3. The band can tell: the reference with one parameter changed -- one sweep fewer, another sor_w, friction bounds 1 % off, a
-     surface flag ignored -- leaves the unchanged reference's band by 10 x or more on at least one body."""
+     surface flag ignored -- leaves the unchanged reference's band by 10 x or more on at least one body.
+  4. Islands with joint rows: the record that M_v without the joint rows' term needs K above 64; the family's population with the
+     term and everything a float32 batch computes for a joint row emulated in float32 (K["joint"]); the band against the allowance
+     it replaces, case by case; and the chains of the joint files, on each of which 19 sweeps, sor_w 1.25, ERP x 1.01 and the
+     world's CFM ignored leave the band by 10 x or more -- one per file and per device form at least for the dropped sweep."""
 import functools
 
 import numpy as np
@@ -15,8 +19,6 @@ import pytest
 
 import lcp_dense as ld
 import quick_band as qb
-import joint_dense as jd
-import limot_dense as lm
 import slider_dense as sd
 import test_gpu_body_flags as gbf
 import test_gpu_hinge_limot as ghl
@@ -202,132 +204,160 @@ def test_the_band_can_tell(name):
 
 
 # --------------------------------------------------------------------------------------------------------------------- 4
-# Islands with joint rows: why the three joint files (test_gpu_joints.py, test_gpu_hinge_limot.py, test_gpu_slider.py) are NOT on
-# the band.  Every float32 QuickStep case their `compare` sees, as (step function, Bodies, World, contact joints, joints, limots,
-# ticks[, before(t, limots)]); a later tick starts from the reference's last state.
-def _w():
-    return ld.World(cfm=1e-5)
-
-
-def _motor_door():
-    B, art, lim, W = ghl.motor_door()
-
-    def before(t, lim):
-        lim["vel"][0] = ghl.motor_vel(t)
-    return B, W, ghl.NO_CONTACTS, art, lim, ghl.MOTOR_TICKS, before
-
-
-def _j(B, art, jts=gj.NO_CONTACTS, ticks=1):
-    return B, _w(), jts, art, None, ticks
-
-
-def _l(B, art, lim, jts=ghl.NO_CONTACTS, ticks=1):
-    return B, _w(), jts, art, lim, ticks
-
-
-JOINT_CASES = {
-    "joints:one_body-ball": lambda: _j(*gj.one_body(jd.BALL)), "joints:one_body-hinge": lambda: _j(*gj.one_body(jd.HINGE)),
-    "joints:two_bodies-plain": lambda: _j(*gj.two_bodies(), ticks=2),
-    "joints:two_bodies-body1_is_world": lambda: _j(*gj.two_bodies(first_is_world_side=True), ticks=2),
-    "joints:two_bodies-kinematic": lambda: _j(*gj.two_bodies(kinematic=True), ticks=2),
-    "joints:chain_on_ground": lambda: _j(*gj.chain_on_ground()),
-    "joints:star-64": lambda: _j(*jd.star(64)), "joints:star-90": lambda: _j(*jd.star(90)),
-    "joints:star_on_ground-100": lambda: _j(*gj.star_on_ground(100)),
-    "joints:pendulum_pairs": lambda: _j(*gj.pendulum_pairs()),
-    "hinge_limot:one_body_per_mode": lambda: _l(*ghl.one_body_per_mode(False)),
-    "hinge_limot:one_body_per_mode-swapped": lambda: _l(*ghl.one_body_per_mode(True)),
-    "hinge_limot:star_on_ground-8": lambda: _l(*lm.hinge_star(8, seed=ghl.STAR_GROUND_SEEDS[8], contacts=True)),
-    "hinge_limot:doors": lambda: _l(*lm.doors(600, nfree=40, seed=ghl.DOORS_SEED)),
-    "hinge_limot:motor_door": _motor_door,
-    "slider:one_body_per_mode": lambda: _l(*sd.one_body_per_mode(False, gsl.MODE_SEED)),
-    "slider:one_body_per_mode-swapped": lambda: _l(*sd.one_body_per_mode(True, gsl.MODE_SEED)),
-    "slider:one_body_fixed": lambda: _l(*sd.one_body(None, False, gsl.MODE_SEED, kind=sd.FIXED), ticks=2),
-    "slider:one_body_fixed-swapped": lambda: _l(*sd.one_body(None, True, gsl.MODE_SEED, kind=sd.FIXED), ticks=2),
-    "slider:cart_pole": lambda: _l(*sd.cart_pole(), ticks=3),
-    "slider:all_kinds_chain": lambda: _l(*sd.all_kinds_chain(gsl.CHAIN_SEED)),
-    "slider:star_on_ground-8": lambda: _l(*sd.star(8, seed=gsl.STAR_GROUND_SEED, contacts=True)),
-    "slider:small_world": lambda: _l(*sd.small_world(gsl.WORLD_SEED)),
-}
-for _mode in ("motor_free", "low_stop_motor_into", "high_stop"):
-    JOINT_CASES[f"hinge_limot:two_bodies-{_mode}"] = lambda mode=_mode: _l(*lm.two_bodies(mode, kinematic=True), ticks=2)
-for _n in (8, 40, 100):
-    JOINT_CASES[f"hinge_limot:hinge_star-{_n}"] = lambda n=_n: _l(*lm.hinge_star(n, seed=ghl.STAR_SEEDS[n]))
-    JOINT_CASES[f"slider:star-{_n}"] = lambda n=_n: _l(*sd.star(n, seed=gsl.STAR_SEEDS[n]))
-for _kind, _mode in [(sd.SLIDER, "motor_free"), (sd.SLIDER, "low_stop_motor_into"), (sd.SLIDER, None), (sd.FIXED, None)]:
-    JOINT_CASES[f"slider:two_bodies-{_kind}-{_mode}"] = lambda k=_kind, m=_mode: _l(*sd.two_bodies(k, m, kinematic=True, seed=gsl.TWO_SEED), ticks=2)
-
-
-def _side_f32(bodies, s, anchor, axis):
-    """joint_dense.side with the body's rotation, R anchor and R axis evaluated in float32 (the quaternion, the anchor and the axis
-    are float32 numbers already): what a float32 batch can know of a_i = R_i anchor_i"""
-    f = np.float32
-    if s < 0:
-        return np.array(anchor, np.float64), np.zeros(3), np.array(axis, np.float64)
-    w, x, y, z = (bodies.quat[s].astype(f) / np.sqrt(np.sum(bodies.quat[s].astype(f) ** 2, dtype=f))).astype(f)
-    one, two = f(1), f(2)
-    R = np.array([[one - two * (y * y + z * z), two * (x * y - w * z), two * (x * z + w * y)],
-                  [two * (x * y + w * z), one - two * (x * x + z * z), two * (y * z - w * x)],
-                  [two * (x * z - w * y), two * (y * z + w * x), one - two * (x * x + y * y)]], f)
-    return bodies.pos[s], (R @ np.asarray(anchor, f)).astype(np.float64), (R @ np.asarray(axis, f)).astype(np.float64)
-
-
-def _joint_step(B, W, jts, art, lim, f32_sides):
-    """the reference's QuickStep tick of a float32 batch holding these inputs -> (Result, the world as the batch holds it)"""
-    B2, _, _ = qb.as_f32_inputs(B, W, jts)
-    Wr, jr, ar, lr = ghl.as_precision("float32", W, jts, art, lim)
-    side = jd.side
-    jd.side = _side_f32 if f32_sides else side
-    try:
-        return sd.step(B2, Wr, jr, ar, lr, "quick"), Wr
-    finally:
-        jd.side = side
+# Islands with joint rows (test_gpu_joints.py, test_gpu_hinge_limot.py, test_gpu_slider.py; test_gpu_small_tick.py holds no
+# articulation joint -- the joint files run the single-launch tick themselves).  Every float32 QuickStep case their `compare` sees is
+# in their F32_QUICK_CASES as () -> (Bodies, World, contact joints, joints, limots, ticks[, before(t, limots)]); a later tick starts
+# from the reference's last state.
+JOINT_FILES = {"joints": gj, "hinge_limot": ghl, "slider": gsl}
+JOINT_CASES = {f"{f}:{name}": case for f, mod in JOINT_FILES.items() for name, case in mod.F32_QUICK_CASES.items()}
+# the scenes a dropped sweep cannot pass (section 3 of each file); the others are the 36 the old model's figures were measured on
+CHAIN_CASES = [f"{f}:{name}" for f, mod in JOINT_FILES.items() for name in mod.CHAIN_CASES]
 
 
 @functools.lru_cache(maxsize=None)
-def _joint_population():
-    """-> per case (sweeps alone in float32, sweeps and the rows' R anchor / R axis in float32), largest deviation from the float64
-    reference over bodies and ticks in eps32 M_v"""
-    out = {}
-    for name, case in JOINT_CASES.items():
-        B, W, jts, art, lim, ticks, *before = case()
-        sweeps = rows = 0.0
-        for t in range(ticks):
-            if before:
-                before[0](t, lim)
-            r, Wr = _joint_step(B, W, jts, art, lim, False)
-            sweeps = max(sweeps, float(np.max(qb.emulation_deviation(r, Wr))))
-            r32, _ = _joint_step(B, W, jts, art, lim, True)
-            lv, av = B.lvel.copy(), B.avel.copy()
-            for I in r32.islands:
-                v = I.velocities(qb.emulate_f32(I, Wr.iters, Wr.sor_w).astype(np.float64)).reshape(-1, 6) if I.m else I.velocities(np.zeros(0)).reshape(-1, 6)
-                lv[I.slots], av[I.slots] = v[:, :3], v[:, 3:]
-            kin = (B.flags & ld.KINEMATIC) != 0
-            lv[kin], av[kin] = r.bodies.lvel[kin], r.bodies.avel[kin]
-            rows = max(rows, float(np.max(qb.deviation(r, lv, av))))
-            B = r.bodies
-        out[name] = (sweeps, rows)
+def _joint_case(name):
+    """-> per tick of the case, largest over bodies: (float32 sweeps alone, old model; float32 sweeps and R anchor / R axis, old
+    model; everything a float32 batch computes for a row in float32, the model with the joint term; the new band at K["joint"] over
+    the old allowance 10 eps32 kappa x scale, both as the largest velocity error allowed over live bodies)"""
+    B, W, jts, art, lim, ticks, *before = JOINT_CASES[name]()
+    out = []
+    for t in range(ticks):
+        if before:
+            before[0](t, lim)
+        r, inp = qb.joint_reference(B, W, jts, art, lim)
+        dev = []
+        for rows, term in ((False, False), ("sides", False), (True, True)):
+            if name in CHAIN_CASES and not term:             # (the old model's record is about the 36 older cases)
+                dev.append(np.nan)
+                continue
+            lv, av = qb.joint_emulation(r, inp, rows)
+            dev.append(float(np.max(qb.deviation(r, lv, av, term))))
+        live = np.nonzero(inp[0].flags & ld.ALIVE)[0]
+        old = qb.old_allowance(r, inp[1], live)             # (None: the old rule does not admit the tick)
+        ratio = np.nan if old is None else float(np.max(qb.velocity_band(r, inp[1], qb.K["joint"])[live])) / old
+        out.append((*dev, ratio))
+        B = r.bodies
     return out
 
 
+def _joint_population():
+    """-> per case the largest of each figure over its ticks (nan where a tick has none)"""
+    return {name: tuple(float(np.max([tick[k] for tick in _joint_case(name)])) for k in range(4)) for name in JOINT_CASES}
+
+
 def test_joint_rows_need_a_term_the_model_lacks():
-    """Two float32 emulations of every float32 QuickStep case of the three joint files, both from the float64 reference of the same
-    float32 inputs.  The sweeps alone (A, b, lo, hi cast to float32) stay where contact rows do: quick_band.JOINT_MEASURED["sweeps"].
-    With the rows' a_i = R_i anchor_i and R_i axis_i evaluated in float32 as well -- nothing else changed -- the deviation reaches
-    JOINT_MEASURED["rows"]: above K_MAX / 2 = 32, so by the K rule the family would need K = 128.  A joint row's right-hand side is
-    ERP / h times a position error, and (ERP / h) eps32 |a| of it is rounding of R anchor whatever lambda is: a term M_v lacks.
-    That is why those files keep 10 eps32 kappa(A) (the issue's rule for a family whose emulation cannot be kept under 32).  The
-    device, run once with the band applied at K = 8, left it by up to 35.4 on the same case this emulation puts at the top; the
-    bodies of the stars are not rotated, their R is exact, and both emulations agree on them."""
-    pop = _joint_population()
+    """The record of why the joint term exists, on the 36 cases the model was first tried on, with the model WITHOUT the term.  The
+    float32 sweeps alone (A, b, lo, hi cast to float32) stay where contact rows do: quick_band.JOINT_MEASURED["sweeps"].  With the
+    rows' a_i = R_i anchor_i and R_i axis_i evaluated in float32 as well -- nothing else changed -- the deviation reaches
+    JOINT_MEASURED["rows"]: above K_MAX / 2 = 32, so by the K rule the family would need K = 128.  The bodies of the stars are
+    not rotated, their R is exact, and both emulations agree on them."""
+    pop = {k: v for k, v in _joint_population().items() if k not in CHAIN_CASES}
+    assert len(pop) == 36
     sweeps = max(pop, key=lambda k: pop[k][0])
     rows = max(pop, key=lambda k: pop[k][1])
-    print(f"joint rows, float32 sweeps on {len(pop)} cases: largest deviation {pop[sweeps][0]:.2f} eps32 M_v on {sweeps} "
+    print(f"joint rows, old model, float32 sweeps on {len(pop)} cases: largest deviation {pop[sweeps][0]:.2f} eps32 M_v on {sweeps} "
           f"(table {qb.JOINT_MEASURED['sweeps']})")
-    print(f"joint rows, float32 sweeps and float32 R anchor / R axis: largest deviation {pop[rows][1]:.2f} eps32 M_v on {rows} "
+    print(f"joint rows, old model, float32 sweeps and float32 R anchor / R axis: largest deviation {pop[rows][1]:.2f} eps32 M_v on {rows} "
           f"(table {qb.JOINT_MEASURED['rows']}); above 8: " + ", ".join(f"{k} {v[1]:.1f}" for k, v in pop.items() if v[1] > 8))
     assert _matches(pop[sweeps][0], qb.JOINT_MEASURED["sweeps"]) and pop[sweeps][0] <= qb.K["contact"] / 2
     assert _matches(pop[rows][1], qb.JOINT_MEASURED["rows"])
-    assert pop[rows][1] > qb.K_MAX / 2 and qb.k_rule(pop[rows][1]) > qb.K_MAX, "the joint family fits the model after all: move it onto the band"
+    assert pop[rows][1] > qb.K_MAX / 2 and qb.k_rule(pop[rows][1]) > qb.K_MAX
     assert rows == "hinge_limot:doors"
     for name in ("joints:star-64", "joints:star-90", "hinge_limot:hinge_star-100", "slider:star-100"):
         assert pop[name][0] == pop[name][1], name              # identity rotations: R anchor is exact in float32
+
+
+def test_joint_family_population():
+    """population (b) of the joint family, with the joint term in the model: everything a float32 batch computes for a joint row done
+    in float32 (quick_band.float32_rows, round_rows), then the float32 sweeps, over every float32 QuickStep case the joint files
+    hold to the band, every tick, the chains of their section 3 included.  (The oracle has no joints: no population (a).)"""
+    pop = _joint_population()
+    worst = max(pop, key=lambda k: pop[k][2])
+    print(f"joint rows, population (b), float32 rows and sweeps on {len(pop)} cases: largest deviation {pop[worst][2]:.2f} eps32 M_v on "
+          f"{worst} (table {qb.MEASURED['joint']['emulation']}, K = {qb.K['joint']}); above 2: " +
+          ", ".join(f"{k} {v[2]:.2f}" for k, v in pop.items() if v[2] > 2))
+    assert pop[worst][2] <= qb.K["joint"] / 2
+    assert _matches(pop[worst][2], qb.MEASURED["joint"]["emulation"])
+
+
+BAND_WIDER = 29          # of the 36 (re-measured below)
+
+
+def test_no_joint_case_is_held_to_less_than_before():
+    """Per float32 QuickStep case the joint files had before the band: the band at K["joint"] over the old allowance
+    10 eps32 kappa(A) x max(|v_ref|, g h), both as the largest velocity error allowed over live bodies.  The band is the wider one
+    on most of them -- kappa ~ 1 .. 10 allowed 10 .. 100 eps32 of the velocity scale, less than the (ERP / h) eps32 |a| the rows'
+    inputs can carry -- so the GPU files assert the old allowance too wherever the old rule admits the tick
+    (quick_band.assert_in_old_allowance).  It admits every tick of every one of these cases: none is held to less than before"""
+    pop = {k: v[3] for k, v in _joint_population().items() if k not in CHAIN_CASES}
+    for k in sorted(pop, key=pop.get):
+        print(f"{k}: band / old allowance {pop[k]:.3g}")
+    assert all(np.isfinite(v) for v in pop.values()), [k for k, v in pop.items() if not np.isfinite(v)]
+    assert sum(v > 1.0 for v in pop.values()) == BAND_WIDER
+    chains = {k: v[3] for k, v in _joint_population().items() if k in CHAIN_CASES}
+    print("chains the old rule admits: " + (", ".join(f"{k} (band / old allowance {v:.3g})" for k, v in chains.items() if np.isfinite(v)) or "none"))
+
+
+# ---- the band can tell, on islands with joint rows
+JOINT_CHANGES = ["19 sweeps", "sor_w 1.25", "ERP x 1.01", "CFM ignored"]
+
+
+@functools.lru_cache(maxsize=None)
+def _joint_changed(name):
+    """-> per change, the largest |v_changed - v_ref| over the unchanged reference's band at K["joint"], over bodies (first tick)"""
+    B, W, jts, art, lim, ticks, *before = JOINT_CASES[name]()
+    if before:
+        before[0](0, lim)
+    r, (B2, W2, j2, a2, l2) = qb.joint_reference(B, W, jts, art, lim)
+    band = qb.velocity_band(r, W2, qb.K["joint"])
+    out = {}
+    for change in JOINT_CHANGES:
+        Wc = ld.World(h=W2.h, gravity=W2.gravity, erp=W2.erp, cfm=W2.cfm, iters=W2.iters, sor_w=W2.sor_w, gyro=W2.gyro)
+        if change == "19 sweeps":
+            Wc.iters = W2.iters - 1
+        elif change == "sor_w 1.25":
+            Wc.sor_w = 1.25
+        elif change == "ERP x 1.01":
+            Wc.erp = 1.01 * W2.erp
+        else:
+            Wc.cfm = 0.0
+        rc = sd.step(B2, Wc, j2, a2, l2, "quick")
+        dv = np.maximum(np.max(np.abs(rc.bodies.lvel - r.bodies.lvel), axis=1), np.max(np.abs(rc.bodies.avel - r.bodies.avel), axis=1))
+        nz = band > 0
+        out[change] = float(np.max(dv[nz] / band[nz]))
+    return out
+
+
+@pytest.mark.parametrize("name", CHAIN_CASES)
+def test_the_band_can_tell_on_joint_chains(name):
+    """every chain of the joint files' section 3: the reference with 19 sweeps, sor_w 1.25, ERP x 1.01 and the world's CFM ignored
+    each leaves the unchanged reference's band by 10 x or more"""
+    out = _joint_changed(name)
+    print(f"{name}: " + ", ".join(f"{c} {v:.3g} x" for c, v in out.items()))
+    for change, v in out.items():
+        assert v >= 10.0, change
+
+
+def test_every_family_and_every_form_has_a_case_that_tells_a_dropped_sweep():
+    """the joint files name, per device form (FORM_CASES: the lane-per-island form, the single-launch tick, the one-wavefront form, the
+    256- and 512-thread register forms, the streamed form), the chains that run on it; one per form and one per file must tell"""
+    tells = lambda name: _joint_changed(name)["19 sweeps"] >= 10.0
+    forms = {}
+    for f, mod in JOINT_FILES.items():
+        assert any(tells(f"{f}:{name}") for name in mod.CHAIN_CASES), f
+        for form, names in mod.FORM_CASES.items():
+            forms.setdefault(form, []).extend(f"{f}:{name}" for name in names)
+    assert sorted(forms) == sorted(["lane per island", "single-launch tick", "one wavefront", "registers, 256 threads",
+                                    "registers, 512 threads", "streamed"])
+    for form, names in forms.items():
+        assert any(tells(name) for name in names), form
+
+
+def test_most_old_joint_cases_cannot_tell_a_dropped_sweep():
+    """why the chains were needed: of the 36 cases the joint files had, the reference with 19 sweeps leaves the band at K["joint"] on
+    a handful only -- the others have converged long before the 19th sweep"""
+    told = sorted(k for k in JOINT_CASES if k not in CHAIN_CASES and _joint_changed(k)["19 sweeps"] >= 1.0)
+    print(f"19 sweeps leaves the band on {len(told)} of 36: {', '.join(told)}")
+    assert len(told) <= 8
+
+
