@@ -311,7 +311,10 @@ extern "C" int dmxBatchUpload(dmxBatchID b, int field, const void *host, int64_t
 extern "C" int dmxBatchDownload(dmxBatchID b, int field, void *host, int64_t first, int64_t count)
 {
     if (!range_ok(b, field, host, first, count)) return DMX_EINVAL;
-    SETTLE(b);
+    // A read-out: what it returns must be a verified state, so the open chunk is closed (a rollback found there breaks the
+    // fixed-axis chain itself), but reading the slab changes nothing the tiles' words depend on -- the chain stands, and the
+    // launch behind a download may be a lean one (dmx_fixed.hpp; the reference's loop reads poses between ticks)
+    { const int rc_close = dmx_close_chunk(b); if (rc_close != DMX_OK) return rc_close; }
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
     if (b->sm_mirror_valid && !b->slab_exposed && k_field_comp0[field] + k_field_k[field] <= C_MASS) {

@@ -14,7 +14,8 @@
 // active slab, with no skip mask and no gate.  It is LEAN if, besides, the launch before it onto these slots was an establishing
 // or lean one with the same key (h and g in the kernel's precision, mass source and value, gyro mode, n_active, elision mask),
 // nothing has happened in between, and it runs in place with no safe-zone check and no boundary pack (those read pos.x / pos.z).
-// Doors that break the chain (brk): every entry point of the C ABI other than the stepping calls themselves (dmx_settle), every
+// Doors that break the chain (brk): every entry point of the C ABI other than the stepping calls themselves and dmxBatchDownload,
+// which only reads the slab and closes the open chunk without touching the record (dmx_settle does both for the others), every
 // writer of state (dmx_state_written), snapshot restore and rollback, the exact tick, the joints tick, and any launch that is
 // not establish or lean.  Two events end it for good (end): a device pointer into the slab, and a stepping call made while the
 // stream is being captured -- replays of a graph run behind the library's back.

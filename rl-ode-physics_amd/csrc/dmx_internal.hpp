@@ -41,6 +41,34 @@ __host__ __device__ __forceinline__ int64_t slab_ix(int c, int64_t i)
     return (i >> SLAB_TILE_LOG2) * (int64_t)(C_COUNT * SLAB_TILE) + (int64_t)c * SLAB_TILE + (i & (SLAB_TILE - 1));
 }
 
+// How integrate_free's state stores leave the compute unit: a vector store with a cache-policy bit, chosen at build time.
+//   STORE_PLAIN   global_store_dword[x2]
+//   STORE_WT      ... sc1: written through to the fabric; the XCD's L2 drops the line (__hip_atomic_store, relaxed, agent scope)
+//   STORE_NT      ... nt: non-temporal; the line stays in the XCD's L2 for the next launch's reads
+// scripts/ubench_store_policy.hip measured the four forms on the lean launch's pattern (profiles/ubench_store_policy.txt): nt is
+// the fastest at every shape and keeps the alternating sweep's re-reads in L2; sc1 loses them in f32.  The values are the bits
+// given: no form converts.  -DDMX_STORE_POLICY=n builds the other forms for an A/B; there is no switch at run time.
+enum : int { STORE_PLAIN = 0, STORE_WT = 1, STORE_NT = 2 };
+#ifndef DMX_STORE_POLICY
+#define DMX_STORE_POLICY 2
+#endif
+constexpr int kStorePolicy = DMX_STORE_POLICY;
+static_assert(kStorePolicy >= STORE_PLAIN && kStorePolicy <= STORE_NT, "DMX_STORE_POLICY is 0 (plain), 1 (write-through) or 2 (non-temporal)");
+#if defined(__HIPCC__)
+__device__ __forceinline__ void store_state(float *p, float v)
+{
+    if constexpr (kStorePolicy == STORE_WT) __hip_atomic_store((uint32_t *)p, __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (kStorePolicy == STORE_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+__device__ __forceinline__ void store_state(double *p, double v)
+{
+    if constexpr (kStorePolicy == STORE_WT) __hip_atomic_store((uint64_t *)p, __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (kStorePolicy == STORE_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+#endif
+
 // GEOM_CONVEX: the batch's one convex hull (StepParams::hull); its bounding radius sits in sides[0] like a sphere's
 enum : int { GEOM_NONE = 0, GEOM_SPHERE = 1, GEOM_BOX = 2, GEOM_CONVEX = 3 };
 // can a geom of class a ever produce a contact with one of class b?  Every pair of classes has a collider since round 3 (box /

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
                     if (ax >= 0 && changed) moved |= 1u << ax;
                     if (in_place && !changed) continue;
                 }
-                So[slab_ix(k, i)] = c[k];
+                store_state(&So[slab_ix(k, i)], c[k]);
             }
             // what this launch observed: an establishing launch writes every tile's word, a lean one only a word that changes
             // (an axis it did not load keeps its bit: same inputs, same bits)
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
             if constexpr (ELIDE) if (in_place) {
                 if (__ballot(bits_differ(c[k], was[k])) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
             }
-            So[slab_ix(k, i)] = c[k];
+            store_state(&So[slab_ix(k, i)], c[k]);       // (dmx_internal.hpp: the state leaves with the store policy's cache bit)
         }
         }
         if (EXT) {
