@@ -535,12 +535,50 @@ int dmxBatchFeedbackDevice(dmxBatchID b, const void **joints_dev, const void **c
  * slots that are not alive.
  * Refused by the ticks that find their own contacts -- dmxBatchStep, dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick,
  * dmxBatchChunkTicks, dmxBatchExactTick: their fused kernels never read the flags while the islands they build do, so while
- * any slot of [0, active count) has a byte other than DMX_BODY_ALIVE they return DMX_EINVAL, say so in one line on stderr
+ * any slot of [0, active count) has a byte other than DMX_BODY_ALIVE -- DMX_BODY_AUTODISABLE and DMX_BODY_DISABLED included,
+ * these ticks know no auto-disable -- they return DMX_EINVAL, say so in one line on stderr
  * and leave the state untouched (ghost slots do not count).  Nothing is silently ignored.
  * dmxBatchFindPairs does not read the flags: a dead slot still takes part in the pair search unless its class is
  * DMX_GEOM_NONE (dmxBatchUploadGeomType), which is how the ODE face retires a destroyed body. */
-enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8 };
+enum { DMX_BODY_ALIVE = 1, DMX_BODY_KINEMATIC = 2, DMX_BODY_NOGRAVITY = 4, DMX_BODY_NOGYRO = 8,
+       DMX_BODY_AUTODISABLE = 16, DMX_BODY_DISABLED = 32 };
 int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64_t first, int64_t count);
+
+/* ---- auto-disable: resting bodies sleep, islands wake on contact (dmxBatchStepJoints only; off by default, as in ODE)
+ * A slot is ASLEEP when its byte has DMX_BODY_ALIVE and DMX_BODY_DISABLED; DMX_BODY_AUTODISABLE lets a body fall asleep by itself.
+ * Parameters of the batch: linear and angular speed thresholds (m/s, rad/s, >= 0), idle_steps (>= 0) and idle_time (seconds,
+ * >= 0); anything else is DMX_EINVAL.  Defaults are ODE's [ODE-recall]: 0.01, 0.01, 10, 0.  Per slot the batch keeps steps_left
+ * (int32) and time_left (a double in both precisions: a run of subtractions of h must not end on another tick in float32).  A
+ * slot's counters are put back to (idle_steps, idle_time) when the batch is created, when dmxBatchSetAutoDisable is called (every
+ * slot), and when dmxBatchUploadBodyFlags takes its DISABLED bit from set to clear or its AUTODISABLE bit from clear to set; an
+ * upload that leaves both bits as they were leaves the counters alone.
+ * Start of a dmxBatchStepJoints tick: islands are formed as always (the active articulation joints and the tick's contact joints
+ * between two live slots).  An island is awake if it holds a live slot without DISABLED (a kinematic body counts like any
+ * other).  In an awake island every member's DISABLED bit is cleared -- the counters are not touched [ODE-recall
+ * dxProcessIslands] -- and the island is stepped as always.  An island without an awake member is left out: its bodies' state,
+ * force and torque accumulators and counters keep their bits, no gravity is applied, its joints make no rows, their feedback is
+ * zeros (as for dropped joints) and its contact joints do not count in dmxBatchLastContactCount.  A lone asleep body is such an
+ * island.
+ * End of the tick, for every slot the tick stepped that has ALIVE | AUTODISABLE and not KINEMATIC, on the post-step velocities in
+ * the batch's precision:
+ *     idle = (lvel.lvel <= lin_threshold^2) && (avel.avel <= ang_threshold^2)
+ *     if idle:  steps_left = max(steps_left - 1, 0);  time_left = max(time_left - h, 0)
+ *     else:     steps_left = idle_steps;              time_left = idle_time
+ *     if steps_left == 0 && time_left == 0:  set DISABLED;  lvel = avel = 0
+ * ODE evaluates the rule at the start of the next step; the two differ only if the host edits velocities between ticks.  ODE's
+ * averaged samples and per-body thresholds are not offered.  Kinematic bodies never fall asleep.  Nothing but the island rule
+ * and a flag upload wakes a body: uploading a pose or a force does not [ODE-recall: dBodySetPosition, dBodyAddForce].
+ * Ray casts go on seeing asleep bodies; the single-launch tick's limit of 512 live bodies counts them too.
+ * dmxBatchDownloadBodyFlags returns the flag bytes as they stand after every tick enqueued so far (it waits for the last tick
+ * that stepped an AUTODISABLE body; so does the next tick's start, which needs the bits to build its islands).
+ * dmxBatchIdleCounters: one entry per slot; either pointer may be NULL.
+ * dmxBatchAutoDisableStats: [0] slots asleep now, [1] islands left out of the last tick, [2] bodies put to sleep by the rule
+ * since creation, [3] bodies woken by the island rule since creation. */
+int dmxBatchSetAutoDisable(dmxBatchID b, double lin_threshold, double ang_threshold, int idle_steps, double idle_time);
+int dmxBatchGetAutoDisable(dmxBatchID b, double *lin_threshold, double *ang_threshold, int *idle_steps, double *idle_time);
+int dmxBatchDownloadBodyFlags(dmxBatchID b, uint8_t *flags_out, int64_t first, int64_t count);
+int dmxBatchIdleCounters(dmxBatchID b, int32_t *steps_left, double *time_left);
+int dmxBatchAutoDisableStats(dmxBatchID b, int64_t out[4]);
 
 /* ---- diagnostics of the last step */
 int dmxBatchLastContactCount(dmxBatchID b, int64_t *n);       /* contact joints created in the last tick */

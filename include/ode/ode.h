@@ -106,6 +106,26 @@ void dWorldSetQuickStepNumIterations(dWorldID, int num);
 int  dWorldGetQuickStepNumIterations(dWorldID);
 void dWorldSetQuickStepW(dWorldID, dReal over_relaxation);
 dReal dWorldGetQuickStepW(dWorldID);
+/* Auto-disable: a body whose speeds have stayed under the thresholds for the idle steps and the idle time is put to sleep; an
+ * island without an awake body is not stepped; a sleeping body wakes when something awake becomes connected to it (the rule is
+ * in include/dmx_batch.h, "auto-disable").  Off by default, as in ODE; defaults 0.01, 0.01, 10 steps, 0 s [ODE-recall].
+ * Departures from ODE: the four values are the world's and hold for ALL its bodies from the next step on (ODE copies them into a
+ * body at creation), and setting one resets every body's idle counters; there are no per-body thresholds; the idle test looks at
+ * the step's own velocities (an average samples count other than 1 is refused with one line on stderr); the test runs at the end
+ * of the step, not at the start of the next.  dBodySetPosition, dBodyAddForce and the like do not wake a body [ODE-recall];
+ * dBodyEnable does.  dSpaceCollide hands pairs of disabled bodies to the callback like any other [ODE-recall]. */
+void dWorldSetAutoDisableFlag(dWorldID, int do_auto_disable);     /* what dBodyCreate copies into a new body */
+int  dWorldGetAutoDisableFlag(dWorldID);
+void dWorldSetAutoDisableLinearThreshold(dWorldID, dReal linear_threshold);
+dReal dWorldGetAutoDisableLinearThreshold(dWorldID);
+void dWorldSetAutoDisableAngularThreshold(dWorldID, dReal angular_threshold);
+dReal dWorldGetAutoDisableAngularThreshold(dWorldID);
+void dWorldSetAutoDisableSteps(dWorldID, int steps);
+int  dWorldGetAutoDisableSteps(dWorldID);
+void dWorldSetAutoDisableTime(dWorldID, dReal time);
+dReal dWorldGetAutoDisableTime(dWorldID);
+void dWorldSetAutoDisableAverageSamplesCount(dWorldID, unsigned int average_samples_count);   /* 1 only */
+int  dWorldGetAutoDisableAverageSamplesCount(dWorldID);
 int  dWorldStep(dWorldID, dReal stepsize);                       /* main.c:213 */
 int  dWorldQuickStep(dWorldID, dReal stepsize);
 
@@ -125,6 +145,12 @@ const dReal *dBodyGetAngularVel(dBodyID);
 void dBodySetKinematic(dBodyID);                                 /* main.c:712 */
 void dBodySetDynamic(dBodyID);
 int  dBodyIsKinematic(dBodyID);
+void dBodySetAutoDisableFlag(dBodyID, int do_auto_disable);      /* 0 also enables the body [ODE-recall] */
+int  dBodyGetAutoDisableFlag(dBodyID);
+void dBodySetAutoDisableDefaults(dBodyID);                       /* the world's flag */
+void dBodyEnable(dBodyID);                                       /* wakes the body and resets its idle counters */
+void dBodyDisable(dBodyID);                                      /* asleep from the next step on, velocities as they are */
+int  dBodyIsEnabled(dBodyID);
 void dBodyAddForce(dBodyID, dReal fx, dReal fy, dReal fz);       /* main.c:532 (commented out there) */
 void dBodyAddTorque(dBodyID, dReal fx, dReal fy, dReal fz);
 void dBodySetMass(dBodyID, const dMass *mass);

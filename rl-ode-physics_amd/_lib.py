@@ -29,6 +29,7 @@ BATCH_SYMBOLS = [
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
     "dmxBatchSetFeedback", "dmxBatchJointFeedback", "dmxBatchContactFeedback", "dmxBatchFeedbackDevice",
+    "dmxBatchSetAutoDisable", "dmxBatchGetAutoDisable", "dmxBatchDownloadBodyFlags", "dmxBatchIdleCounters", "dmxBatchAutoDisableStats",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -150,5 +151,10 @@ def load():
     sig("dmxBatchJointFeedback", I, P, P)
     sig("dmxBatchContactFeedback", I, P, L, P)
     sig("dmxBatchFeedbackDevice", I, P, C.POINTER(P), C.POINTER(P))
+    sig("dmxBatchSetAutoDisable", I, P, D, D, I, D)
+    sig("dmxBatchGetAutoDisable", I, P, C.POINTER(D), C.POINTER(D), C.POINTER(I), C.POINTER(D))
+    sig("dmxBatchDownloadBodyFlags", I, P, P, L, L)
+    sig("dmxBatchIdleCounters", I, P, P, P)
+    sig("dmxBatchAutoDisableStats", I, P, P)
     _lib = lib
     return lib

@@ -22,6 +22,8 @@ EXACT_AUTO, EXACT_STAGED, EXACT_ONE_WORKGROUP = 0, 1, 2
 STEPPER_QUICK, STEPPER_EXACT = 0, 1
 ORDER_CREATION, ORDER_ODE = 0, 1
 BODY_ALIVE, BODY_KINEMATIC, BODY_NOGRAVITY, BODY_NOGYRO = 1, 2, 4, 8
+BODY_AUTODISABLE, BODY_DISABLED = 16, 32      # auto-disable: may fall asleep by itself / is asleep
+AUTO_DISABLE_STATS = ("asleep", "islands_skipped", "slept", "woken")
 CONTACT_SOFT_ERP, CONTACT_SOFT_CFM = 0x008, 0x010
 CONTACT_APPROX1_1, CONTACT_APPROX1_2, CONTACT_APPROX1 = 0x1000, 0x2000, 0x3000      # friction bounded by mu times the normal force
 # dmxContactJoint (include/dmx_batch.h): the C layout, padding included (tests/test_solver_dense.py checks it with offsetof)
@@ -332,6 +334,38 @@ class BatchWorld:
         BODY_ALIVE (include/dmx_batch.h)"""
         f = np.ascontiguousarray(flags, dtype=np.uint8)
         _check(self.lib.dmxBatchUploadBodyFlags(self.h, f.ctypes.data, first, f.shape[0]), "dmxBatchUploadBodyFlags")
+
+    # -- auto-disable: resting bodies sleep, islands wake on contact (include/dmx_batch.h, "auto-disable") --
+    def set_auto_disable(self, lin_threshold=0.01, ang_threshold=0.01, idle_steps=10, idle_time=0.0):
+        """the batch's thresholds (m/s, rad/s) and idle counters for bodies that carry BODY_AUTODISABLE; resets every slot's
+        counters.  step_joints only"""
+        _check(self.lib.dmxBatchSetAutoDisable(self.h, float(lin_threshold), float(ang_threshold), int(idle_steps), float(idle_time)),
+               "dmxBatchSetAutoDisable")
+
+    def auto_disable(self):
+        """-> (lin_threshold, ang_threshold, idle_steps, idle_time)"""
+        a, b, t, s = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        _check(self.lib.dmxBatchGetAutoDisable(self.h, C.byref(a), C.byref(b), C.byref(s), C.byref(t)), "dmxBatchGetAutoDisable")
+        return a.value, b.value, s.value, t.value
+
+    def body_flags(self):
+        """-> [n] uint8: the flag bytes as they stand after every tick enqueued so far (BODY_DISABLED: asleep)"""
+        out = np.zeros(self.n, np.uint8)
+        _check(self.lib.dmxBatchDownloadBodyFlags(self.h, out.ctypes.data, 0, self.n), "dmxBatchDownloadBodyFlags")
+        return out
+
+    def idle_counters(self):
+        """-> (steps_left [n] int32, time_left [n] float64)"""
+        st, tl = np.zeros(self.n, np.int32), np.zeros(self.n, np.float64)
+        _check(self.lib.dmxBatchIdleCounters(self.h, st.ctypes.data, tl.ctypes.data), "dmxBatchIdleCounters")
+        return st, tl
+
+    def auto_disable_stats(self):
+        """asleep: slots asleep now; islands_skipped: in the last tick; slept / woken: bodies put to sleep by the rule / woken by
+        the island rule since creation"""
+        out = (C.c_int64 * 4)()
+        _check(self.lib.dmxBatchAutoDisableStats(self.h, out), "dmxBatchAutoDisableStats")
+        return dict(zip(AUTO_DISABLE_STATS, out))
 
     def set_row_order(self, order, seed=0):
         """ORDER_CREATION (default) / ORDER_ODE: the order QuickStep sweeps an island's rows in"""

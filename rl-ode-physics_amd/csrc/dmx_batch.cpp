@@ -171,12 +171,22 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
                     (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], (long long)s[5], (long long)s[6],
                     (long long)s[7], (long long)s[8]);
     }
+    {
+        static const bool report = [] { const char *e = getenv("DMX_AUTODISABLE_REPORT"); return e && atoi(e) != 0; }();
+        if (report)
+            fprintf(stderr, "libode_mi355 auto-disable: asleep=%lld slept=%lld woken=%lld flag_reads=%lld\n", (long long)b->ad_n_disabled,
+                    (long long)b->ad_slept, (long long)b->ad_woken, (long long)b->ad_flag_reads);
+    }
     for (int p = 0; p < 2; p++) {
         if (b->sm_stage[p]) (void)hipHostFree(b->sm_stage[p]);
         if (b->sm_ev[p]) (void)hipEventDestroy(b->sm_ev[p]);
     }
     if (b->sm_mirror) (void)hipHostFree(b->sm_mirror);
     if (b->sm_diag) (void)hipFree(b->sm_diag);
+    if (b->ad_steps_dev) (void)hipFree(b->ad_steps_dev);
+    if (b->ad_time_dev) (void)hipFree(b->ad_time_dev);
+    if (b->ad_mirror) (void)hipHostFree(b->ad_mirror);
+    if (b->ad_ev) (void)hipEventDestroy(b->ad_ev);
     dmx::lcp_grid_free(b);
     if (b->slab) (void)hipFree(b->slab);
     if (b->slab_alt) (void)hipFree(b->slab_alt);
@@ -363,14 +373,137 @@ extern "C" int dmxBatchUploadBodyFlags(dmxBatchID b, const uint8_t *flags, int64
     SETTLE(b);
     if (count == 0) return DMX_OK;
     HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_ad_merge(b); if (rc != DMX_OK) return rc; }      // (what is replaced below must be the bytes as the last tick left them)
+    // auto-disable: a slot whose DISABLED bit goes from set to clear, or whose AUTODISABLE bit goes from clear to set, starts its
+    // idle counters afresh; an upload that leaves both bits as they were leaves the counters alone
+    int64_t reset_lo = -1, reset_hi = -1;
+    std::vector<uint8_t> reset_slots;
+    bool ad_bits = false;
     for (int64_t i = 0; i < count; i++) {
         uint8_t &f = b->h_bflags[(size_t)(first + i)];
-        if (first + i < b->n_active) b->n_flagged += (int64_t)(flags[i] != BF_ALIVE) - (int64_t)(f != BF_ALIVE);
-        f = flags[i];
+        const uint8_t g = flags[i];
+        if (first + i < b->n_active) b->n_flagged += (int64_t)(g != BF_ALIVE) - (int64_t)(f != BF_ALIVE);
+        if ((f ^ g) & (BF_AUTODISABLE | BF_DISABLED | BF_ALIVE)) {
+            const bool reset = ((f & BF_DISABLED) && !(g & BF_DISABLED)) || (!(f & BF_AUTODISABLE) && (g & BF_AUTODISABLE));
+            if (reset) {
+                if (reset_lo < 0) { reset_lo = first + i; reset_slots.assign((size_t)count, 0); }
+                reset_hi = first + i; reset_slots[(size_t)i] = 1;
+            }
+            b->ad_n_auto += (int64_t)((g & BF_AUTODISABLE) != 0) - (int64_t)((f & BF_AUTODISABLE) != 0);
+            const uint8_t asleep = BF_ALIVE | BF_DISABLED;
+            b->ad_n_disabled += (int64_t)((g & asleep) == asleep) - (int64_t)((f & asleep) == asleep);
+        }
+        if (g & (BF_AUTODISABLE | BF_DISABLED)) ad_bits = true;
+        f = g;
     }
     b->state_version++;         // what rays can see has changed
+    if (ad_bits && !b->ad_steps_dev) { const int rc = dmx_ad_ensure(b); if (rc != DMX_OK) return rc; }
+    if (reset_lo >= 0 && b->ad_steps_dev) {
+        // the counters of [reset_lo, reset_hi]: read, the slots named above put back to the batch's values, written
+        const size_t m = (size_t)(reset_hi - reset_lo + 1);
+        std::vector<int32_t> st(m); std::vector<double> tl(m);
+        HIP_TRY(hipMemcpyAsync(st.data(), b->ad_steps_dev + reset_lo, m * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(tl.data(), b->ad_time_dev + reset_lo, m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        for (size_t k = 0; k < m; k++)
+            if (reset_slots[(size_t)(reset_lo - first) + k]) { st[k] = b->ad_steps; tl[k] = b->ad_time; }
+        HIP_TRY(hipMemcpyAsync(b->ad_steps_dev + reset_lo, st.data(), m * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->ad_time_dev + reset_lo, tl.data(), m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(b->bflags + first, b->h_bflags.data() + first, (size_t)count, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    return DMX_OK;
+}
+
+// ---- auto-disable (include/dmx_batch.h) ----------------------------------------------------------------------------------
+static int ad_fill_counters(dmxBatch *b)
+{
+    std::vector<int32_t> st((size_t)b->stride, b->ad_steps); std::vector<double> tl((size_t)b->stride, b->ad_time);
+    HIP_TRY(hipMemcpyAsync(b->ad_steps_dev, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->ad_time_dev, tl.data(), tl.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return DMX_OK;
+}
+
+int dmx_ad_ensure(dmxBatch *b)
+{
+    if (b->ad_steps_dev) return DMX_OK;
+    HIP_TRY(hipMalloc((void **)&b->ad_steps_dev, (size_t)b->stride * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->ad_time_dev, (size_t)b->stride * sizeof(double)));
+    HIP_TRY(hipHostMalloc((void **)&b->ad_mirror, (size_t)b->stride, hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void **)&b->ad_mirror_dev, b->ad_mirror, 0));
+    HIP_TRY(hipEventCreateWithFlags(&b->ad_ev, hipEventDisableTiming));
+    return ad_fill_counters(b);
+}
+
+int dmx_ad_merge(dmxBatch *b)
+{
+    if (!b->ad_pending) return DMX_OK;
+    HIP_TRY(hipEventSynchronize(b->ad_wait_ev));
+    b->ad_pending = false;
+    for (int64_t s = 0; s < b->n; s++) {
+        const uint8_t m = b->ad_mirror[s] & 0x7f;          // (bit 7: the single-launch tick's mark of a slot it left out, dmx_small.hpp)
+        uint8_t &f = b->h_bflags[(size_t)s];
+        if (m == f) continue;
+        if ((m & BF_DISABLED) && !(f & BF_DISABLED)) { b->ad_slept++; if (f & BF_ALIVE) b->ad_n_disabled++; }
+        f = m;
+    }
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetAutoDisable(dmxBatchID b, double lin_threshold, double ang_threshold, int idle_steps, double idle_time)
+{
+    if (!b || !(lin_threshold >= 0) || !(ang_threshold >= 0) || idle_steps < 0 || !(idle_time >= 0) || !std::isfinite(idle_time)) return DMX_EINVAL;
+    SETTLE(b);
+    HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_ad_merge(b); if (rc != DMX_OK) return rc; }
+    b->ad_lin = lin_threshold; b->ad_ang = ang_threshold; b->ad_steps = idle_steps; b->ad_time = idle_time;
+    return b->ad_steps_dev ? ad_fill_counters(b) : DMX_OK;       // (not yet made: they are made holding these values)
+}
+
+extern "C" int dmxBatchGetAutoDisable(dmxBatchID b, double *lin_threshold, double *ang_threshold, int *idle_steps, double *idle_time)
+{
+    if (!b) return DMX_EINVAL;
+    if (lin_threshold) *lin_threshold = b->ad_lin;
+    if (ang_threshold) *ang_threshold = b->ad_ang;
+    if (idle_steps) *idle_steps = b->ad_steps;
+    if (idle_time) *idle_time = b->ad_time;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchDownloadBodyFlags(dmxBatchID b, uint8_t *flags_out, int64_t first, int64_t count)
+{
+    if (!b || !flags_out || first < 0 || count < 0 || first + count > b->n) return DMX_EINVAL;
+    { const int rc_close = dmx_close_chunk(b); if (rc_close != DMX_OK) return rc_close; }
+    HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_ad_merge(b); if (rc != DMX_OK) return rc; }
+    b->ad_flag_reads++;
+    if (count) memcpy(flags_out, b->h_bflags.data() + first, (size_t)count);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchIdleCounters(dmxBatchID b, int32_t *steps_left, double *time_left)
+{
+    if (!b || (!steps_left && !time_left)) return DMX_EINVAL;
+    { const int rc_close = dmx_close_chunk(b); if (rc_close != DMX_OK) return rc_close; }
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->ad_steps_dev) {          // (no slot has ever carried one of the two bits: every counter stands at the batch's values)
+        for (int64_t s = 0; s < b->n; s++) { if (steps_left) steps_left[s] = b->ad_steps; if (time_left) time_left[s] = b->ad_time; }
+        return DMX_OK;
+    }
+    if (steps_left) HIP_TRY(hipMemcpyAsync(steps_left, b->ad_steps_dev, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    if (time_left) HIP_TRY(hipMemcpyAsync(time_left, b->ad_time_dev, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchAutoDisableStats(dmxBatchID b, int64_t out[4])
+{
+    if (!b || !out) return DMX_EINVAL;
+    HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_ad_merge(b); if (rc != DMX_OK) return rc; }
+    out[0] = b->ad_n_disabled; out[1] = b->ad_skipped; out[2] = b->ad_slept; out[3] = b->ad_woken;
     return DMX_OK;
 }
 

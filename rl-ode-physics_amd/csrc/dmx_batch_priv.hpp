@@ -16,6 +16,7 @@
 #include "dmx_internal.hpp"
 #include "dmx_uniform.hpp"
 #include "dmx_fixed.hpp"
+#include "dmx_autodisable.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -219,7 +220,25 @@ struct dmxBatch {
     const void *fb_devp = nullptr, *fb_host = nullptr;
     std::vector<char> fb_tmp;
     int64_t last_units = 0;                        // units the last dmxBatchStepJoints tick carried among its contact entries
+    // auto-disable (dmxBatchSetAutoDisable; the rule is in dmx_autodisable.hpp, the host side in dmx_joints.cpp).  The counters
+    // live on the device, one per slot, allocated with the first slot that carries DMX_BODY_AUTODISABLE.  ad_mirror: one byte
+    // per slot, host-mapped pinned -- a single-launch tick's kernel writes the stepped slots' flag bytes there, the general
+    // path copies the device's flag bytes into it behind its kernels; ad_pending = such a tick is enqueued and its DISABLED bits
+    // have not reached h_bflags yet: dmx_ad_merge waits for ad_ev (recorded behind the tick) and takes them over.
+    double ad_lin = 0.01, ad_ang = 0.01, ad_time = 0.0;
+    int ad_steps = 10;
+    int32_t *ad_steps_dev = nullptr; double *ad_time_dev = nullptr;
+    uint8_t *ad_mirror = nullptr, *ad_mirror_dev = nullptr;
+    hipEvent_t ad_ev = nullptr, ad_wait_ev = nullptr; bool ad_pending = false;      // ad_wait_ev: ad_ev, or the small tick's own event
+    int64_t ad_n_auto = 0, ad_n_disabled = 0;      // slots of [0, n) that carry AUTODISABLE / ALIVE and DISABLED, by h_bflags
+    int64_t ad_skipped = 0, ad_slept = 0, ad_woken = 0, ad_flag_reads = 0;      // dmxBatchAutoDisableStats [1] .. [3]; dmxBatchDownloadBodyFlags calls
+    std::vector<int> sc_ad_dropped;                // the live slots the tick in the making leaves out (asleep islands)
+    std::vector<uint8_t> sc_awake;                 // per slot, idle = 0: the island rooted at the slot holds an awake body (dmx_joints.cpp)
 };
+// auto-disable: the per-slot counters (reset to the batch's values) and the flag mirror, made when the feature is first used
+int dmx_ad_ensure(dmxBatch *b);
+// the DISABLED bits a tick enqueued earlier has set -> h_bflags (waits for that tick; nothing to do when none is pending)
+int dmx_ad_merge(dmxBatch *b);
 inline bool dmx_limot_present(const dmxHingeLimot &l) { return dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax); }
 // the ticks that build their own islands on the device do not know articulation joints: they say so instead of ignoring them
 inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
@@ -235,7 +254,7 @@ inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
 inline bool dmx_refuse_flags(const dmxBatch *b, const char *what)
 {
     if (b->n_flagged == 0) return false;
-    fprintf(stderr, "libode_mi355: %s does not honour per-body flags (dmxBatchUploadBodyFlags): %lld slot(s) carry a byte other than DMX_BODY_ALIVE; use dmxBatchStepJoints\n",
+    fprintf(stderr, "libode_mi355: %s does not honour per-body flags (dmxBatchUploadBodyFlags): %lld slot(s) carry a byte other than DMX_BODY_ALIVE (DMX_BODY_AUTODISABLE and DMX_BODY_DISABLED included); use dmxBatchStepJoints\n",
             what, (long long)b->n_flagged);
     return true;
 }

@@ -94,6 +94,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour articulation joints (dmxBatchSetJoints)\n");
         return DMX_EINVAL;
     }
+    { const int rc_ad = dmx_ad_merge(b); if (rc_ad != DMX_OK) return rc_ad; }      // (the islands below are judged by the bytes the last tick left)
     int n_limots = 0;
     if (!b->art.empty()) {
         for (size_t a = 0; a < b->art.size(); a++) {
@@ -121,7 +122,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             }
         }
     }
-    const int n_units = (int)cj.size();
+    int n_units = (int)cj.size();
     // rows of an entry, and how many of them can clamp (a limot unit's one row is counted as able to, whatever its state will be)
     auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT; };
     auto rpc_of = [&](const CJ &c) { return c.unit ? ((c.unit == UNIT_HINGE2 || c.unit == UNIT_SLIDER2) ? 2 : is_limot(c.unit) ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
@@ -141,6 +142,51 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         cj.push_back(c);
         if (pyramid_bits(j)) pyramid = true;
     }
+    // ---- auto-disable: an island without an awake body is left out of the tick, whole; in an awake island every member is awake.
+    // Only while some live slot is asleep: a batch without one does nothing here but compare a count.
+    std::vector<int> &ad_dropped = b->sc_ad_dropped;        // the live slots this tick leaves out
+    ad_dropped.clear();
+    b->ad_skipped = 0;
+    if (b->ad_n_disabled > 0 && !include && !geo) {
+        UnionFind uf(b->sc_parent);
+        for (const CJ &c : cj) if (c.b2 >= 0) uf.unite(c.b1, c.b2);
+        std::vector<uint8_t> &awake = b->sc_awake;
+        awake.assign((size_t)n, 0);
+        for (int s = 0; s < n; s++) if (live(s) && !(b->h_bflags[(size_t)s] & BF_DISABLED)) awake[(size_t)uf.find(s)] = 1;
+        int64_t woke_lo = -1, woke_hi = -1;
+        for (int s = 0; s < n; s++) {
+            if (!live(s)) continue;
+            const int r = uf.find(s);
+            if (!awake[(size_t)r]) { ad_dropped.push_back(s); if (r == s) b->ad_skipped++; continue; }
+            if (b->h_bflags[(size_t)s] & BF_DISABLED) {      // woken by the island rule: the bit goes, the counters stand
+                b->h_bflags[(size_t)s] &= (uint8_t)~BF_DISABLED;
+                b->ad_woken++; b->ad_n_disabled--;
+                if (woke_lo < 0) woke_lo = s;
+                woke_hi = s;
+            }
+        }
+        if (!ad_dropped.empty()) {
+            // their joints make no rows: the entries go before anything is counted, scheduled or staged (order kept: units first)
+            size_t keep = 0;
+            n_units = 0; n_limots = 0; pyramid = false;
+            for (size_t k = 0; k < cj.size(); k++) {
+                const CJ &c = cj[k];
+                if (!awake[(size_t)uf.find(c.b1)]) continue;
+                if (c.unit) { n_units++; if (c.unit == UNIT_LIMOT || c.unit == UNIT_SLIMOT) n_limots++; }
+                else if (pyramid_bits(*c.j)) pyramid = true;
+                cj[keep++] = c;
+            }
+            cj.resize(keep);
+        }
+        // scratch back to its idle state (the tick's own grouping below starts from the identity again, over the entries kept);
+        // sc_awake: 2 marks a slot left out until the tick's list of slots is made, 0 otherwise
+        for (int s = 0; s < n; s++) if (live(s)) { b->sc_parent[(size_t)s] = s; awake[(size_t)s] = 0; }
+        for (int s : ad_dropped) awake[(size_t)s] = 2;
+        if (woke_lo >= 0) {
+            b->state_version++;
+            HIP_TRY(hipMemcpyAsync(b->bflags + woke_lo, b->h_bflags.data() + woke_lo, (size_t)(woke_hi - woke_lo + 1), hipMemcpyHostToDevice, b->stream));
+        }
+    }
     const int nc = (int)cj.size();
     if (pyramid && b->row_order_ode && !exact) {
         // ODE moves such rows to the end of its order; this library defines them in creation order only (include/dmx_batch.h)
@@ -159,8 +205,17 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     std::vector<int> &slots = b->sc_slots;
     slots.clear();
     if (include && b->sc_include_list) slots.assign(b->sc_include_list, b->sc_include_list + b->sc_include_count);
-    else for (int s = 0; s < n; s++) if (live(s)) slots.push_back(s);
+    else if (ad_dropped.empty()) { for (int s = 0; s < n; s++) if (live(s)) slots.push_back(s); }
+    else {
+        for (int s = 0; s < n; s++) if (live(s) && b->sc_awake[(size_t)s] != 2) slots.push_back(s);
+        for (int s : ad_dropped) b->sc_awake[(size_t)s] = 0;
+    }
     const int nlive = (int)slots.size();
+    // does the tick step a body that can fall asleep?  Then the end-of-tick rule runs behind it, and its flags travel to the host
+    bool ad_tick = false;
+    if (b->ad_n_auto > 0 && !include && !geo)
+        for (int s : slots) if (b->h_bflags[(size_t)s] & BF_AUTODISABLE) { ad_tick = true; break; }
+    const IdleParams<T> ad_params = make_idle_params<T>(b->ad_lin, b->ad_ang, b->ad_steps, b->ad_time, h);
 
     // ---- islands ----------------------------------------------------------------------------------------
     UnionFind uf(b->sc_parent);
@@ -668,8 +723,19 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         } else {
             lds = small_tick_sor_lds((int)sizeof(T), big_max_bodies, &K.lds_bodies);
         }
-        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream, pyramid));
+        // the kernel's AD instantiation: for the end-of-tick rule, and whenever slots were left out (a full refresh of the mirror
+        // must cover them).  The flag mirror starts as the host's bytes, the slots left out marked.
+        const bool ad_kernel = ad_tick || !ad_dropped.empty();
+        if (ad_kernel) {
+            if ((rc = dmx_ad_ensure(b)) != DMX_OK) return rc;
+            memcpy(b->ad_mirror, b->h_bflags.data(), (size_t)n);
+            for (int s : ad_dropped) b->ad_mirror[s] |= SMALL_AD_SKIPPED;
+            K.ad_flags = b->bflags; K.ad_mirror = b->ad_mirror_dev;
+            K.ad_steps = b->ad_steps_dev; K.ad_time = b->ad_time_dev; K.ad = ad_params;
+        }
+        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream, pyramid, ad_kernel));
         HIP_TRY(hipEventRecord(b->sm_ev[sp], b->stream));
+        if (ad_tick) { b->ad_wait_ev = b->sm_ev[sp]; b->ad_pending = true; }      // (the tick's own event gates the flag mirror too)
         b->sm_ev_pending[sp] = true;
         b->sm_parity = sp ^ 1;
         b->sm_diag_cur = cur;
@@ -763,6 +829,14 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb, pyramid));
         if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
         if (ode_order) HIP_TRY(hipStreamSynchronize(b->stream));      // the order table came from pageable host memory
+    }
+    if (ad_tick) {
+        // behind the tick's last kernel: the rule for every slot it stepped, then the flag bytes on their way to the host
+        if ((rc = dmx_ad_ensure(b)) != DMX_OK) return rc;
+        HIP_TRY(launch_autodisable_update<T>((T *)b->slab, b->bflags, b->ad_steps_dev, b->ad_time_dev, ad_params, I.bodies, nlive, n, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->ad_mirror, b->bflags, (size_t)n, hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipEventRecord(b->ad_ev, b->stream));
+        b->ad_wait_ev = b->ad_ev; b->ad_pending = true;
     }
     b->fb_valid = fb;
     b->last_islands = true;

@@ -14,6 +14,7 @@
 #include "dmx_islands_dev.hpp"
 #include "dmx_lcp_lds.hpp"
 #include "dmx_small.hpp"
+#include "dmx_autodisable.hpp"
 
 namespace dmx {
 
@@ -42,7 +43,10 @@ template <class T> __device__ __forceinline__ void island_feedback(const IslandS
 // existed (F is an argument they never read).
 // APX: a QuickStep tick with pyramid rows (DMX_CONTACT_APPROX1): the island functions' APX instantiations, made with FB's store on --
 // F.mode says whether the tick reports feedback too.  (Under dWorldStep such a tick takes the general path.)
-template <class T, bool EXACT, bool FB = false, bool APX = false>
+// AD: a tick that stepped a body with DMX_BODY_AUTODISABLE, or left an asleep island out: the thread that finished a body applies
+// the end-of-tick rule (idle_update) before it mirrors the body, and writes the body's flag byte to the host-mapped flag mirror.
+// An instantiation of its own again: a tick without such a body launches the kernel it launched before auto-disable existed.
+template <class T, bool EXACT, bool FB = false, bool APX = false, bool AD = false>
 __global__ __launch_bounds__(EXACT ? 256 : 64) void small_world_tick(T *S, const uint8_t *bflags, int64_t stride, IslandSet<T> I, StepParams<T> P,
                                                                      StepDiag *diag, SmallTick<T> K, FeedbackSet<T> F)
 {
@@ -56,7 +60,11 @@ __global__ __launch_bounds__(EXACT ? 256 : 64) void small_world_tick(T *S, const
         const int isl = I.big_list[blockIdx.x];
         if (FB && (!APX || F.mode != FB_OFF)) island_feedback(I, P, F, isl, tid, WG);                                       // (the rows' lambda is behind the barrier)
         const int b0 = I.body_off[isl], nb = I.body_off[isl + 1] - b0;
-        for (int k = tid; k < nb; k += WG) mirror_body(S, K.mirror, I.bodies[b0 + k]);      // (body k was finished by this thread)
+        for (int k = tid; k < nb; k += WG) {                                                // (body k was finished by this thread)
+            const int s = I.bodies[b0 + k];
+            if (AD) K.ad_mirror[s] = idle_update<T>(S, K.ad_flags, K.ad_steps, K.ad_time, K.ad, s);
+            mirror_body(S, K.mirror, s);
+        }
     } else {
         constexpr int LANES = EXACT ? WG : SMALL_TAIL_LANES;
         const int isl = (int)(blockIdx.x - (unsigned)I.n_big) * LANES + tid;
@@ -68,12 +76,19 @@ __global__ __launch_bounds__(EXACT ? 256 : 64) void small_world_tick(T *S, const
             }
             if (FB && (!APX || F.mode != FB_OFF)) island_feedback(I, P, F, isl, 0, 1);
             const int b0 = I.body_off[isl], nb = I.body_off[isl + 1] - b0;
-            for (int k = 0; k < nb; k++) mirror_body(S, K.mirror, I.bodies[b0 + k]);
+            for (int k = 0; k < nb; k++) {
+                const int s = I.bodies[b0 + k];
+                if (AD) K.ad_mirror[s] = idle_update<T>(S, K.ad_flags, K.ad_steps, K.ad_time, K.ad, s);
+                mirror_body(S, K.mirror, s);
+            }
         }
     }
     if (K.full)         // slots outside every island (not alive): nobody else brings the mirror up to date for them
-        for (int s = (int)(blockIdx.x * WG) + tid; s < K.n_slots; s += (int)(gridDim.x * WG))
-            if (!(bflags[s] & BF_ALIVE)) mirror_body(S, K.mirror, s);
+        for (int s = (int)(blockIdx.x * WG) + tid; s < K.n_slots; s += (int)(gridDim.x * WG)) {
+            // AD: ... nor for the slots of the asleep islands this tick left out, which the host marked in the flag mirror
+            // (SMALL_AD_SKIPPED: no thread of this tick writes such a slot's entry, so reading it here races with nobody)
+            if (AD ? (!(K.ad_flags[s] & BF_ALIVE) || (K.ad_mirror[s] & SMALL_AD_SKIPPED)) : !(bflags[s] & BF_ALIVE)) mirror_body(S, K.mirror, s);
+        }
 }
 
 size_t small_tick_sor_lds(int real_bytes, int max_bodies, int *lds_bodies)
@@ -85,7 +100,7 @@ size_t small_tick_sor_lds(int real_bytes, int max_bodies, int *lds_bodies)
     return std::max(wg, tail);
 }
 
-template <class T, bool FB, bool APX = false>
+template <class T, bool FB, bool APX = false, bool AD = false>
 static hipError_t launch_small_tick_fb(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
                                        const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st)
 {
@@ -94,27 +109,32 @@ static hipError_t launch_small_tick_fb(T *S, const uint8_t *bflags, int64_t stri
     const unsigned grid = (unsigned)I.n_big + (unsigned)std::max(1, (I.n_islands + lanes - 1) / lanes);
     if (exact && !APX) {
         if (lds_bytes > (size_t)64 * 1024) {
-            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&small_world_tick<T, true, FB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&small_world_tick<T, true, FB, false, AD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
             if (ea != hipSuccess) return ea;
         }
-        hipLaunchKernelGGL((small_world_tick<T, true, FB>), dim3(grid), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
+        hipLaunchKernelGGL((small_world_tick<T, true, FB, false, AD>), dim3(grid), dim3(256), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
     } else {
-        hipLaunchKernelGGL((small_world_tick<T, false, FB, APX>), dim3(grid), dim3(64), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
+        hipLaunchKernelGGL((small_world_tick<T, false, FB, APX, AD>), dim3(grid), dim3(64), lds_bytes, st, S, bflags, stride, I, P, diag, K, F);
     }
     return hipGetLastError();
 }
 template <class T>
 hipError_t launch_small_tick(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid)
+                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid, bool ad)
 {
+    if (ad) {
+        if (pyramid) return exact ? hipErrorInvalidValue : launch_small_tick_fb<T, true, true, true>(S, bflags, stride, I, P, diag, K, F, false, lds_bytes, st);
+        return F.mode != FB_OFF ? launch_small_tick_fb<T, true, false, true>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st)
+                                : launch_small_tick_fb<T, false, false, true>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st);
+    }
     if (pyramid) return exact ? hipErrorInvalidValue : launch_small_tick_fb<T, true, true>(S, bflags, stride, I, P, diag, K, F, false, lds_bytes, st);
     return F.mode != FB_OFF ? launch_small_tick_fb<T, true>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st)
                             : launch_small_tick_fb<T, false>(S, bflags, stride, I, P, diag, K, F, exact, lds_bytes, st);
 }
 template hipError_t launch_small_tick<float>(float *, const uint8_t *, int64_t, const IslandSet<float> &, const StepParams<float> &, StepDiag *,
-                                             const SmallTick<float> &, const FeedbackSet<float> &, bool, size_t, hipStream_t, bool);
+                                             const SmallTick<float> &, const FeedbackSet<float> &, bool, size_t, hipStream_t, bool, bool);
 template hipError_t launch_small_tick<double>(double *, const uint8_t *, int64_t, const IslandSet<double> &, const StepParams<double> &, StepDiag *,
-                                              const SmallTick<double> &, const FeedbackSet<double> &, bool, size_t, hipStream_t, bool);
+                                              const SmallTick<double> &, const FeedbackSet<double> &, bool, size_t, hipStream_t, bool, bool);
 
 hipError_t dmx_touch_small(int real_bytes)
 {

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "dmx_batch_priv.hpp"
+#include "dmx_autodisable.hpp"
 
 namespace dmx {
 
@@ -25,11 +26,19 @@ template <class T> struct SmallTick {
     int full;              // 1: the mirror was not valid before this tick -- the slots no island steps are copied too
     int lds_bodies;        // QuickStep: accumulators of up to this many island bodies in LDS (as launch_islands chooses)
     int murty; T tol_rel;  // dWorldStep: lcp_island_lds' pivoting mode and tolerance (as launch_lcp_lds chooses)
+    // auto-disable, read by the kernel's AD instantiation only: the device's flag bytes as the view idle_update reads and writes, the
+    // host-mapped flag mirror (one byte per slot, filled by the host before the launch: SMALL_AD_SKIPPED marks the slots of asleep
+    // islands), the per-slot counters and the rule's parameters
+    uint8_t *ad_flags = nullptr, *ad_mirror = nullptr;
+    int32_t *ad_steps = nullptr; double *ad_time = nullptr;
+    IdleParams<T> ad;
 };
+// in the host-mapped flag mirror only, never in a flag byte: the tick left this live slot out (an asleep island)
+constexpr uint8_t SMALL_AD_SKIPPED = 0x80;
 
 template <class T>
 hipError_t launch_small_tick(T *S, const uint8_t *bflags, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, StepDiag *diag,
-                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid = false);      // (F.mode: the kernel's FB instantiation; pyramid: its APX one, QuickStep only)
+                             const SmallTick<T> &K, const FeedbackSet<T> &F, bool exact, size_t lds_bytes, hipStream_t st, bool pyramid = false, bool ad = false);      // (F.mode: the kernel's FB instantiation; pyramid: its APX one, QuickStep only; ad: its AD one)
 // dynamic LDS of the QuickStep form for islands of up to max_bodies bodies (out: SmallTick::lds_bodies)
 size_t small_tick_sor_lds(int real_bytes, int max_bodies, int *lds_bodies);
 hipError_t dmx_touch_small(int real_bytes);

@@ -130,6 +130,20 @@ struct dxWorld {
     std::vector<double> dev_statics;   // the static boxes the device holds (18 doubles each), for the device pair search
     std::vector<dReal> buf;
     std::vector<dmxContactJoint> cj;
+    // auto-disable (dWorldSetAutoDisable*).  The four values are the world's and hold for all its bodies (stock ODE copies them
+    // into a body at creation); the flag is what dBodyCreate copies.  ad_dirty: the batch has not been told the values yet.
+    // n_ad: bodies whose flags carry DMX_BODY_AUTODISABLE or DMX_BODY_DISABLED -- only while there is one does to_host() ask the
+    // batch for the flag bytes; a world that never touches the feature makes no call it did not make before.
+    bool ad_flag = false, ad_dirty = false;
+    double ad_lin = 0.01, ad_ang = 0.01, ad_time = 0.0;
+    int ad_steps = 10, n_ad = 0;
+    std::vector<uint8_t> flbuf;
+    void set_flags(dxBody *b, int flags)
+    {
+        const int bits = DMX_BODY_AUTODISABLE | DMX_BODY_DISABLED;
+        n_ad += (int)((flags & bits) != 0) - (int)((b->flags & bits) != 0);
+        b->flags = flags;
+    }
 
     void create_batch(int capacity)
     {
@@ -146,6 +160,7 @@ struct dxWorld {
         pushed_valid = false;          // a new batch has been told nothing yet
         art_dirty = !arts.empty();
         feedback_sent = false;         // (a new batch's feedback is off: world_step switches it on again if a struct is set)
+        ad_dirty = ad_lin != 0.01 || ad_ang != 0.01 || ad_steps != 10 || ad_time != 0.0;      // (a new batch holds the defaults)
         // One read-back the general way into the buffer to_host() uses, now.  The runtime registers a pageable destination the
         // first time a device-to-host copy lands in it (8 ms, measured); a world whose ticks run on the single-launch path reads
         // its poses from the batch's host mirror and would meet that at the first tick that falls back -- a whole 120 Hz frame.
@@ -179,6 +194,14 @@ struct dxWorld {
             const dReal *r = &buf[(size_t)s * 13];
             for (int k = 0; k < 3; k++) { b->pos[k] = r[k]; b->lvel[k] = r[7 + k]; b->avel[k] = r[10 + k]; }
             for (int k = 0; k < 4; k++) b->q[k] = r[3 + k];
+        }
+        if (n_ad > 0 && hi > 0) {
+            // the DISABLED bits the ticks set or cleared come back too: to_device() uploads every slot's flags from dxBody::flags,
+            // and a stale byte there would wake a sleeper or put a woken body back to sleep
+            flbuf.resize((size_t)hi);
+            DMX_MUST(dmxBatchDownloadBodyFlags(batch, flbuf.data(), 0, hi));
+            for (int s = 0; s < hi; s++)
+                if (dxBody *b = slots[(size_t)s]) set_flags(b, (b->flags & ~DMX_BODY_DISABLED) | (flbuf[(size_t)s] & DMX_BODY_DISABLED));
         }
         for (dxBody *b : slots) {
             if (!b) continue;
@@ -302,13 +325,35 @@ extern "C" void dWorldSetQuickStepNumIterations(dWorldID w, int n) { w->iters = 
 extern "C" int dWorldGetQuickStepNumIterations(dWorldID w) { return w->iters; }
 extern "C" void dWorldSetQuickStepW(dWorldID w, dReal v) { w->sor_w = v; }
 extern "C" dReal dWorldGetQuickStepW(dWorldID w) { return w->sor_w; }
+// auto-disable: the flag is what dBodyCreate copies into a new body; the four values are the world's and hold for ALL its bodies
+// from the next step on -- stock ODE copies them into a body at creation and lets dBodySetAutoDisable* change them per body
+// [ODE-recall]; setting one resets every body's idle counters (dmxBatchSetAutoDisable)
+extern "C" void dWorldSetAutoDisableFlag(dWorldID w, int do_auto_disable) { w->ad_flag = do_auto_disable != 0; }
+extern "C" int dWorldGetAutoDisableFlag(dWorldID w) { return w->ad_flag ? 1 : 0; }
+extern "C" void dWorldSetAutoDisableLinearThreshold(dWorldID w, dReal v) { if (v >= 0) { w->ad_lin = v; w->ad_dirty = true; } }
+extern "C" dReal dWorldGetAutoDisableLinearThreshold(dWorldID w) { return (dReal)w->ad_lin; }
+extern "C" void dWorldSetAutoDisableAngularThreshold(dWorldID w, dReal v) { if (v >= 0) { w->ad_ang = v; w->ad_dirty = true; } }
+extern "C" dReal dWorldGetAutoDisableAngularThreshold(dWorldID w) { return (dReal)w->ad_ang; }
+extern "C" void dWorldSetAutoDisableSteps(dWorldID w, int steps) { if (steps >= 0) { w->ad_steps = steps; w->ad_dirty = true; } }
+extern "C" int dWorldGetAutoDisableSteps(dWorldID w) { return w->ad_steps; }
+extern "C" void dWorldSetAutoDisableTime(dWorldID w, dReal t) { if (t >= 0) { w->ad_time = t; w->ad_dirty = true; } }
+extern "C" dReal dWorldGetAutoDisableTime(dWorldID w) { return (dReal)w->ad_time; }
+extern "C" void dWorldSetAutoDisableAverageSamplesCount(dWorldID, unsigned int n)
+{
+    if (n != 1) fprintf(stderr, "libode_mi355: dWorldSetAutoDisableAverageSamplesCount: %u is not supported (the idle test looks at one sample, the step's own); ignored\n", n);
+}
+extern "C" int dWorldGetAutoDisableAverageSamplesCount(dWorldID) { return 1; }
 
 static int world_step(dWorldID w, dReal h, int stepper)
 {
     if (!w || !(h > 0)) return 0;
     w->to_device();
     w->push_params(stepper);
-    if (w->art_dirty) {                // the articulation joints go to the batch only when they changed
+    if (w->ad_dirty) {                 // (resets every slot's idle counters: include/dmx_batch.h)
+        DMX_MUST(dmxBatchSetAutoDisable(w->batch, w->ad_lin, w->ad_ang, w->ad_steps, w->ad_time));
+        w->ad_dirty = false;
+    }
+    if (w->art_dirty) {               // the articulation joints go to the batch only when they changed
         w->aj.clear();
         for (const dxJoint *j : w->arts) {
             dmxJoint a;
@@ -449,6 +494,7 @@ extern "C" dBodyID dBodyCreate(dWorldID w)
     dMassSetParameters(&b->mass, 1, 0, 0, 0, 1, 1, 1, 0, 0, 0);   // ODE default; the reference never sets mass (F7)
     w->slots[(size_t)slot] = b;
     w->host_dirty = true;
+    if (w->ad_flag) w->set_flags(b, b->flags | DMX_BODY_AUTODISABLE);      // dBodySetAutoDisableDefaults
     return b;
 }
 extern "C" void dBodyDestroy(dBodyID b)
@@ -460,6 +506,7 @@ extern "C" void dBodyDestroy(dBodyID b)
     for (dxJoint *j : w->joints) { if (j->b1 == b) j->b1 = nullptr; if (j->b2 == b) j->b2 = nullptr; }
     // its articulation joints are detached on both sides, ODE's limbo: inactive until attached again
     for (dxJoint *j : w->arts) if (j->b1 == b || j->b2 == b) { j->b1 = j->b2 = nullptr; w->art_dirty = true; }
+    w->set_flags(b, DMX_BODY_ALIVE);      // (out of the count of bodies with an auto-disable bit)
     w->slots[(size_t)b->slot] = nullptr;
     w->host_dirty = true;
     delete b;
@@ -495,6 +542,20 @@ extern "C" void dBodySetDynamic(dBodyID b) { touch(b); b->flags &= ~DMX_BODY_KIN
 extern "C" int dBodyIsKinematic(dBodyID b) { return (b->flags & DMX_BODY_KINEMATIC) != 0; }
 extern "C" void dBodySetGyroscopicMode(dBodyID b, int on) { touch(b); if (on) b->flags &= ~DMX_BODY_NOGYRO; else b->flags |= DMX_BODY_NOGYRO; }
 extern "C" int dBodyGetGyroscopicMode(dBodyID b) { return (b->flags & DMX_BODY_NOGYRO) == 0; }
+// auto-disable (include/dmx_batch.h, "auto-disable").  touch() brings the DISABLED bits the ticks left back first, so the upload
+// of every slot's flags that follows a change changes this body's byte only.  dBodyEnable clears DISABLED, which resets the
+// body's idle counters in the batch; dBodyDisable sets it and leaves the velocities as they are [ODE-recall].
+extern "C" void dBodySetAutoDisableFlag(dBodyID b, int do_auto_disable)
+{
+    touch(b);
+    // (switching it off also enables the body [ODE-recall dBodySetAutoDisableFlag: "reset the IsDisabled state"])
+    b->world->set_flags(b, do_auto_disable ? b->flags | DMX_BODY_AUTODISABLE : b->flags & ~(DMX_BODY_AUTODISABLE | DMX_BODY_DISABLED));
+}
+extern "C" int dBodyGetAutoDisableFlag(dBodyID b) { return (b->flags & DMX_BODY_AUTODISABLE) != 0; }
+extern "C" void dBodySetAutoDisableDefaults(dBodyID b) { dBodySetAutoDisableFlag(b, b->world->ad_flag ? 1 : 0); }
+extern "C" void dBodyEnable(dBodyID b) { touch(b); b->world->set_flags(b, b->flags & ~DMX_BODY_DISABLED); }
+extern "C" void dBodyDisable(dBodyID b) { touch(b); b->world->set_flags(b, b->flags | DMX_BODY_DISABLED); }
+extern "C" int dBodyIsEnabled(dBodyID b) { b->world->to_host(); return (b->flags & DMX_BODY_DISABLED) == 0; }
 extern "C" void dBodyAddForce(dBodyID b, dReal x, dReal y, dReal z) { touch(b); b->facc[0] += x; b->facc[1] += y; b->facc[2] += z; }
 extern "C" void dBodyAddTorque(dBodyID b, dReal x, dReal y, dReal z) { touch(b); b->tacc[0] += x; b->tacc[1] += y; b->tacc[2] += z; }
 extern "C" void dBodySetMass(dBodyID b, const dMass *m)
