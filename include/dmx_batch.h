@@ -235,6 +235,14 @@ int dmxBatchSetTorqueFree(dmxBatchID b, int on);
 /* for tests and diagnostics: [0] contact-free launches so far that took a kernel with the short tick built in (the rule said on),
  * [1] those that took the general kernel.  Which wavefronts of a launch pass the quaternion guard is not counted. */
 int dmxBatchTorqueFreeStats(dmxBatchID b, int64_t out[2]);
+/* Instructions the lean launch does not need: a contact-free launch that is lean (dmxBatchSetLoadElision), has its constants as
+ * arguments and takes the short tick (dmxBatchSetTorqueFree) -- one tick, in place, no force accumulators -- runs a kernel of its
+ * own whose wavefronts read a compact argument block, step one tile in a straight line when the tile's lateral axes are fixed and
+ * every quaternion passes the short tick's guard, and run the general launch's tile body otherwise.  Same results bit for bit.
+ * Default on (DMX_LEAN_KERNEL=0 in the environment, read at dmxBatchCreate: off -- the launches are then the ones they always were). */
+int dmxBatchSetLeanKernel(dmxBatchID b, int on);
+/* for tests and diagnostics: [0] contact-free launches so far that took that kernel, [1] those that did not */
+int dmxBatchLeanKernelStats(dmxBatchID b, int64_t out[2]);
 /* for tests and diagnostics, never on a hot path (takes the counts, then settles the batch -- which, like every observer, breaks
  * the chain: that break shows in the next call's count -- and reads the words back): [0] launches that established the
  * words, [1] lean launches, [2] times the chain was broken, [3] 1 once ended for good, [4] / [5] tiles of the active range whose

@@ -24,7 +24,7 @@ BATCH_SYMBOLS = [
     "dmxBatchChunkBegin", "dmxBatchChunkTick", "dmxBatchCheckZonesOnStream", "dmxBatchChunkEnd",
     "dmxBatchChunkCommit", "dmxBatchChunkRollback", "dmxBatchExactTick", "dmxBatchRefreshGhostsOnStream", "dmxBatchSetConvexHull", "dmxBatchChunkTicks", "dmxBatchSetTicksPerLaunch",
     "dmxBatchSetSnapshotMode", "dmxBatchSetStaticBoxes", "dmxBatchSetStepper", "dmxBatchSetConvexHullFaces",
-    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision", "dmxBatchSetLoadElision", "dmxBatchSetTorqueFree", "dmxBatchTorqueFreeStats", "dmxBatchLoadElisionStats",
+    "dmxBatchCollisionStatsEx", "dmxBatchFindPairs", "dmxBatchCrossPairs", "dmxBatchSetRowOrder", "dmxBatchLcpStats", "dmxBatchSetSmallTick", "dmxBatchSmallTickStats", "dmxBatchSetExactPipeline", "dmxBatchSetStaticPath", "dmxBatchSetClassPairs", "dmxBatchSetElision", "dmxBatchSetLoadElision", "dmxBatchSetTorqueFree", "dmxBatchTorqueFreeStats", "dmxBatchLoadElisionStats", "dmxBatchSetLeanKernel", "dmxBatchLeanKernelStats",
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
@@ -114,6 +114,8 @@ def load():
     sig("dmxBatchSetTorqueFree", I, P, I)
     sig("dmxBatchTorqueFreeStats", I, P, P)
     sig("dmxBatchLoadElisionStats", I, P, P)
+    sig("dmxBatchSetLeanKernel", I, P, I)
+    sig("dmxBatchLeanKernelStats", I, P, P)
     sig("dmxBatchSetExactPipeline", I, P, I)
     sig("dmxBatchSetStaticPath", I, P, I)
     sig("dmxBatchSetClassPairs", I, P, I, I, I)

@@ -437,6 +437,17 @@ class BatchWorld:
         _check(self.lib.dmxBatchTorqueFreeStats(self.h, out), "dmxBatchTorqueFreeStats")
         return {"short": int(out[0]), "general": int(out[1])}
 
+    def set_lean_kernel(self, on=True):
+        """lean contact-free launches with the short tick on run the straight-line kernel of their own (default on;
+        include/dmx_batch.h).  Same results bit for bit."""
+        _check(self.lib.dmxBatchSetLeanKernel(self.h, 1 if on else 0), "dmxBatchSetLeanKernel")
+
+    def lean_kernel_stats(self):
+        """dict: contact-free launches that took the straight-line kernel / any other kernel"""
+        out = (C.c_int64 * 2)()
+        _check(self.lib.dmxBatchLeanKernelStats(self.h, out), "dmxBatchLeanKernelStats")
+        return {"lean_kernel": int(out[0]), "other": int(out[1])}
+
     def load_elision_stats(self):
         """dict: establish / lean launches, chain breaks, ended for good, tiles with x / z fixed.  Settles the batch."""
         out = (C.c_int64 * 6)()

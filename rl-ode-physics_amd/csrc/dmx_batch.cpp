@@ -92,6 +92,8 @@ extern "C" int dmxBatchCreate(dmxBatchID *out, int64_t n, int precision, int dev
         b->fix.on = loads_default;
         static const bool torque_free_default = [] { const char *e = getenv("DMX_TORQUE_FREE"); return !(e && atoi(e) == 0); }();
         b->torque_free = torque_free_default;
+        static const bool lean_kernel_default = [] { const char *e = getenv("DMX_LEAN_KERNEL"); return !(e && atoi(e) == 0); }();
+        b->lean_kernel = lean_kernel_default;
     }
     b->prof_on = getenv("DMX_HOST_PROFILE") != nullptr;
     {
@@ -546,7 +548,8 @@ template <class T> static int step_t(dmxBatch *b, double h, int nsteps, int64_t 
         P.ticks = ext ? 1 : std::min(per, nsteps - s);
         T *S = (T *)b->slab + slab_ix(0, first);
         const int fix_mode = dmx_fix_next<T>(b, P, first, count, true, ext);
-        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev, fix_mode, b->fix_words, b->torque_free, b->tf_stats));
+        HIP_TRY(launch_step<T>(S, S, b->gtype + first, b->stride, count, P, ext, b->diag + first / 64, b->stream, b->sweep_rev, fix_mode, b->fix_words, b->torque_free, b->tf_stats,
+                               b->lean_kernel, b->lk_stats));
         if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
         s += P.ticks;
     }
@@ -650,6 +653,21 @@ extern "C" int dmxBatchTorqueFreeStats(dmxBatchID b, int64_t out[2])
 {
     if (!b || !out) return DMX_EINVAL;
     out[0] = b->tf_stats[0]; out[1] = b->tf_stats[1];
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetLeanKernel(dmxBatchID b, int on)
+{
+    if (!b || (on != 0 && on != 1)) return DMX_EINVAL;
+    SETTLE(b);
+    b->lean_kernel = on != 0;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchLeanKernelStats(dmxBatchID b, int64_t out[2])
+{
+    if (!b || !out) return DMX_EINVAL;
+    out[0] = b->lk_stats[0]; out[1] = b->lk_stats[1];
     return DMX_OK;
 }
 

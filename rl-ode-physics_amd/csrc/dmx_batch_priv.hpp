@@ -115,6 +115,10 @@ struct dmxBatch {
     // off): dmx_torque_free.hpp decides per launch whether it applies.  Off, the launches are the ones they always were.
     bool torque_free = true;
     int64_t tf_stats[2] = { 0, 0 };  // contact-free launches with / without the short tick built in (dmxBatchTorqueFreeStats)
+    // integrate_free_lean, the straight-line kernel of a lean launch (dmxBatchSetLeanKernel; DMX_LEAN_KERNEL=0 in the environment
+    // switches it off): launch_step decides per launch whether it applies.  Off, the launches are the ones they always were.
+    bool lean_kernel = true;
+    int64_t lk_stats[2] = { 0, 0 };  // contact-free launches that took that kernel / that did not (dmxBatchLeanKernelStats)
     bool stepped_with_plane = false;
     // general island path (explicit contact joints)
     uint8_t *bflags = nullptr;                 // device, per-slot BF_* flags

@@ -215,7 +215,8 @@ template <class T> int launch_fast(dmxBatch *b, const StepParams<T> &P, bool ext
         }
     }
     const int fix_mode = dmx_fix_next<T>(b, P, 0, b->n_active, So == S, ext);
-    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream, b->sweep_rev, fix_mode, b->fix_words, b->torque_free, b->tf_stats));
+    HIP_TRY(launch_step<T>(S, So, b->gtype, b->stride, b->n_active, P, ext, b->diag, b->stream, b->sweep_rev, fix_mode, b->fix_words, b->torque_free, b->tf_stats,
+                           b->lean_kernel, b->lk_stats));
     if (step_is_contact_free(P)) b->sweep_rev = !b->sweep_rev;      // the next one walks the tiles the other way (dmx_sweep.hpp)
     b->bp_fresh = false;                     // the poses have moved on from the ones the zones were built at
     if (So != S) {

@@ -276,10 +276,13 @@ struct StepDiag {
 // torque_free: the batch's switch for the short tick of a body without torque (dmx_torque_free.hpp decides per launch whether it
 // applies); off, the launch is the one it always was.  tf_stats: two counters of the caller's, [0] contact-free launches that took an
 // instantiation with the short tick, [1] those that did not (dmxBatchTorqueFreeStats).
+// lean_kernel: the batch's switch for integrate_free_lean, the straight-line kernel of a lean launch (dmx_kernels.hip: launch_step
+// has the rule); off, the launch is the one it always was.  lk_stats: two counters of the caller's, [0] contact-free launches that
+// took that kernel, [1] those that did not (dmxBatchLeanKernelStats).
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
                        StepDiag *diag, hipStream_t st, int rev, int fix_mode = 0, uint32_t *fix_words = nullptr, bool torque_free = false,
-                       int64_t *tf_stats = nullptr);
+                       int64_t *tf_stats = nullptr, bool lean_kernel = false, int64_t *lk_stats = nullptr);
 // does launch_step take these parameters to integrate_free (no plane, no static geometry with contact slots)?
 template <class T> inline bool step_is_contact_free(const StepParams<T> &P)
 {

@@ -25,6 +25,7 @@
 #include "dmx_fixed.hpp"
 #include "dmx_torque_free.hpp"
 #include "dmx_launch_consts.hpp"
+#include "dmx_lean_tick.hpp"
 
 namespace dmx {
 
@@ -108,119 +109,64 @@ __global__ __launch_bounds__(256, MINW) void integrate_free(T *S, T *So, int64_t
     const bool in_place = ELIDE && So == S;         // wave-uniform: two kernel arguments
     for (int64_t i = sweep_block(blockIdx.x, gridDim.x, rev) * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        if constexpr (!FIX) {
-            if (P.skip != nullptr && P.skip[i]) continue;      // this body belongs to the island path this tick
-        }
-        T c[NLOAD];
-        uint32_t fixed = 0, seen = 0;       // FIX, lean launches: the tile's word as read, and its lateral axes (wave-uniform)
-        if constexpr (FIX) {
-            // The tile's word first, then the loads every tile needs (pos.y, quat, lvel.y, avel and the constants): they are in flight
-            // before anything waits on the word.  Only then the lateral loads, one scalar branch per axis around both of its loads.
-            // The y axis is among the loads issued ahead of the word, so a fixed y saves nothing and bit 1 is kept for the record.
-            uint32_t word = 0;
-            if (fix_mode == FIX_LEAN) word = fix_words[__builtin_amdgcn_readfirstlane((int)(i >> 6))];
-#pragma unroll
-            for (int k = 0; k < NLOAD; k++)
-                if (k >= C_MASS || fix_axis_of(k) < 0 || fix_axis_of(k) == 1) c[k] = S[slab_ix(k, i)];
-            seen = __builtin_amdgcn_readfirstlane(word);
-            fixed = seen & 5u;
-#pragma unroll
-            for (int ax = 0; ax < 3; ax += 2) {
-                if (fixed & (1u << ax)) { c[C_POS + ax] = T(0); c[C_LVEL + ax] = T(0); }     // never looked at: see the stores
-                else { c[C_POS + ax] = S[slab_ix(C_POS + ax, i)]; c[C_LVEL + ax] = S[slab_ix(C_LVEL + ax, i)]; }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NLOAD; k++) c[k] = S[slab_ix(k, i)];
-        }
-        T was[ELIDE ? C_MASS : 1];          // the state as loaded, to tell which components the launch changed
-        if constexpr (ELIDE) {
-#pragma unroll
-            for (int k = 0; k < C_MASS; k++) was[k] = c[k];
-        }
-        T bx, bz, bs;
-        if (P.bp_check) { bx = S[slab_ix(C_BPX, i)]; bz = S[slab_ix(C_BPZ, i)]; bs = S[slab_ix(C_BPSAFE, i)]; }
-        T f[6];
-        if (EXT) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) f[k] = S[slab_ix(C_FORCE + k, i)];
-        }
-        // P.ticks ticks with the state in registers: one read and one write of the state per launch, not per tick
-        for (int s = 0; s < nticks; s++) {
-            if (P.bp_check && ((P.bp_check & BPC_ALL) || (s == 0 && (P.bp_check & BPC_FIRST)) ||
-                               (s == nticks - 1 && (P.bp_check & BPC_LAST)))) {
-                // dSpaceCollide for body-body pairs, by proof: a body inside its safe zone cannot touch any other
-                int z = zone_state(c[C_POS] - bx, c[C_POS + 2] - bz, bs);
-                if (P.n_static > 0) {
-                    const int z2 = static_state(P, c[C_POS], c[C_POS + 1], c[C_POS + 2], S[slab_ix(C_BPR, i)]);
-                    z = z2 > z ? z2 : z;
-                }
-                report_zone(z, P.bp_flags);
-            }
-            V3<T> x = { c[C_POS], c[C_POS + 1], c[C_POS + 2] };
-            Q4<T> q = { c[C_QUAT], c[C_QUAT + 1], c[C_QUAT + 2], c[C_QUAT + 3] };
-            V3<T> v = { c[C_LVEL], c[C_LVEL + 1], c[C_LVEL + 2] };
-            V3<T> w = { c[C_AVEL], c[C_AVEL + 1], c[C_AVEL + 2] };
-            T mass;
-            V3<T> Ib;
-            if constexpr (UNI) { mass = P.uni_mass; Ib = P.uni_inertia; }
-            else { mass = c[C_MASS]; Ib = { c[C_INERTIA], c[C_INERTIA + 1], c[C_INERTIA + 2] }; }
-            V3<T> facc = { T(0), T(0), T(0) }, tacc = { T(0), T(0), T(0) };
-            if (EXT && s == 0) {                       // the accumulators act in the first tick and are cleared by it
-                facc = { f[0], f[1], f[2] };
-                tacc = { f[3], f[4], f[5] };
-            }
-            if constexpr (UNI) {
-                // what the tick makes of the launch's constants alone arrives with them (dmx_launch_consts.hpp: the quotients;
-                // dmx_torque_free.hpp: hm and m g): nothing here divides, and nothing is left to compute ahead of the loop
-                const TickGiven<T, EXT> K = { { lc.inv_Ib[0], lc.inv_Ib[1], lc.inv_Ib[2] }, lc.iso != 0, lc.inv_h, tf.hm, mass,
-                                              { tf.mg[0], tf.mg[1], tf.mg[2] } };
-                if constexpr (TF) {
-                    // the short tick for a wavefront whose every active lane it is proven for, the general one for any other
-                    free_body_step_torque_free(x, q, v, w, Ib, P.g, P.h, P.gyro, tf.on, K);
-                } else {
-                    free_body_step_with(x, q, v, w, Ib, facc, tacc, P.g, P.h, P.gyro, K);
-                }
-            } else {
-                free_body_step(x, q, v, w, mass, Ib, facc, tacc, P.g, P.h, P.gyro);
-            }
-            if (s == nticks - 1) pack_boundary(P, i, x, q, v, w);
-            c[C_POS] = x.x; c[C_POS + 1] = x.y; c[C_POS + 2] = x.z;
-            c[C_QUAT] = q.w; c[C_QUAT + 1] = q.x; c[C_QUAT + 2] = q.y; c[C_QUAT + 3] = q.z;
-            c[C_LVEL] = v.x; c[C_LVEL + 1] = v.y; c[C_LVEL + 2] = v.z;
-            c[C_AVEL] = w.x; c[C_AVEL + 1] = w.y; c[C_AVEL + 2] = w.z;
-        }
-        if constexpr (FIX) {
-            uint32_t moved = 0;             // axes on which some lane's pos or lvel changed its bits in this tick
-#pragma unroll
-            for (int k = 0; k < C_MASS; k++) {
-                const int ax = fix_axis_of(k);
-                if (ax >= 0 && (fixed & (1u << ax))) continue;      // proven fixed and not loaded: nothing to test, nothing to write
-                if (in_place || ax >= 0) {
-                    const bool changed = __ballot(bits_differ(c[k], was[k])) != 0ull;
-                    if (ax >= 0 && changed) moved |= 1u << ax;
-                    if (in_place && !changed) continue;
-                }
-                store_state(&So[slab_ix(k, i)], c[k]);
-            }
-            // what this launch observed: an establishing launch writes every tile's word, a lean one only a word that changes
-            // (an axis it did not load keeps its bit: same inputs, same bits)
-            const uint32_t word = ~moved & 7u;
-            if ((fix_mode != FIX_LEAN || word != seen) && (threadIdx.x & 63) == 0) fix_words[i >> 6] = word;
-        } else {
-#pragma unroll
-        for (int k = 0; k < C_MASS; k++) {
-            if constexpr (ELIDE) if (in_place) {
-                if (__ballot(bits_differ(c[k], was[k])) == 0ull) continue;      // all 64 bodies keep this component's bits: nothing to write
-            }
-            store_state(&So[slab_ix(k, i)], c[k]);       // (dmx_internal.hpp: the state leaves with the store policy's cache bit)
-        }
-        }
-        if (EXT) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) S[slab_ix(C_FORCE + k, i)] = T(0);
-        }
+#include "dmx_free_tile.inc"
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// integrate_free_lean: the lean launch (FIX_LEAN) of integrate_free<T, false, MWU, false, 3, true, true> as a kernel of its own,
+// for launches the host already knows to be lean, in place, one tick, with the constants as arguments and the short tick on
+// (launch_step has the rule).  What such a launch's wavefront needs stands in LeanHot (dmx_lean_tick.hpp) at the head of the
+// arguments; the kernel asks for nothing else ahead of its loads -- neither StepParams nor the dispatch packet -- has no grid-stride
+// loop (one tile per wavefront: launch_step's grid covers every tile) and tests nothing the host has decided.
+//   Straight line: a wavefront whose word has both lateral bits set and whose active lanes all pass torque_free_admits.  The word's
+//   load first, the nine loads behind it, lean_tick, nine ballots with the elided stores, and the word rewritten if its y bit changes.
+//   Any other wavefront -- a clear lateral axis, a lane that fails the guard -- runs dmx_free_tile.inc, the very body of the
+//   kernel this one stands in for, from its own loads on: nothing has been stored by then.
+// Same bits either way (tests/test_lean_tick.py on the host, tests/test_gpu_lean_kernel.py on the device).  64-bit indexing as
+// everywhere.  No launch bound beyond the workgroup's size (profiles/lean_kernel_resources.txt has the candidate with one).
+// ---------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256) void integrate_free_lean(LeanHot<T> A, StepParams<T> P, TorqueFree<T> tf, LaunchConsts<T> lc)
+{
+    const int64_t i = sweep_block(blockIdx.x, A.g8, A.rev) * (int64_t)256 + threadIdx.x;
+    if (i >= A.n) return;
+    T *t = A.S + slab_ix(0, i);         // component k of body i is t[k * SLAB_TILE]
+    const uint32_t word = A.fix_words[__builtin_amdgcn_readfirstlane((int)(i >> 6))];
+    // pos.y, quat, lvel.y, avel
+    constexpr int NK = 9;
+    constexpr int comp[NK] = { C_POS + 1, C_QUAT, C_QUAT + 1, C_QUAT + 2, C_QUAT + 3, C_LVEL + 1, C_AVEL, C_AVEL + 1, C_AVEL + 2 };
+    T was[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) was[k] = t[comp[k] * SLAB_TILE];
+    const uint32_t seen = __builtin_amdgcn_readfirstlane(word);
+    Q4<T> q = { was[1], was[2], was[3], was[4] };
+    if ((seen & 5u) != 5u || __ballot(!torque_free_admits(q)) != 0ull) {
+        // the tile as integrate_free<T, false, MWU, false, 3, true, true> steps it in a lean launch in place: the fragment's names
+        constexpr bool EXT = false, FIX = true, TF = true, ELIDE = true, UNI = true, in_place = true;
+        constexpr int NLOAD = C_MASS, fix_mode = FIX_LEAN, nticks = 1;
+        T *const S = A.S, *const So = A.S;
+        uint32_t *const fix_words = A.fix_words;
+        do {        // (a `continue` of the fragment leaves the tile)
+#include "dmx_free_tile.inc"
+        } while (false);
+        return;
+    }
+    T xy = was[0], vy = was[5];
+    V3<T> w = { was[6], was[7], was[8] };
+    lean_tick(xy, q, vy, w, A.hm, A.mgy, A.h);
+    const T now[NK] = { xy, q.w, q.x, q.y, q.z, vy, w.x, w.y, w.z };
+    uint32_t moved = 0;             // bit 1: some lane's pos.y or lvel.y changed its bits in this tick
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const bool changed = __ballot(bits_differ(now[k], was[k])) != 0ull;
+        if (fix_axis_of(comp[k]) == 1 && changed) moved |= 2u;
+        if (!changed) continue;
+        store_state(&t[comp[k] * SLAB_TILE], now[k]);
+    }
+    // (the lateral axes were not loaded and keep their bits: same inputs, same bits)
+    const uint32_t neww = ~moved & 7u;
+    if (neww != seen && (threadIdx.x & 63) == 0) A.fix_words[i >> 6] = neww;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -596,7 +542,8 @@ constexpr int64_t kOneLaunchBodies = 256 * 4 * 64;
 
 template <class T>
 hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_t n, const StepParams<T> &P, bool ext,
-                       StepDiag *diag, hipStream_t st, int rev, int fix_mode, uint32_t *fix_words, bool torque_free, int64_t *tf_stats)
+                       StepDiag *diag, hipStream_t st, int rev, int fix_mode, uint32_t *fix_words, bool torque_free, int64_t *tf_stats,
+                       bool lean_kernel, int64_t *lk_stats)
 {
     if (P.n_static > 0 && P.sbuf != nullptr) {
         // bodies at static geometry: narrowphase against the plane and the static boxes, then the fused solve + integrate
@@ -655,19 +602,31 @@ hipError_t launch_step(T *S, T *So, const uint8_t *gtype, int64_t stride, int64_
             if (P.ticks > 1 || ext || !(opt & OPT_ELIDE) || fix_words == nullptr || P.skip != nullptr || P.gate != nullptr) return hipErrorInvalidValue;
             // a lean launch has not loaded every pos.x / pos.z: it cannot fill another slab, test safe zones or pack the boundary
             if (fix_mode == FIX_LEAN && (So != S || P.bp_check != 0 || P.pack_out != nullptr)) return hipErrorInvalidValue;
-            if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, true, true>);
+            // A lean launch with the constants as arguments and the short tick on -- all decided above -- is the straight-line kernel
+            // (integrate_free_lean), unless the batch's switch is off: what a wavefront of it reads ahead of its loads is LeanHot alone.
+            // The refusals above hold for it as they stand: in place, one tick, no accumulators, no zones, no pack, no gate, no skip mask.
+            const bool lean = lean_kernel && fix_mode == FIX_LEAN && opt == 3 && tf.on;
+            if (lk_stats != nullptr) lk_stats[lean ? 0 : 1]++;
+            if (lean) {
+                const LeanHot<T> hot = { n, grid, rev & 1, S, fix_words, P.h, tf.hm, tf.mg[1] };
+                hipLaunchKernelGGL((integrate_free_lean<T>), dim3(grid), dim3(256), 0, st, hot, P, tf, lc);
+            }
+            else if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, true, true>);
             else if (opt == 3) launch(integrate_free<T, false, MWU, false, 3, true>);
             else launch(integrate_free<T, false, MWU, false, 1, true>);
         } else if (P.ticks > 1) {
+            if (lk_stats != nullptr) lk_stats[1]++;
             if ((opt & OPT_UNI) && tf.on) launch(integrate_free<T, false, 1, true, OPT_UNI, false, true>);
             else if (opt & OPT_UNI) launch(integrate_free<T, false, 1, true, OPT_UNI>);
             else launch(integrate_free<T, false, 1, true, 0>);
         } else if (ext) {
+            if (lk_stats != nullptr) lk_stats[1]++;
             if (opt == 3) launch(integrate_free<T, true, 1, false, 3>);
             else if (opt == 2) launch(integrate_free<T, true, 1, false, 2>);
             else if (opt == 1) launch(integrate_free<T, true, 1, false, 1>);
             else launch(integrate_free<T, true, 1, false, 0>);
         } else {
+            if (lk_stats != nullptr) lk_stats[1]++;
             if (opt == 3 && tf.on) launch(integrate_free<T, false, MWU, false, 3, false, true>);
             else if (opt == 2 && tf.on) launch(integrate_free<T, false, MWU, false, 2, false, true>);
             else if (opt == 3) launch(integrate_free<T, false, MWU, false, 3>);
@@ -773,7 +732,7 @@ hipError_t launch_soa_to_aos(const T *S, int64_t stride, int comp0, int k, int64
 
 #define DMX_INSTANTIATE(T)                                                                                         \
     template hipError_t launch_step<T>(T *, T *, const uint8_t *, int64_t, int64_t, const StepParams<T> &, bool,   \
-                                       StepDiag *, hipStream_t, int, int, uint32_t *, bool, int64_t *);                                      \
+                                       StepDiag *, hipStream_t, int, int, uint32_t *, bool, int64_t *, bool, int64_t *);                                   \
     template hipError_t launch_pack_transforms<T>(const T *, int64_t, int64_t, int64_t, T *, hipStream_t);         \
     template hipError_t launch_gather<T>(const T *, int64_t, const int32_t *, int64_t, T *, hipStream_t);          \
     template hipError_t launch_scatter<T>(T *, int64_t, const int32_t *, int64_t, const T *, hipStream_t);         \
@@ -803,6 +762,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
         touch((const void *)&integrate_free<float, false, 7, false, 3, true>);
         touch((const void *)&integrate_free<float, false, 7, false, 3, false, true>);
         touch((const void *)&integrate_free<float, false, 7, false, 3, true, true>);
+        touch((const void *)&integrate_free_lean<float>);
         touch((const void *)&step_plane<float, false, 2, 4>);
         touch((const void *)&step_contacts<float, false, 1, 8, true>);
         touch((const void *)&check_zones<float>);
@@ -813,6 +773,7 @@ hipError_t dmx_touch_kernels(int real_bytes)
         touch((const void *)&integrate_free<double, false, 1, false, 3, true>);
         touch((const void *)&integrate_free<double, false, 1, false, 3, false, true>);
         touch((const void *)&integrate_free<double, false, 1, false, 3, true, true>);
+        touch((const void *)&integrate_free_lean<double>);
         touch((const void *)&step_plane<double, false, 1, 4>);
         touch((const void *)&step_contacts<double, false, 1, 8, true>);
         touch((const void *)&check_zones<double>);

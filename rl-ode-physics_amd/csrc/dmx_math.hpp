@@ -209,11 +209,16 @@ template <class T> DMX_HD void integrate_quat(Q4<T> &q, const V3<T> &w, T h)
 
 // The last statements of every body's tick: v += hm f ; w += dw ; x += h v ; q += h/2 (0,w) q, renormalised.  The general tick
 // (dmx_step_fused.hpp: tick_tail) comes here with hm = h * (1 / m), f = the force accumulator and dw = Iw^-1 (h tacc).
+// Its pieces, one axis or one vector at a time (dmx_lean_tick.hpp composes the tick of a tile whose lateral axes are not even
+// loaded from them): an axis of v, all of w, an axis of x.
+template <class T> DMX_HD void tick_kick_axis(T &vk, T hm, T fk) { vk = fma_(hm, fk, vk); }
+template <class T> DMX_HD void tick_turn(V3<T> &w, const V3<T> &dw) { w.x += dw.x; w.y += dw.y; w.z += dw.z; }
+template <class T> DMX_HD void tick_drift_axis(T &xk, T h, T vk) { xk = fma_(h, vk, xk); }
 template <class T> DMX_HD void tick_integrate(V3<T> &x, Q4<T> &q, V3<T> &v, V3<T> &w, T hm, const V3<T> &f, const V3<T> &dw, T h)
 {
-    v.x = fma_(hm, f.x, v.x); v.y = fma_(hm, f.y, v.y); v.z = fma_(hm, f.z, v.z);
-    w.x += dw.x; w.y += dw.y; w.z += dw.z;
-    x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
+    tick_kick_axis(v.x, hm, f.x); tick_kick_axis(v.y, hm, f.y); tick_kick_axis(v.z, hm, f.z);
+    tick_turn(w, dw);
+    tick_drift_axis(x.x, h, v.x); tick_drift_axis(x.y, h, v.y); tick_drift_axis(x.z, h, v.z);
     integrate_quat(q, w, h);
 }
 // The tick of a body without rows and without torque (dmx_torque_free.hpp has the rule and the proof): hm = h * (1 / m) and
