@@ -588,6 +588,46 @@ int dmxBatchDownloadBodyFlags(dmxBatchID b, uint8_t *flags_out, int64_t first, i
 int dmxBatchIdleCounters(dmxBatchID b, int32_t *steps_left, double *time_left);
 int dmxBatchAutoDisableStats(dmxBatchID b, int64_t out[4]);
 
+/* ---- damping, maximum angular speed, contact correction (dmxBatchStepJoints only; all four are no-ops at their defaults, ODE's)
+ * The rules are this library's definitions, written from ODE as recalled [ODE-recall dWorldSetDamping, dBodySetMaxAngularSpeed,
+ * dWorldSetContactSurfaceLayer, dWorldSetContactMaxCorrectingVel]; the deliberate differences are named.
+ * Per-slot table, one dmxBodyDamping per slot: lin_scale, ang_scale in [0, 1]; lin_threshold, ang_threshold >= 0 (m/s, rad/s);
+ * max_angular_speed > 0 or +inf.  Anything else is DMX_EINVAL with nothing changed.  Defaults [ODE-recall]: 0, 0, 0.01, 0.01, +inf.
+ * The table lives on the device in the batch's precision and is allocated by the first call that sets a non-default value; a
+ * batch that never made one stages, launches and loads exactly what it does without this section.
+ * Damping: at the start of a tick, after the islands are formed and the auto-disable wake rule has run, for every slot the tick
+ * steps that is ALIVE and not KINEMATIC, on the pre-tick velocities, in the batch's precision:
+ *     if lin_scale != 0 and lvel.lvel > lin_threshold^2:  lvel *= (1 - lin_scale)
+ *     if ang_scale != 0 and avel.avel > ang_threshold^2:  avel *= (1 - ang_scale)
+ * threshold^2 and 1 - scale are formed in the batch's precision (as the auto-disable thresholds are squared); the comparison is
+ * strict.  Gravity, the gyroscopic torque, the rows' right-hand sides and the bounce rule all see the damped velocities.
+ * Differences from ODE: ODE damps kinematic bodies too -- this library does not, a kinematic body keeps its velocities (above);
+ * and the slots of islands left asleep are not damped: they keep their bits, like everything else of theirs.
+ * Maximum angular speed: in the integrator, after the velocity update and before the pose update, for a non-kinematic slot:
+ *     if avel.avel > max^2:  avel *= max / sqrt(avel.avel)
+ * The quaternion advances with the capped avel.  With max = +inf the test is never true.
+ * Contact surface layer and maximum correcting velocity: two scalars of the batch, surface_layer >= 0 (metres) and
+ * max_correcting_vel > 0 or +inf (m/s), defaults 0 and +inf.  They act on the normal row of every contact joint of the tick:
+ *     depth = max(depth - surface_layer, 0)
+ *     c = (erp / h) * depth
+ *     if c > max_correcting_vel:  c = max_correcting_vel
+ *     then the bounce rule as always  (c = max(c, -bounce * outgoing))
+ * The clamp sits between the push-out and the bounce: a bounce may exceed it, as in ODE.  Articulation rows and friction rows are
+ * untouched.  At the defaults the arithmetic is depth - 0 and a comparison with +inf: bit-identical to a library without them.
+ * Refused by the ticks that find their own contacts -- dmxBatchStep, dmxBatchStepTimed, dmxBatchStepRange, dmxBatchChunkTick,
+ * dmxBatchChunkTicks, dmxBatchExactTick -- whose fused kernels know none of this: while the table holds a non-default entry in
+ * [0, active count), or a contact scalar is not at its default, they return DMX_EINVAL, say so in one line on stderr and leave
+ * the state untouched.  Nothing is silently ignored.
+ * dmxBatchSetDamping / dmxBatchSetMaxAngularSpeed: every slot's four damping values / maximum speed; the other fields stand.
+ * dmxBatchDownloadBodyDamping returns the defaults while no table has been made. */
+typedef struct dmxBodyDamping { double lin_scale, ang_scale, lin_threshold, ang_threshold, max_angular_speed; } dmxBodyDamping;
+int dmxBatchSetDamping(dmxBatchID b, double lin_scale, double ang_scale, double lin_threshold, double ang_threshold);
+int dmxBatchSetMaxAngularSpeed(dmxBatchID b, double max_speed);
+int dmxBatchUploadBodyDamping(dmxBatchID b, const dmxBodyDamping *damping, int64_t first, int64_t count);
+int dmxBatchDownloadBodyDamping(dmxBatchID b, dmxBodyDamping *out, int64_t first, int64_t count);
+int dmxBatchSetContactCorrection(dmxBatchID b, double surface_layer, double max_correcting_vel);
+int dmxBatchGetContactCorrection(dmxBatchID b, double *surface_layer, double *max_correcting_vel);
+
 /* ---- diagnostics of the last step */
 int dmxBatchLastContactCount(dmxBatchID b, int64_t *n);       /* contact joints created in the last tick */
 int dmxBatchLastResidual(dmxBatchID b, double *r);            /* sum |delta lambda| of the last SOR sweep */

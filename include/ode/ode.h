@@ -126,6 +126,26 @@ void dWorldSetAutoDisableTime(dWorldID, dReal time);
 dReal dWorldGetAutoDisableTime(dWorldID);
 void dWorldSetAutoDisableAverageSamplesCount(dWorldID, unsigned int average_samples_count);   /* 1 only */
 int  dWorldGetAutoDisableAverageSamplesCount(dWorldID);
+/* damping, maximum angular speed and the contact correction scalars (include/dmx_batch.h, "damping"): all no-ops at their defaults,
+ * scale 0, thresholds 0.01, maximum speed dInfinity, layer 0, maximum correcting velocity dInfinity.  The world's damping values
+ * and maximum angular speed are what dBodyCreate copies into a new body; bodies that exist keep theirs.  A value out of range
+ * (a scale outside [0, 1], a negative threshold or layer, a maximum that is not positive) is ignored with one line on stderr.
+ * Unlike stock ODE, kinematic bodies are not damped. */
+void dWorldSetLinearDamping(dWorldID, dReal scale);
+dReal dWorldGetLinearDamping(dWorldID);
+void dWorldSetAngularDamping(dWorldID, dReal scale);
+dReal dWorldGetAngularDamping(dWorldID);
+void dWorldSetDamping(dWorldID, dReal linear_scale, dReal angular_scale);
+void dWorldSetLinearDampingThreshold(dWorldID, dReal threshold);
+dReal dWorldGetLinearDampingThreshold(dWorldID);
+void dWorldSetAngularDampingThreshold(dWorldID, dReal threshold);
+dReal dWorldGetAngularDampingThreshold(dWorldID);
+void dWorldSetMaxAngularSpeed(dWorldID, dReal max_speed);
+dReal dWorldGetMaxAngularSpeed(dWorldID);
+void dWorldSetContactSurfaceLayer(dWorldID, dReal depth);
+dReal dWorldGetContactSurfaceLayer(dWorldID);
+void dWorldSetContactMaxCorrectingVel(dWorldID, dReal vel);
+dReal dWorldGetContactMaxCorrectingVel(dWorldID);
 int  dWorldStep(dWorldID, dReal stepsize);                       /* main.c:213 */
 int  dWorldQuickStep(dWorldID, dReal stepsize);
 
@@ -151,6 +171,18 @@ void dBodySetAutoDisableDefaults(dBodyID);                       /* the world's 
 void dBodyEnable(dBodyID);                                       /* wakes the body and resets its idle counters */
 void dBodyDisable(dBodyID);                                      /* asleep from the next step on, velocities as they are */
 int  dBodyIsEnabled(dBodyID);
+void dBodySetLinearDamping(dBodyID, dReal scale);
+dReal dBodyGetLinearDamping(dBodyID);
+void dBodySetAngularDamping(dBodyID, dReal scale);
+dReal dBodyGetAngularDamping(dBodyID);
+void dBodySetDamping(dBodyID, dReal linear_scale, dReal angular_scale);
+void dBodySetLinearDampingThreshold(dBodyID, dReal threshold);
+dReal dBodyGetLinearDampingThreshold(dBodyID);
+void dBodySetAngularDampingThreshold(dBodyID, dReal threshold);
+dReal dBodyGetAngularDampingThreshold(dBodyID);
+void dBodySetMaxAngularSpeed(dBodyID, dReal max_speed);
+dReal dBodyGetMaxAngularSpeed(dBodyID);
+void dBodySetDampingDefaults(dBodyID);                           /* the world's five values */
 void dBodyAddForce(dBodyID, dReal fx, dReal fy, dReal fz);       /* main.c:532 (commented out there) */
 void dBodyAddTorque(dBodyID, dReal fx, dReal fy, dReal fz);
 void dBodySetMass(dBodyID, const dMass *mass);

@@ -30,6 +30,8 @@ BATCH_SYMBOLS = [
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
     "dmxBatchSetFeedback", "dmxBatchJointFeedback", "dmxBatchContactFeedback", "dmxBatchFeedbackDevice",
     "dmxBatchSetAutoDisable", "dmxBatchGetAutoDisable", "dmxBatchDownloadBodyFlags", "dmxBatchIdleCounters", "dmxBatchAutoDisableStats",
+    "dmxBatchSetDamping", "dmxBatchSetMaxAngularSpeed", "dmxBatchUploadBodyDamping", "dmxBatchDownloadBodyDamping",
+    "dmxBatchSetContactCorrection", "dmxBatchGetContactCorrection",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
 
@@ -158,5 +160,11 @@ def load():
     sig("dmxBatchDownloadBodyFlags", I, P, P, L, L)
     sig("dmxBatchIdleCounters", I, P, P, P)
     sig("dmxBatchAutoDisableStats", I, P, P)
+    sig("dmxBatchSetDamping", I, P, D, D, D, D)
+    sig("dmxBatchSetMaxAngularSpeed", I, P, D)
+    sig("dmxBatchUploadBodyDamping", I, P, P, L, L)
+    sig("dmxBatchDownloadBodyDamping", I, P, P, L, L)
+    sig("dmxBatchSetContactCorrection", I, P, D, D)
+    sig("dmxBatchGetContactCorrection", I, P, C.POINTER(D), C.POINTER(D))
     _lib = lib
     return lib

@@ -24,6 +24,9 @@ ORDER_CREATION, ORDER_ODE = 0, 1
 BODY_ALIVE, BODY_KINEMATIC, BODY_NOGRAVITY, BODY_NOGYRO = 1, 2, 4, 8
 BODY_AUTODISABLE, BODY_DISABLED = 16, 32      # auto-disable: may fall asleep by itself / is asleep
 AUTO_DISABLE_STATS = ("asleep", "islands_skipped", "slept", "woken")
+# dmxBodyDamping (include/dmx_batch.h): five doubles per slot; the defaults are 0, 0, 0.01, 0.01, inf
+BODY_DAMPING_DTYPE = np.dtype([("lin_scale", "<f8"), ("ang_scale", "<f8"), ("lin_threshold", "<f8"), ("ang_threshold", "<f8"),
+                               ("max_angular_speed", "<f8")])
 CONTACT_SOFT_ERP, CONTACT_SOFT_CFM = 0x008, 0x010
 CONTACT_APPROX1_1, CONTACT_APPROX1_2, CONTACT_APPROX1 = 0x1000, 0x2000, 0x3000      # friction bounded by mu times the normal force
 # dmxContactJoint (include/dmx_batch.h): the C layout, padding included (tests/test_solver_dense.py checks it with offsetof)
@@ -366,6 +369,40 @@ class BatchWorld:
         out = (C.c_int64 * 4)()
         _check(self.lib.dmxBatchAutoDisableStats(self.h, out), "dmxBatchAutoDisableStats")
         return dict(zip(AUTO_DISABLE_STATS, out))
+
+    # -- damping, maximum angular speed, contact correction (include/dmx_batch.h, "damping"); step_joints only --
+    def set_damping(self, lin_scale=0.0, ang_scale=0.0, lin_threshold=0.01, ang_threshold=0.01):
+        """every slot's damping: velocities above the threshold are scaled by 1 - scale at the start of a tick"""
+        _check(self.lib.dmxBatchSetDamping(self.h, float(lin_scale), float(ang_scale), float(lin_threshold), float(ang_threshold)),
+               "dmxBatchSetDamping")
+
+    def set_max_angular_speed(self, max_speed=float("inf")):
+        """every slot's cap on |avel| (rad/s), applied by the integrator before the pose update"""
+        _check(self.lib.dmxBatchSetMaxAngularSpeed(self.h, float(max_speed)), "dmxBatchSetMaxAngularSpeed")
+
+    def upload_body_damping(self, table, first=0):
+        """table: [k] BODY_DAMPING_DTYPE (or [k, 5] numbers in its field order) for slots first .. first + k - 1"""
+        t = np.asarray(table)
+        if t.dtype != BODY_DAMPING_DTYPE:
+            t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 5).view(BODY_DAMPING_DTYPE).reshape(-1)
+        t = np.ascontiguousarray(t)
+        _check(self.lib.dmxBatchUploadBodyDamping(self.h, t.ctypes.data, int(first), t.shape[0]), "dmxBatchUploadBodyDamping")
+
+    def body_damping(self):
+        """-> [n] BODY_DAMPING_DTYPE (the defaults while no value has been set)"""
+        out = np.zeros(self.n, BODY_DAMPING_DTYPE)
+        _check(self.lib.dmxBatchDownloadBodyDamping(self.h, out.ctypes.data, 0, self.n), "dmxBatchDownloadBodyDamping")
+        return out
+
+    def set_contact_correction(self, surface_layer=0.0, max_correcting_vel=float("inf")):
+        """depth the contacts may keep (m) and the cap on a contact's push-out velocity (m/s); a bounce may exceed the cap"""
+        _check(self.lib.dmxBatchSetContactCorrection(self.h, float(surface_layer), float(max_correcting_vel)), "dmxBatchSetContactCorrection")
+
+    def contact_correction(self):
+        """-> (surface_layer, max_correcting_vel)"""
+        a, b = C.c_double(), C.c_double()
+        _check(self.lib.dmxBatchGetContactCorrection(self.h, C.byref(a), C.byref(b)), "dmxBatchGetContactCorrection")
+        return a.value, b.value
 
     def set_row_order(self, order, seed=0):
         """ORDER_CREATION (default) / ORDER_ODE: the order QuickStep sweeps an island's rows in"""

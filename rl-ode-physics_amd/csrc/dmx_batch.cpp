@@ -185,6 +185,7 @@ extern "C" int dmxBatchDestroy(dmxBatchID b)
     }
     if (b->sm_mirror) (void)hipHostFree(b->sm_mirror);
     if (b->sm_diag) (void)hipFree(b->sm_diag);
+    if (b->damp_dev) (void)hipFree(b->damp_dev);
     if (b->ad_steps_dev) (void)hipFree(b->ad_steps_dev);
     if (b->ad_time_dev) (void)hipFree(b->ad_time_dev);
     if (b->ad_mirror) (void)hipHostFree(b->ad_mirror);
@@ -509,6 +510,114 @@ extern "C" int dmxBatchAutoDisableStats(dmxBatchID b, int64_t out[4])
     return DMX_OK;
 }
 
+// ---- damping, angular speed cap, contact correction (include/dmx_batch.h) ------------------------------------------------------
+static bool damp_is_default(const dmxBodyDamping &d)
+{
+    return d.lin_scale == 0 && d.ang_scale == 0 && d.lin_threshold == 0.01 && d.ang_threshold == 0.01 && d.max_angular_speed == __builtin_huge_val();
+}
+static bool damp_is_valid(const dmxBodyDamping &d)
+{
+    return d.lin_scale >= 0 && d.lin_scale <= 1 && d.ang_scale >= 0 && d.ang_scale <= 1 && d.lin_threshold >= 0 && d.ang_threshold >= 0 &&
+           d.max_angular_speed > 0;
+}
+static const dmxBodyDamping kDampDefault = { 0.0, 0.0, 0.01, 0.01, __builtin_huge_val() };
+
+void dmx_damp_recount(dmxBatch *b)
+{
+    b->damp_n_set = b->damp_n_scaled = b->damp_n_capped = 0;
+    for (size_t s = 0; s < b->h_damp.size(); s++) {
+        const dmxBodyDamping &d = b->h_damp[s];
+        if ((int64_t)s < b->n_active && !damp_is_default(d)) b->damp_n_set++;
+        if (d.lin_scale != 0 || d.ang_scale != 0) b->damp_n_scaled++;
+        if (d.max_angular_speed != __builtin_huge_val()) b->damp_n_capped++;
+    }
+}
+
+// h_damp[first, first + count) -> the device, in the batch's precision (the table is made, all defaults, on first use)
+static int damp_push(dmxBatch *b, int64_t first, int64_t count)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    const bool fresh = !b->damp_dev;
+    if (fresh) {
+        HIP_TRY(hipMalloc(&b->damp_dev, (size_t)b->stride * DAMP_REALS * b->rsize));
+        first = 0; count = b->n;
+    }
+    const size_t lo = fresh ? 0 : (size_t)first, m = fresh ? (size_t)b->stride : (size_t)count;       // (a fresh table: the pad slots too)
+    std::vector<char> tmp(m * DAMP_REALS * b->rsize);
+    for (size_t k = 0; k < m; k++) {
+        const dmxBodyDamping &d = lo + k < b->h_damp.size() ? b->h_damp[lo + k] : kDampDefault;
+        const double v[DAMP_REALS] = { d.lin_scale, d.ang_scale, d.lin_threshold, d.ang_threshold, d.max_angular_speed };
+        for (int c = 0; c < DAMP_REALS; c++) {
+            if (b->precision == DMX_F32) ((float *)tmp.data())[k * DAMP_REALS + c] = (float)v[c];
+            else ((double *)tmp.data())[k * DAMP_REALS + c] = v[c];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync((char *)b->damp_dev + lo * DAMP_REALS * b->rsize, tmp.data(), tmp.size(), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    dmx_damp_recount(b);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchUploadBodyDamping(dmxBatchID b, const dmxBodyDamping *damping, int64_t first, int64_t count)
+{
+    if (!b || first < 0 || count < 0 || first + count > b->n || (count > 0 && !damping)) return DMX_EINVAL;
+    bool all_default = true;
+    for (int64_t i = 0; i < count; i++) {
+        if (!damp_is_valid(damping[i])) return DMX_EINVAL;
+        if (!damp_is_default(damping[i])) all_default = false;
+    }
+    SETTLE(b);
+    if (count == 0 || (b->h_damp.empty() && all_default)) return DMX_OK;      // (no table yet, and none needed)
+    if (b->h_damp.empty()) b->h_damp.assign((size_t)b->n, kDampDefault);
+    for (int64_t i = 0; i < count; i++) b->h_damp[(size_t)(first + i)] = damping[i];
+    return damp_push(b, first, count);
+}
+
+extern "C" int dmxBatchDownloadBodyDamping(dmxBatchID b, dmxBodyDamping *out, int64_t first, int64_t count)
+{
+    if (!b || first < 0 || count < 0 || first + count > b->n || (count > 0 && !out)) return DMX_EINVAL;
+    for (int64_t i = 0; i < count; i++) out[i] = b->h_damp.empty() ? kDampDefault : b->h_damp[(size_t)(first + i)];
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchSetDamping(dmxBatchID b, double lin_scale, double ang_scale, double lin_threshold, double ang_threshold)
+{
+    if (!b) return DMX_EINVAL;
+    const dmxBodyDamping d = { lin_scale, ang_scale, lin_threshold, ang_threshold, __builtin_huge_val() };
+    if (!damp_is_valid(d)) return DMX_EINVAL;
+    SETTLE(b);
+    if (b->h_damp.empty() && damp_is_default(d)) return DMX_OK;
+    if (b->h_damp.empty()) b->h_damp.assign((size_t)b->n, kDampDefault);
+    for (dmxBodyDamping &e : b->h_damp) { e.lin_scale = lin_scale; e.ang_scale = ang_scale; e.lin_threshold = lin_threshold; e.ang_threshold = ang_threshold; }
+    return damp_push(b, 0, b->n);
+}
+
+extern "C" int dmxBatchSetMaxAngularSpeed(dmxBatchID b, double max_speed)
+{
+    if (!b || !(max_speed > 0)) return DMX_EINVAL;
+    SETTLE(b);
+    if (b->h_damp.empty() && max_speed == __builtin_huge_val()) return DMX_OK;
+    if (b->h_damp.empty()) b->h_damp.assign((size_t)b->n, kDampDefault);
+    for (dmxBodyDamping &e : b->h_damp) e.max_angular_speed = max_speed;
+    return damp_push(b, 0, b->n);
+}
+
+extern "C" int dmxBatchSetContactCorrection(dmxBatchID b, double surface_layer, double max_correcting_vel)
+{
+    if (!b || !(surface_layer >= 0) || !(surface_layer < __builtin_huge_val()) || !(max_correcting_vel > 0)) return DMX_EINVAL;
+    SETTLE(b);
+    b->surface_layer = surface_layer; b->max_corr_vel = max_correcting_vel;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchGetContactCorrection(dmxBatchID b, double *surface_layer, double *max_correcting_vel)
+{
+    if (!b) return DMX_EINVAL;
+    if (surface_layer) *surface_layer = b->surface_layer;
+    if (max_correcting_vel) *max_correcting_vel = b->max_corr_vel;
+    return DMX_OK;
+}
+
 int dmx_ensure_dev(dmxBatch::DevBuf &d, size_t bytes)
 {
     if (bytes <= d.bytes) return DMX_OK;
@@ -564,6 +673,7 @@ extern "C" int dmxBatchStep(dmxBatchID b, double h, int nsteps)
     if (dmx_refuse_joints(b, "dmxBatchStep")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStep")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchStep")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchStep")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -834,6 +944,7 @@ extern "C" int dmxBatchChunkTick(dmxBatchID b, double h, int check)
     if (dmx_refuse_joints(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchChunkTick")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchChunkTick")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -845,6 +956,7 @@ extern "C" int dmxBatchChunkTicks(dmxBatchID b, double h, int nticks, int check_
     if (dmx_refuse_joints(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchChunkTicks")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
     dmx_state_stepped(b);
@@ -907,6 +1019,7 @@ extern "C" int dmxBatchExactTick(dmxBatchID b, double h)
     if (dmx_refuse_joints(b, "dmxBatchExactTick")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchExactTick")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchExactTick")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchExactTick")) return DMX_EINVAL;
     SETTLE(b);
     HIP_TRY(hipSetDevice(b->device));
     dmx_note_capture(b);
@@ -1003,6 +1116,7 @@ extern "C" int dmxBatchSetActiveCount(dmxBatchID b, int64_t n_active)
     b->n_active = n_active;
     b->n_flagged = 0;
     for (int64_t i = 0; i < n_active; i++) b->n_flagged += b->h_bflags[(size_t)i] != BF_ALIVE;
+    dmx_damp_recount(b);
     return DMX_OK;
 }
 
@@ -1012,6 +1126,7 @@ extern "C" int dmxBatchStepRange(dmxBatchID b, double h, int64_t first, int64_t 
     if (dmx_refuse_joints(b, "dmxBatchStepRange")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStepRange")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchStepRange")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchStepRange")) return DMX_EINVAL;
     SETTLE(b);
     // lanes own 16 B packs of consecutive bodies: ranges must start on a pack and end on one (or at the end)
     const int64_t pack = 16 / (int64_t)b->rsize;
@@ -1057,6 +1172,7 @@ extern "C" int dmxBatchStepTimed(dmxBatchID b, double h, int nsteps, float *ms)
     if (dmx_refuse_joints(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     if (dmx_refuse_flags(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     if (dmx_refuse_approx1(b, "dmxBatchStepTimed")) return DMX_EINVAL;
+    if (dmx_refuse_stability(b, "dmxBatchStepTimed")) return DMX_EINVAL;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     int rc = dmxBatchStep(b, h, nsteps);

@@ -17,6 +17,7 @@
 #include "dmx_uniform.hpp"
 #include "dmx_fixed.hpp"
 #include "dmx_autodisable.hpp"
+#include "dmx_damping.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -238,7 +239,28 @@ struct dmxBatch {
     int64_t ad_skipped = 0, ad_slept = 0, ad_woken = 0, ad_flag_reads = 0;      // dmxBatchAutoDisableStats [1] .. [3]; dmxBatchDownloadBodyFlags calls
     std::vector<int> sc_ad_dropped;                // the live slots the tick in the making leaves out (asleep islands)
     std::vector<uint8_t> sc_awake;                 // per slot, idle = 0: the island rooted at the slot holds an awake body (dmx_joints.cpp)
+    // damping, angular speed cap, contact correction (include/dmx_batch.h, "damping"; the rules are in dmx_damping.hpp and
+    // contact_rows).  h_damp: the table as given, empty until a call sets a non-default value; damp_dev: the same on the device,
+    // DAMP_REALS reals per slot of the stride in the batch's precision.  The three counts follow every change of the table
+    // (dmx_damp_recount): entries of [0, n_active) that differ from the defaults (the refusal), slots of [0, n) with a scale
+    // other than zero (the damping kernel is launched) and with a finite maximum speed (finish_body is handed the table).
+    std::vector<dmxBodyDamping> h_damp;
+    void *damp_dev = nullptr;
+    int64_t damp_n_set = 0, damp_n_scaled = 0, damp_n_capped = 0;
+    double surface_layer = 0.0, max_corr_vel = __builtin_huge_val();
 };
+void dmx_damp_recount(dmxBatch *b);
+// the ticks that find their own contacts know neither damping, nor the angular speed cap, nor the contact correction scalars
+inline bool dmx_refuse_stability(const dmxBatch *b, const char *what)
+{
+    const bool scalars = b->surface_layer != 0.0 || b->max_corr_vel != __builtin_huge_val();
+    if (b->damp_n_set == 0 && !scalars) return false;
+    fprintf(stderr, "libode_mi355: %s does not honour damping, the maximum angular speed or the contact correction scalars (dmxBatchSetDamping, "
+                    "dmxBatchSetMaxAngularSpeed, dmxBatchUploadBodyDamping, dmxBatchSetContactCorrection): %lld slot(s) hold a non-default entry, "
+                    "surface_layer = %g, max_correcting_vel = %g; use dmxBatchStepJoints\n",
+            what, (long long)b->damp_n_set, b->surface_layer, b->max_corr_vel);
+    return true;
+}
 // auto-disable: the per-slot counters (reset to the batch's values) and the flag mirror, made when the feature is first used
 int dmx_ad_ensure(dmxBatch *b);
 // the DISABLED bits a tick enqueued earlier has set -> h_bflags (waits for that tick; nothing to do when none is pending)

@@ -424,6 +424,9 @@ template <class T> IslandSet<T> island_set_of(dmxBatch *b, const ExactBuffers<T>
 {
     IslandSet<T> I;
     memset(&I, 0, sizeof(I));
+    // (the zeroes above are the defaults of everything but this one: these ticks refuse a batch whose damping table or contact
+    //  scalars are not at their defaults -- dmx_refuse_stability -- so the defaults are what their islands always carry)
+    I.max_corr_vel = (T)__builtin_huge_val();
     I.body_off = B.body_off; I.bodies = B.bodies; I.con_off = B.con_off; I.row_off = B.row_off;
     I.cb1 = B.cb1; I.cb2 = B.cb2; I.csrc = B.csrc; I.crow = B.crow;
     I.gpos = B.gpos; I.gnormal = B.gnormal; I.gdepth = B.gdepth;

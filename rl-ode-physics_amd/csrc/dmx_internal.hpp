@@ -117,6 +117,15 @@ template <class T> struct IslandSet {
     const int *row_level;  // level of every scheduled row, laid out like lev_rows (an island's rows start at its lev_off[0])
     const int *order;      // optional (dmxBatchSetRowOrder, DMX_ORDER_ODE): sweep `it` visits row order[(it / 8) * order_stride +
     int order_stride;      //   row_off[island] + i] at its i-th step; null: rows in creation order (solve_islands only)
+    // damping, angular speed cap, contact correction (include/dmx_batch.h, "damping").  They ride here and not in StepParams:
+    // StepParams is an argument of every fused kernel too (integrate_free, step_plane, step_contacts, ...), and a field appended
+    // there moves the arguments behind it in all of them.  surface_layer / max_corr_vel act on every contact's normal row; at
+    // their defaults (0, +inf) the arithmetic is depth - 0 and a comparison with +inf.  damping: the per-slot table on the device,
+    // DAMP_REALS reals per slot (dmx_damping.hpp), null unless some slot's maximum angular speed is finite: finish_body then loads
+    // nothing.  (Where the three stand among the fields decides how small_world_tick's scalar registers spill: here no kernel's
+    // scratch grows over the parent's, at the end of the struct three instantiations' did -- profiles/stability_kernel_resources.txt.)
+    T surface_layer = T(0), max_corr_vel = (T)__builtin_huge_val();
+    const T *damping = nullptr;
     int singles;           // 1: islands of one body with 1..8 contacts are left to solve_singles / solve_singles_lds (one lane each);
                            // whoever builds `big` must then keep such islands out of it
     // 1: some entries of the contact arrays are units of articulation joints (dmx_island_rows.hpp: joint_unit_rows), marked by

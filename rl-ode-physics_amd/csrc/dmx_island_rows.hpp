@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include "dmx_internal.hpp"
 #include "dmx_math.hpp"
+#include "dmx_damping.hpp"
 
 namespace dmx {
 
@@ -485,9 +486,10 @@ DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, cons
             T erp = P.erp;
             if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
             if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
-            T depth = ind ? I.gdepth[gi] : I.cdepth[ci];
+            T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
             if (depth < 0) depth = 0;
             cval = (hinv * erp) * depth;
+            if (cval > I.max_corr_vel) cval = I.max_corr_vel;
             if (mode & SURF_BOUNCE) {
                 T outgoing = dot3p(J, ldS(S, stride, C_LVEL, s1)) + dot3p(J + 3, ldS(S, stride, C_AVEL, s1));
                 if (s2 >= 0) outgoing += dot3p(J + 6, ldS(S, stride, C_LVEL, s2)) + dot3p(J + 9, ldS(S, stride, C_AVEL, s2));
@@ -713,8 +715,10 @@ __device__ __forceinline__ T row_sor_lds(T *rows, RowRegs<T> &r, T *fc, bool eag
 }
 
 // ---- body k: v += h cforce ; v += h M^-1 f ; integrate ; clear accumulators -------------------------------------
+// (damping: IslandSet::damping, the per-slot table of dmx_damping.hpp or null -- the angular speed cap of a non-kinematic slot.
+//  Every device caller names it: the form without it, below, exists on the host only)
 template <class T>
-DMX_HD void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b, int s, bool has_rows, T h)
+DMX_HD void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b, int s, bool has_rows, T h, const T *damping)
 {
     V3<T> x = ldS(S, stride, C_POS, s);
     Q4<T> q = { S[slab_ix(C_QUAT + 0, s)], S[slab_ix(C_QUAT + 1, s)],
@@ -730,6 +734,9 @@ DMX_HD void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b,
         V3<T> tacc = ld3(b + BW_TACC);
         tacc.x *= h; tacc.y *= h; tacc.z *= h;
         w.x += dot3p(b + BW_INVI + 0, tacc); w.y += dot3p(b + BW_INVI + 3, tacc); w.z += dot3p(b + BW_INVI + 6, tacc);
+        // the angular speed cap, between the velocities and the poses (the quaternion advances with the capped avel); the table's
+        // address is a kernel argument: a wave-uniform test, and nothing is loaded while the table does not exist
+        if (damping != nullptr) cap_angular_speed(w, damping[(size_t)DAMP_REALS * (size_t)s + DAMP_MAX_ANG_SPEED]);
     }
     x.x = fma_(h, v.x, x.x); x.y = fma_(h, v.y, x.y); x.z = fma_(h, v.z, x.z);
     integrate_quat(q, w, h);
@@ -739,6 +746,13 @@ DMX_HD void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b,
     S[slab_ix(C_LVEL + 0, s)] = v.x; S[slab_ix(C_LVEL + 1, s)] = v.y; S[slab_ix(C_LVEL + 2, s)] = v.z;
     S[slab_ix(C_AVEL + 0, s)] = w.x; S[slab_ix(C_AVEL + 1, s)] = w.y; S[slab_ix(C_AVEL + 2, s)] = w.z;
     for (int j = 0; j < 6; j++) S[slab_ix(C_FORCE + j, s)] = T(0);
+}
+// the integrator without a table, for the host harnesses that predate the cap (tests/harness/friction_sweep_harness.cpp): host
+// only, so that a kernel that left the table out does not compile
+template <class T>
+__host__ inline void finish_body(T *S, const uint8_t *bflags, int64_t stride, const T *b, int s, bool has_rows, T h)
+{
+    finish_body<T>(S, bflags, stride, b, s, has_rows, h, (const T *)nullptr);
 }
 
 }  // namespace dmx

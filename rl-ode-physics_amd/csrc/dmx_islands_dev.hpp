@@ -82,9 +82,10 @@ __device__ __forceinline__ void solve_singles_body(T *__restrict__ S, const uint
                         T erp = P.erp;
                         if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
                         if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
-                        T depth = ind ? I.gdepth[gi] : I.cdepth[ci];
+                        T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
                         if (depth < 0) depth = 0;
                         cval = (hinv * erp) * depth;
+                        if (cval > I.max_corr_vel) cval = I.max_corr_vel;
                         if (mode & SURF_BOUNCE) {
                             const T outgoing = dot3p(r.J, v1) + dot3p(r.J + 3, w1);
                             const T bv = own_surface ? I.cbounce_vel[ci] : P.bounce_vel;
@@ -148,7 +149,7 @@ __device__ __forceinline__ void solve_singles_body(T *__restrict__ S, const uint
             }
         }
     }
-    finish_body(S, bflags, stride, b, s, true, h);
+    finish_body(S, bflags, stride, b, s, true, h, I.damping);
     atomicAdd(&diag->contacts, (unsigned long long)nc);
     atomicAdd(&diag->residual, resid);
 }
@@ -214,9 +215,10 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
                 T erp = P.erp;
                 if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
                 if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
-                T depth = ind ? I.gdepth[gi] : I.cdepth[ci];
+                T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
                 if (depth < 0) depth = 0;
                 cval = (hinv * erp) * depth;
+                if (cval > I.max_corr_vel) cval = I.max_corr_vel;
                 if (mode & SURF_BOUNCE) {
                     const T outgoing = dot3p(J, v1) + dot3p(J + 3, w1);
                     const T bv = own_surface ? I.cbounce_vel[ci] : P.bounce_vel;
@@ -297,7 +299,7 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
     };
     for (int it = 0; it + 1 < P.iters; it++) sweep(std::false_type{});
     if (P.iters > 0) sweep(std::true_type{});
-    finish_body(S, bflags, stride, b, s, true, h);
+    finish_body(S, bflags, stride, b, s, true, h, I.damping);
     atomicAdd(&diag->contacts, (unsigned long long)nc);
     atomicAdd(&diag->residual, resid);
 }
@@ -343,7 +345,7 @@ __device__ __forceinline__ void solve_islands_body(T *__restrict__ S, const uint
             }
         }
     }
-    for (int k = 0; k < nb; k++) finish_body(S, bflags, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], m > 0, h);
+    for (int k = 0; k < nb; k++) finish_body(S, bflags, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], m > 0, h, I.damping);
     if (nc > 0) {
         atomicAdd(&diag->contacts, (unsigned long long)nc);
         atomicAdd(&diag->residual, resid);
@@ -938,7 +940,7 @@ __device__ __forceinline__ void solve_island_wg_body(T *__restrict__ S, const ui
             }
         }
     }
-    for (int k = tid; k < nb; k += WG) finish_body(S, bflags, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], m > 0, h);
+    for (int k = tid; k < nb; k += WG) finish_body(S, bflags, stride, bs + (size_t)k * BW_COUNT, I.bodies[b0 + k], m > 0, h, I.damping);
 
     // residual: wave reduction, then one atomic per wave
 #pragma unroll

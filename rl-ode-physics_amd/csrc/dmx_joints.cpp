@@ -691,6 +691,15 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     }
 
     StepParams<T> P = dmx_make_params<T>(b, h);
+    // damping, angular speed cap, contact correction (include/dmx_batch.h, "damping").  The scalars ride in the island set; the
+    // table reaches finish_body only while some slot's maximum speed is finite, and the damping pass goes in front of the tick's
+    // first kernel -- the single-launch tick's one launch included, whose body list it reads where that launch reads it -- only
+    // while some slot's scale is not zero.  (A tick of a subset comes from a caller that has refused any of this.)
+    I.surface_layer = (T)b->surface_layer; I.max_corr_vel = (T)b->max_corr_vel;
+    if (!include && !geo) {
+        if (b->damp_n_capped > 0) I.damping = (const T *)b->damp_dev;
+        if (b->damp_n_scaled > 0) HIP_TRY(launch_damping<T>((T *)b->slab, b->bflags, (const T *)b->damp_dev, I.bodies, nlive, n, b->stream));
+    }
     if (small) {
         // one launch: islands with rows a workgroup each, free bodies and one-body islands a lane each; the new state goes to
         // the slab and to the mirror.  Nobody waits here: dmxBatchDownload(DMX_STATE) does, when the caller reads a pose.

@@ -572,7 +572,7 @@ __global__ __launch_bounds__(1024) void lcp_forces(T *__restrict__ S, const uint
         T *b = bs + (size_t)k * BW_COUNT;
 #pragma unroll
         for (int q = 0; q < 6; q++) b[BW_FC + q] = f[q];
-        if (FINISH) finish_body(S, bflags, stride, b, I.bodies[b0 + k], true, P.h);
+        if (FINISH) finish_body(S, bflags, stride, b, I.bodies[b0 + k], true, P.h, I.damping);
     }
     if (FINISH) {
 #pragma unroll

@@ -413,7 +413,7 @@ __device__ __forceinline__ void lcp_island_lds_body(T *__restrict__ S, const uin
         }
         T *b = bs + (size_t)k * BW_COUNT;
         for (int q = 0; q < 6; q++) b[BW_FC + q] = f[q];
-        finish_body(S, bflags, stride, b, I.bodies[b0 + k], m > 0, h);
+        finish_body(S, bflags, stride, b, I.bodies[b0 + k], m > 0, h, I.damping);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) resid += __shfl_xor(resid, o, 64);

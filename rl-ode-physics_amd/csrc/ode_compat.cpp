@@ -64,6 +64,7 @@ struct dxBody {
     dVector3 facc = { 0, 0, 0, 0 }, tacc = { 0, 0, 0, 0 };
     dMass mass;
     int flags = DMX_BODY_ALIVE;
+    dmxBodyDamping damp = { 0.0, 0.0, 0.01, 0.01, __builtin_huge_val() };      // dBodySetDamping & co.: the world's at creation
     std::vector<dxGeom *> geoms;
 };
 
@@ -138,6 +139,28 @@ struct dxWorld {
     double ad_lin = 0.01, ad_ang = 0.01, ad_time = 0.0;
     int ad_steps = 10, n_ad = 0;
     std::vector<uint8_t> flbuf;
+    // damping, maximum angular speed, contact correction (dWorldSetDamping & co.; include/dmx_batch.h, "damping").  damp: what
+    // dBodyCreate copies into a new body.  damp_used: some body has ever held a non-default entry -- only then does a step send
+    // the table (damp_dirty: it changed since); cc_dirty: the batch has not been told the two contact scalars yet.  A world that
+    // never touches any of this makes no call it did not make before; a world that outgrows its batch sends both again.
+    dmxBodyDamping damp = { 0.0, 0.0, 0.01, 0.01, __builtin_huge_val() };
+    double surface_layer = 0.0, max_corr_vel = __builtin_huge_val();
+    bool damp_used = false, damp_dirty = false, cc_dirty = false;
+    std::vector<dmxBodyDamping> dbuf;
+    void push_damping()
+    {
+        if (damp_dirty) {
+            const dmxBodyDamping def = { 0.0, 0.0, 0.01, 0.01, __builtin_huge_val() };
+            dbuf.assign((size_t)cap, def);
+            for (int s = 0; s < cap; s++) if (slots[(size_t)s]) dbuf[(size_t)s] = slots[(size_t)s]->damp;
+            DMX_MUST(dmxBatchUploadBodyDamping(batch, dbuf.data(), 0, cap));
+            damp_dirty = false;
+        }
+        if (cc_dirty) {
+            DMX_MUST(dmxBatchSetContactCorrection(batch, surface_layer, max_corr_vel));
+            cc_dirty = false;
+        }
+    }
     void set_flags(dxBody *b, int flags)
     {
         const int bits = DMX_BODY_AUTODISABLE | DMX_BODY_DISABLED;
@@ -161,6 +184,8 @@ struct dxWorld {
         art_dirty = !arts.empty();
         feedback_sent = false;         // (a new batch's feedback is off: world_step switches it on again if a struct is set)
         ad_dirty = ad_lin != 0.01 || ad_ang != 0.01 || ad_steps != 10 || ad_time != 0.0;      // (a new batch holds the defaults)
+        damp_dirty = damp_used;
+        cc_dirty = surface_layer != 0.0 || max_corr_vel != __builtin_huge_val();
         // One read-back the general way into the buffer to_host() uses, now.  The runtime registers a pageable destination the
         // first time a device-to-host copy lands in it (8 ms, measured); a world whose ticks run on the single-launch path reads
         // its poses from the batch's host mirror and would meet that at the first tick that falls back -- a whole 120 Hz frame.
@@ -344,6 +369,45 @@ extern "C" void dWorldSetAutoDisableAverageSamplesCount(dWorldID, unsigned int n
 }
 extern "C" int dWorldGetAutoDisableAverageSamplesCount(dWorldID) { return 1; }
 
+// damping, maximum angular speed, contact correction (include/dmx_batch.h, "damping").  One place says what a value may be.
+namespace {
+bool damp_value_ok(const char *who, bool ok, double v)
+{
+    if (!ok) fprintf(stderr, "libode_mi355: %s: %g is out of range; ignored\n", who, v);
+    return ok;
+}
+bool damp_entry_default(const dmxBodyDamping &d)
+{
+    // (in dReal, the width the values were given in: dBodySetLinearDampingThreshold(b, 0.01f) of the single-precision build sets the
+    //  default, though (double)0.01f is not the double 0.01)
+    return d.lin_scale == 0 && d.ang_scale == 0 && (dReal)d.lin_threshold == (dReal)0.01 && (dReal)d.ang_threshold == (dReal)0.01 &&
+           d.max_angular_speed == __builtin_huge_val();
+}
+void body_damping_changed(dxBody *b)
+{
+    dxWorld *w = b->world;
+    if (!w->damp_used && damp_entry_default(b->damp)) return;
+    w->damp_used = true; w->damp_dirty = true;
+}
+}  // namespace
+extern "C" void dWorldSetLinearDamping(dWorldID w, dReal v) { if (damp_value_ok("dWorldSetLinearDamping", v >= 0 && v <= 1, v)) w->damp.lin_scale = v; }
+extern "C" dReal dWorldGetLinearDamping(dWorldID w) { return (dReal)w->damp.lin_scale; }
+extern "C" void dWorldSetAngularDamping(dWorldID w, dReal v) { if (damp_value_ok("dWorldSetAngularDamping", v >= 0 && v <= 1, v)) w->damp.ang_scale = v; }
+extern "C" dReal dWorldGetAngularDamping(dWorldID w) { return (dReal)w->damp.ang_scale; }
+extern "C" void dWorldSetDamping(dWorldID w, dReal lin, dReal ang) { dWorldSetLinearDamping(w, lin); dWorldSetAngularDamping(w, ang); }
+extern "C" void dWorldSetLinearDampingThreshold(dWorldID w, dReal v) { if (damp_value_ok("dWorldSetLinearDampingThreshold", v >= 0, v)) w->damp.lin_threshold = v; }
+extern "C" dReal dWorldGetLinearDampingThreshold(dWorldID w) { return (dReal)w->damp.lin_threshold; }
+extern "C" void dWorldSetAngularDampingThreshold(dWorldID w, dReal v) { if (damp_value_ok("dWorldSetAngularDampingThreshold", v >= 0, v)) w->damp.ang_threshold = v; }
+extern "C" dReal dWorldGetAngularDampingThreshold(dWorldID w) { return (dReal)w->damp.ang_threshold; }
+extern "C" void dWorldSetMaxAngularSpeed(dWorldID w, dReal v) { if (damp_value_ok("dWorldSetMaxAngularSpeed", v > 0, v)) w->damp.max_angular_speed = v; }
+extern "C" dReal dWorldGetMaxAngularSpeed(dWorldID w) { return (dReal)w->damp.max_angular_speed; }
+extern "C" void dWorldSetContactSurfaceLayer(dWorldID w, dReal v)
+{ if (damp_value_ok("dWorldSetContactSurfaceLayer", v >= 0 && v < dInfinity, v)) { w->surface_layer = v; w->cc_dirty = true; } }
+extern "C" dReal dWorldGetContactSurfaceLayer(dWorldID w) { return (dReal)w->surface_layer; }
+extern "C" void dWorldSetContactMaxCorrectingVel(dWorldID w, dReal v)
+{ if (damp_value_ok("dWorldSetContactMaxCorrectingVel", v > 0, v)) { w->max_corr_vel = v; w->cc_dirty = true; } }
+extern "C" dReal dWorldGetContactMaxCorrectingVel(dWorldID w) { return (dReal)w->max_corr_vel; }
+
 static int world_step(dWorldID w, dReal h, int stepper)
 {
     if (!w || !(h > 0)) return 0;
@@ -353,6 +417,7 @@ static int world_step(dWorldID w, dReal h, int stepper)
         DMX_MUST(dmxBatchSetAutoDisable(w->batch, w->ad_lin, w->ad_ang, w->ad_steps, w->ad_time));
         w->ad_dirty = false;
     }
+    w->push_damping();
     if (w->art_dirty) {               // the articulation joints go to the batch only when they changed
         w->aj.clear();
         for (const dxJoint *j : w->arts) {
@@ -495,6 +560,8 @@ extern "C" dBodyID dBodyCreate(dWorldID w)
     w->slots[(size_t)slot] = b;
     w->host_dirty = true;
     if (w->ad_flag) w->set_flags(b, b->flags | DMX_BODY_AUTODISABLE);      // dBodySetAutoDisableDefaults
+    b->damp = w->damp;                                                     // dBodySetDampingDefaults
+    body_damping_changed(b);
     return b;
 }
 extern "C" void dBodyDestroy(dBodyID b)
@@ -507,6 +574,7 @@ extern "C" void dBodyDestroy(dBodyID b)
     // its articulation joints are detached on both sides, ODE's limbo: inactive until attached again
     for (dxJoint *j : w->arts) if (j->b1 == b || j->b2 == b) { j->b1 = j->b2 = nullptr; w->art_dirty = true; }
     w->set_flags(b, DMX_BODY_ALIVE);      // (out of the count of bodies with an auto-disable bit)
+    if (w->damp_used) w->damp_dirty = true;      // (its slot goes back to the defaults)
     w->slots[(size_t)b->slot] = nullptr;
     w->host_dirty = true;
     delete b;
@@ -556,6 +624,19 @@ extern "C" void dBodySetAutoDisableDefaults(dBodyID b) { dBodySetAutoDisableFlag
 extern "C" void dBodyEnable(dBodyID b) { touch(b); b->world->set_flags(b, b->flags & ~DMX_BODY_DISABLED); }
 extern "C" void dBodyDisable(dBodyID b) { touch(b); b->world->set_flags(b, b->flags | DMX_BODY_DISABLED); }
 extern "C" int dBodyIsEnabled(dBodyID b) { b->world->to_host(); return (b->flags & DMX_BODY_DISABLED) == 0; }
+// damping and the maximum angular speed of one body: the table goes to the batch at the next step
+extern "C" void dBodySetLinearDamping(dBodyID b, dReal v) { if (damp_value_ok("dBodySetLinearDamping", v >= 0 && v <= 1, v)) { b->damp.lin_scale = v; body_damping_changed(b); } }
+extern "C" dReal dBodyGetLinearDamping(dBodyID b) { return (dReal)b->damp.lin_scale; }
+extern "C" void dBodySetAngularDamping(dBodyID b, dReal v) { if (damp_value_ok("dBodySetAngularDamping", v >= 0 && v <= 1, v)) { b->damp.ang_scale = v; body_damping_changed(b); } }
+extern "C" dReal dBodyGetAngularDamping(dBodyID b) { return (dReal)b->damp.ang_scale; }
+extern "C" void dBodySetDamping(dBodyID b, dReal lin, dReal ang) { dBodySetLinearDamping(b, lin); dBodySetAngularDamping(b, ang); }
+extern "C" void dBodySetLinearDampingThreshold(dBodyID b, dReal v) { if (damp_value_ok("dBodySetLinearDampingThreshold", v >= 0, v)) { b->damp.lin_threshold = v; body_damping_changed(b); } }
+extern "C" dReal dBodyGetLinearDampingThreshold(dBodyID b) { return (dReal)b->damp.lin_threshold; }
+extern "C" void dBodySetAngularDampingThreshold(dBodyID b, dReal v) { if (damp_value_ok("dBodySetAngularDampingThreshold", v >= 0, v)) { b->damp.ang_threshold = v; body_damping_changed(b); } }
+extern "C" dReal dBodyGetAngularDampingThreshold(dBodyID b) { return (dReal)b->damp.ang_threshold; }
+extern "C" void dBodySetMaxAngularSpeed(dBodyID b, dReal v) { if (damp_value_ok("dBodySetMaxAngularSpeed", v > 0, v)) { b->damp.max_angular_speed = v; body_damping_changed(b); } }
+extern "C" dReal dBodyGetMaxAngularSpeed(dBodyID b) { return (dReal)b->damp.max_angular_speed; }
+extern "C" void dBodySetDampingDefaults(dBodyID b) { b->damp = b->world->damp; body_damping_changed(b); }
 extern "C" void dBodyAddForce(dBodyID b, dReal x, dReal y, dReal z) { touch(b); b->facc[0] += x; b->facc[1] += y; b->facc[2] += z; }
 extern "C" void dBodyAddTorque(dBodyID b, dReal x, dReal y, dReal z) { touch(b); b->tacc[0] += x; b->tacc[1] += y; b->tacc[2] += z; }
 extern "C" void dBodySetMass(dBodyID b, const dMass *m)
