@@ -426,6 +426,57 @@ DMX_HD int joint_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, co
     return n;
 }
 
+// ---- contact_rows with the second body absent, for the one-lane forms of a one-body island (dmx_islands_dev.hpp), which keep their
+// rows in storage of their own; held to contact_rows bit for bit by tests/harness/single_contact_harness.cpp.  Contact ci of the body
+// at x1: gi = its index in the table its geometry lies in, c1 = the contact point less x1, the surface mode, rows per contact, their
+// directions (normal, then the two friction directions when mu > 0) and the friction rows' bounds.
+template <class T>
+DMX_HD void single_contact(const IslandSet<T> &I, const StepParams<T> &P, int ci, const V3<T> &x1, size_t &gi, V3<T> &c1, int &mode,
+                           int &rpc, V3<T> *dir, T &lo_f, T &hi_f)
+{
+    const bool own_surface = I.cmu != nullptr, ind = I.csrc != nullptr;
+    gi = ind ? (size_t)I.csrc[ci] : (size_t)ci;
+    const V3<T> normal = ld3((ind ? I.gnormal : I.cnormal) + 3 * gi);
+    const V3<T> cpos = ld3((ind ? I.gpos : I.cpos) + 3 * gi);
+    c1 = { cpos.x - x1.x, cpos.y - x1.y, cpos.z - x1.z };
+    mode = own_surface ? I.cmode[ci] : P.surf_mode;
+    T mu = own_surface ? I.cmu[ci] : P.mu;
+    if (mu < 0) mu = 0;
+    rpc = mu > 0 ? 3 : 1;
+    dir[0] = normal;
+    dir[1] = dir[2] = { T(0), T(0), T(0) };
+    if (rpc == 3) plane_space(normal, dir[1], dir[2]);
+    lo_f = -mu; hi_f = mu;
+}
+// ... and its row along d: J = [d | c1 x d], c and cfm ("for now": row_setup divides by h) -- for the normal row the surface rule: soft
+// ERP / CFM, depth less the surface layer, the maximum correcting velocity (dmxBatchSetContactCorrection), bounce
+template <class T>
+DMX_HD void single_contact_row(const IslandSet<T> &I, const StepParams<T> &P, int ci, size_t gi, int mode, bool is_normal, const V3<T> &c1,
+                               const V3<T> &d, const V3<T> &v1, const V3<T> &w1, T hinv, T *J, T &cval, T &cfm)
+{
+    J[0] = d.x; J[1] = d.y; J[2] = d.z;
+    const V3<T> a = cross(c1, d);
+    J[3] = a.x; J[4] = a.y; J[5] = a.z;
+    cval = T(0); cfm = P.cfm;
+    if (!is_normal) return;
+    const bool own_surface = I.cmu != nullptr;
+    T erp = P.erp;
+    if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
+    if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
+    T depth = (I.csrc != nullptr ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;
+    if (depth < 0) depth = 0;
+    cval = (hinv * erp) * depth;
+    if (cval > I.max_corr_vel) cval = I.max_corr_vel;
+    if (mode & SURF_BOUNCE) {
+        const T outgoing = dot3p(J, v1) + dot3p(J + 3, w1);
+        const T bv = own_surface ? I.cbounce_vel[ci] : P.bounce_vel;
+        if (bv >= 0 && (-outgoing) > bv) {
+            const T newc = -(own_surface ? I.cbounce[ci] : P.bounce) * outgoing;
+            if (newc > cval) cval = newc;
+        }
+    }
+}
+
 // ---- rows of contact ci (normal + 2 friction when mu > 0), written at island-relative row m -----------------
 // RPCK = 3: the caller knows the contact has friction rows (constant trip counts: a caller that hands in thread-local
 // arrays gets them in registers)
@@ -483,6 +534,8 @@ DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, cons
         }
         T cval = T(0), cfm = P.cfm;
         if (dnum == 0) {
+            // (single_contact_row's surface rule, spelt again with the second body's share of the approach speed: change both, the host
+            //  harness above holds them together.  Taken from one function, eight kernels of dmx_lcp change: profiles/fused_dedup_resources.txt, section 2.)
             T erp = P.erp;
             if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
             if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);

@@ -16,9 +16,9 @@ namespace dmx {
 // A body touching static geometry only (the ground plane, static boxes) is an island of its own: all its rows share the one
 // body, so the sweep is a pure chain -- a wavefront per island (solve_island_wg) would run one lane at a time.  Here a LANE
 // owns the island: up to SINGLE_MAXC contacts x 3 rows live in its registers (no row traffic at all), 64 islands per wave.
-// stage_body, body_tmp and finish_body are the general island step's own; contact_rows, row_setup and row_sor are restated here with
-// the second body absent (the "contact_rows" block twice, in solve_singles_body and solve_singles_lds_body: change both), held to the
-// general path bit for bit by tests/test_gpu_static.py and tests/test_gpu_parity.py.  (What a box resting on the reference's floor, main.c:115, costs per tick.)
+// stage_body, body_tmp and finish_body are the general island step's own; contact_rows is single_contact / single_contact_row
+// (dmx_island_rows.hpp: the second body absent), row_setup and row_sor are restated here
+// with the second body absent, held to the general path bit for bit by tests/test_gpu_static.py and tests/test_gpu_parity.py.  (What a box resting on the reference's floor, main.c:115, costs per tick.)
 constexpr int SINGLE_MAXC = 4;          // rows in registers (solve_singles)
 constexpr int SINGLE_MAXC_LDS = 8;      // rows in LDS (solve_singles_lds): a convex hull's eight contacts with the floor
 
@@ -42,60 +42,27 @@ __device__ __forceinline__ void solve_singles_body(T *__restrict__ S, const uint
     if (nc > SINGLE_MAXC) return;                             // five to eight contacts: solve_singles_lds
     T b[BW_COUNT];
     stage_body(S, bflags, stride, I, P, b, s, 0);
-    const bool own_surface = I.cmu != nullptr, ind = I.csrc != nullptr;
     const V3<T> x1 = ldS(S, stride, C_POS, s), v1 = ldS(S, stride, C_LVEL, s), w1 = ldS(S, stride, C_AVEL, s);
     constexpr int MAXR = 3 * SINGLE_MAXC;
     RowS<T> row[MAXR];
     bool valid[MAXR];
     T lo_f[SINGLE_MAXC], hi_f[SINGLE_MAXC];           // friction bounds of contact c (normal rows: [0, inf))
-    // ---- contact_rows, second body absent
 #pragma unroll
     for (int c = 0; c < SINGLE_MAXC; c++) {
 #pragma unroll
         for (int d = 0; d < 3; d++) valid[3 * c + d] = false;
         lo_f[c] = hi_f[c] = T(0);
         if (c < nc) {
-            const int ci = c0 + c;
-            const size_t gi = ind ? (size_t)I.csrc[ci] : (size_t)ci;
-            const V3<T> normal = ld3((ind ? I.gnormal : I.cnormal) + 3 * gi);
-            const V3<T> cpos = ld3((ind ? I.gpos : I.cpos) + 3 * gi);
-            const V3<T> c1 = { cpos.x - x1.x, cpos.y - x1.y, cpos.z - x1.z };
-            const int mode = own_surface ? I.cmode[ci] : P.surf_mode;
-            T mu = own_surface ? I.cmu[ci] : P.mu;
-            if (mu < 0) mu = 0;
-            const int rpc = mu > 0 ? 3 : 1;
-            V3<T> dir[3];
-            dir[0] = normal;
-            dir[1] = dir[2] = { T(0), T(0), T(0) };
-            if (rpc == 3) plane_space(normal, dir[1], dir[2]);
-            lo_f[c] = -mu; hi_f[c] = mu;
+            size_t gi; int mode, rpc;
+            V3<T> c1, dir[3];
+            single_contact(I, P, c0 + c, x1, gi, c1, mode, rpc, dir, lo_f[c], hi_f[c]);
 #pragma unroll
             for (int dnum = 0; dnum < 3; dnum++) {
                 if (dnum < rpc) {
                     RowS<T> &r = row[3 * c + dnum];
                     valid[3 * c + dnum] = true;
-                    r.J[0] = dir[dnum].x; r.J[1] = dir[dnum].y; r.J[2] = dir[dnum].z;
-                    const V3<T> a = cross(c1, dir[dnum]);
-                    r.J[3] = a.x; r.J[4] = a.y; r.J[5] = a.z;
-                    T cval = T(0), cfm = P.cfm;
-                    if (dnum == 0) {
-                        T erp = P.erp;
-                        if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
-                        if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
-                        T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
-                        if (depth < 0) depth = 0;
-                        cval = (hinv * erp) * depth;
-                        if (cval > I.max_corr_vel) cval = I.max_corr_vel;
-                        if (mode & SURF_BOUNCE) {
-                            const T outgoing = dot3p(r.J, v1) + dot3p(r.J + 3, w1);
-                            const T bv = own_surface ? I.cbounce_vel[ci] : P.bounce_vel;
-                            if (bv >= 0 && (-outgoing) > bv) {
-                                const T newc = -(own_surface ? I.cbounce[ci] : P.bounce) * outgoing;
-                                if (newc > cval) cval = newc;
-                            }
-                        }
-                    }
-                    r.rhs = cval; r.ad = cfm; r.lam = T(0);
+                    single_contact_row(I, P, c0 + c, gi, mode, dnum == 0, c1, dir[dnum], v1, w1, hinv, r.J, r.rhs, r.ad);      // (c and cfm for now)
+                    r.lam = T(0);
                 }
             }
         }
@@ -176,7 +143,6 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
     const int s = I.bodies[I.body_off[isl]];
     T b[BW_COUNT];
     stage_body(S, bflags, stride, I, P, b, s, 0);
-    const bool own_surface = I.cmu != nullptr, ind = I.csrc != nullptr;
     const V3<T> x1 = ldS(S, stride, C_POS, s), v1 = ldS(S, stride, C_LVEL, s), w1 = ldS(S, stride, C_AVEL, s);
     auto at = [&](int r, int f) -> T & { return rs[(size_t)(r * RS_FIELDS + f) * lanes + lane]; };
     unsigned valid = 0;                                       // bit r: slot r (= 3 * contact + direction) holds a row
@@ -188,46 +154,16 @@ __device__ __forceinline__ void solve_singles_lds_body(T *__restrict__ S, const 
     for (int c = 0; c < SINGLE_MAXC_LDS; c++) {
         lo_f[c] = hi_f[c] = T(0);
         if (c >= nc) continue;
-        const int ci = c0 + c;
-        const size_t gi = ind ? (size_t)I.csrc[ci] : (size_t)ci;
-        const V3<T> normal = ld3((ind ? I.gnormal : I.cnormal) + 3 * gi);
-        const V3<T> cpos = ld3((ind ? I.gpos : I.cpos) + 3 * gi);
-        const V3<T> c1 = { cpos.x - x1.x, cpos.y - x1.y, cpos.z - x1.z };
-        const int mode = own_surface ? I.cmode[ci] : P.surf_mode;
-        T mu = own_surface ? I.cmu[ci] : P.mu;
-        if (mu < 0) mu = 0;
-        const int rpc = mu > 0 ? 3 : 1;
-        V3<T> dir[3];
-        dir[0] = normal;
-        dir[1] = dir[2] = { T(0), T(0), T(0) };
-        if (rpc == 3) plane_space(normal, dir[1], dir[2]);
-        lo_f[c] = -mu; hi_f[c] = mu;
+        size_t gi; int mode, rpc;
+        V3<T> c1, dir[3];
+        single_contact(I, P, c0 + c, x1, gi, c1, mode, rpc, dir, lo_f[c], hi_f[c]);
 #pragma unroll
         for (int dnum = 0; dnum < 3; dnum++) {
             if (dnum >= rpc) continue;
             const int r = 3 * c + dnum;
             valid |= 1u << r;
-            T J[6] = { dir[dnum].x, dir[dnum].y, dir[dnum].z, T(0), T(0), T(0) };
-            const V3<T> a = cross(c1, dir[dnum]);
-            J[3] = a.x; J[4] = a.y; J[5] = a.z;
-            T cval = T(0), cfm = P.cfm;
-            if (dnum == 0) {
-                T erp = P.erp;
-                if (mode & SURF_SOFT_ERP) erp = own_surface ? I.csoft_erp[ci] : T(0);
-                if (mode & SURF_SOFT_CFM) cfm = own_surface ? I.csoft_cfm[ci] : T(0);
-                T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
-                if (depth < 0) depth = 0;
-                cval = (hinv * erp) * depth;
-                if (cval > I.max_corr_vel) cval = I.max_corr_vel;
-                if (mode & SURF_BOUNCE) {
-                    const T outgoing = dot3p(J, v1) + dot3p(J + 3, w1);
-                    const T bv = own_surface ? I.cbounce_vel[ci] : P.bounce_vel;
-                    if (bv >= 0 && (-outgoing) > bv) {
-                        const T newc = -(own_surface ? I.cbounce[ci] : P.bounce) * outgoing;
-                        if (newc > cval) cval = newc;
-                    }
-                }
-            }
+            T J[6], cval, cfm;
+            single_contact_row(I, P, c0 + c, gi, mode, dnum == 0, c1, dir[dnum], v1, w1, hinv, J, cval, cfm);
             for (int j = 0; j < 6; j++) at(r, RS_J + j) = J[j];
 #pragma unroll
             for (int q = 0; q < MAXR; q++) if (q == r) { rhsr[q] = cval; adr[q] = cfm; }      // (static indices keep the arrays in registers)

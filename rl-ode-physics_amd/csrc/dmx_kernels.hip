@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, MINW) void step_plane(T *S, T *So, const uint8
 // contact, every contact with its own normal) -> SOR-PGS sweeps -> velocity update -> integrate, one lane per body, rows in
 // registers.  Around the rows the tick is tick_head / tick_tail (dmx_step_fused.hpp), as in step_plane_body and free_body_step; the
 // loads, rows, sweep, stores and diagnostics are a second copy of step_plane_body's, with every contact's own normal and M^-1 J^T's
-// linear part kept per row: change both (same bits as the oracle, tests/test_gpu_static.py).
+// linear part kept per row: change both -- the measured reason stands there (same bits as the oracle, tests/test_gpu_static.py).
 // Two instantiations share a tick: NC = 4 steps the bodies with 0..4 contacts (free bodies included), NC = 8 -- launched
 // behind it when the batch may have such bodies (P.have8) -- those with 5..8; each leaves the other's lanes alone.  A body
 // with more contacts than the buffer holds raises BPF_NOFAST (the exact path steps it: the chunk is rolled back).

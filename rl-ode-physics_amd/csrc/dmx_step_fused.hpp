@@ -334,7 +334,8 @@ __device__ __forceinline__ void step_plane_body(T *S, T *So, const uint8_t *__re
                 if (__ballot(nc > k) != 0ull) ncu = k + 1;
             T rsum = T(0);
             // (The rows, the sweep and its dispatch exist twice, here and in step_contacts (dmx_kernels.hip), which keeps M^-1 J^T's
-            //  linear part per row: change both.  Why they are not shared yet: DESIGN.md section 4.)
+            //  linear part per row: change both.  Shared as functions they were measured against this very text on an MI355X, and
+            //  some instantiation ran slower each time: profiles/fused_dedup_ab.txt section 2)
             // One sweep over the wave's rows.  FAST: the friction rows are unbounded (mu = inf, the reference's surface): no
             // friction clamp.  LAST: only the final sweep tallies |delta lambda|.  Same arithmetic in every variant.
             // FULL: every contact slot of every active lane is taken and friction rows exist (a box resting on the plane: four

@@ -277,6 +277,37 @@ def test_solver_parameters_are_honoured():
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("surface", [(float("inf"), 0.2, 0.1), (0.4, 0.2, 0.1), (0.0, 0.5, 0.3)], ids=["mu_inf", "mu_0.4", "mu_0_bounce"])
+def test_plane_sweep_dispatch_under_three_surfaces(dtype, surface):
+    """step_plane's sweep in its three forms (unbounded friction with every contact slot taken, unbounded friction, clamped friction
+    or one row per contact) on one-body islands: a wavefront of boxes landing flat, four contacts each in the same tick, and a
+    partial one of spinning boxes landing on faces, edges and corners of the ground plane."""
+    mu, bounce, bounce_vel = surface
+    scene = pkg.scenes.box_grid(12, 6, seed=4, y_range=(0.6, 1.2), spin=True, box_mass=True).astype(dtype)
+    scene.avel[:64] = 0                                       # the first wavefront lands flat, all in one tick
+    scene.pos[:64, 1] = scene.sides[:64, 1] / 2 + scene.pos.dtype.type(0.02)
+
+    def gs(w):
+        w.set_surface(mu=mu, bounce=bounce, bounce_vel=bounce_vel)
+
+    def os_(orc, ow):
+        orc.lib.orc_world_set_surface(ow.w, 0x004, mu, bounce, bounce_vel)
+    steps = 90
+    ow = _oracle_build(_orc(dtype), scene, setup=os_)
+    full = partial = False
+    for _ in range(steps):
+        ow.tick(H)
+        assert ow.n_body_pairs() == 0, "scene left the single-body-island regime"
+        c = np.bincount([max(j[0], j[1]) for j in ow.joints()], minlength=scene.n)
+        full = full or bool((c[:64] == 4).all())
+        partial = partial or bool(((c[64:] > 0) & (c[64:] < 4)).any())
+    assert full and partial
+    w = _gpu_run(scene, dtype, steps, setup=gs)
+    _compare(w.state(), ow.state())
+    assert w.last_contact_count() == ow.n_contacts() > scene.n
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
 @pytest.mark.parametrize("mu", [0.0, 0.4, float("inf")])
 def test_piles_with_and_without_friction(dtype, mu):
     """Multi-body islands under the three shapes of a contact: one row (mu = 0: the island solve's row-per-lane form), three

@@ -91,6 +91,78 @@ def test_fused_and_exact_static_paths_agree_with_the_oracle(dtype):
     _same(states[False], ow.state())
 
 
+SURFACES = {"mu_inf": (float("inf"), 0.2, 0.1), "mu_0.4": (0.4, 0.2, 0.1), "mu_0_bounce": (0.0, 0.5, 0.3)}      # mu, bounce, bounce_vel
+
+
+def _flat_and_tilted_boxes():
+    """70 boxes, 3 m apart, a hair above a floor box whose top is at y = 0.5: bodies 0..63 (one wavefront) lie flat and land on a
+    face, four contacts each in the same tick; bodies 64..69 (a partial wavefront) are tilted by a tenth of a radian onto an edge (two
+    contacts) or a corner (one) and rock down from there -- a tilt small enough that none of them leaves the safe zone the
+    collision proof gives it, so that every tick stays on the fused path -> (pos, quat, mass, inertia, sides), the floor"""
+    rng = np.random.default_rng(31)
+    n = 70
+    sides = rng.uniform(0.5, 1.0, (n, 3))
+    quat = np.tile([1.0, 0.0, 0.0, 0.0], (n, 1))
+    low = sides[:, 1] / 2                                    # the lowest point below the centre
+    for b in range(64, n):
+        az = rng.uniform(0.10, 0.16)                         # about z: onto an edge
+        qz = np.array([np.cos(az / 2), 0.0, 0.0, np.sin(az / 2)])
+        ax = 0.0 if b % 2 == 0 else rng.uniform(0.10, 0.16)  # then about x: onto a corner
+        qx = np.array([np.cos(ax / 2), np.sin(ax / 2), 0.0, 0.0])
+        q = np.array([qx[0] * qz[0] - qx[1:] @ qz[1:], *(qx[0] * qz[1:] + qz[0] * qx[1:] + np.cross(qx[1:], qz[1:]))])
+        quat[b] = q
+        w_, x_, y_, z_ = q
+        row_y = np.array([2 * (x_ * y_ + w_ * z_), 1 - 2 * (x_ * x_ + z_ * z_), 2 * (y_ * z_ - w_ * x_)])      # R's second row: world y of the body axes
+        low[b] = 0.5 * np.abs(row_y) @ sides[b]
+    pos = np.stack([3.0 * np.arange(n) - 1.5 * n, 0.5 + low + 0.02, np.zeros(n)], axis=1)
+    mass = sides.prod(axis=1, keepdims=True)
+    inertia = mass / 12 * np.stack([sides[:, 1] ** 2 + sides[:, 2] ** 2, sides[:, 0] ** 2 + sides[:, 2] ** 2, sides[:, 0] ** 2 + sides[:, 1] ** 2], axis=1)
+    floor = [((400.0, 1.0, 50.0), (0.0, 0.0, 0.0), pkg.scenes._rot_z(0.0))]
+    return (pos, quat, mass, inertia, sides), floor
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("surface", list(SURFACES))
+def test_sweep_dispatch_at_a_static_floor_under_three_surfaces(dtype, surface):
+    """step_contacts' sweep takes one of three forms per wavefront: FAST and FULL (unbounded friction, every contact slot of every
+    lane taken), FAST alone, and neither (bounded friction: the friction rows clamp; or mu = 0: one row per contact).  One
+    wavefront of boxes flat on the floor (four contacts each) and a partial one of boxes on an edge or a corner, under mu = inf,
+    mu = 0.4 and mu = 0 with bounce 0.5 above 0.3 m/s, the ground plane on beneath the floor: the oracle's bits in each."""
+    mu, bounce, bounce_vel = SURFACES[surface]
+    boxes, floor = _flat_and_tilted_boxes()
+    scene = _box_scene(*boxes, dtype)
+    scene.plane = (0.0, 1.0, 0.0, 0.0)
+    steps = 90
+    orc = _orc(dtype)
+    ow = orc.world()
+    orc.lib.orc_world_set_surface(ow.w, 0x004, mu, bounce, bounce_vel)
+    ow.add_plane(*scene.plane)
+    ow.add_static_box(*floor[0])
+    ow.add_boxes(scene.pos, scene.quat, scene.lvel, scene.avel, scene.mass[:, 0], scene.inertia, scene.sides)
+    full = partial = False
+    for _ in range(steps):
+        ow.tick(H)
+        assert all(j[0] < 0 or j[1] < 0 for j in ow.joints())           # static contacts only: every island is one body
+        c = _contacts_per_body(ow, scene.n)
+        assert c.max() <= 4
+        full = full or bool((c[:64] == 4).all())
+        partial = partial or bool(((c[64:] > 0) & (c[64:] < 4)).any())
+    assert full, "no tick with four contacts on every body of the first wavefront"
+    assert partial, "no tick with one to three contacts on a body of the second wavefront"
+    w = pkg.BatchWorld(scene.n, dtype=dtype)
+    w.set_surface(mu=mu, bounce=bounce, bounce_vel=bounce_vel)
+    w.load_scene(scene)
+    w.set_static_boxes(floor)
+    w.step(H, steps)
+    got = w.state()
+    st = w.collision_stats()
+    contacts = w.last_contact_count()
+    w.close()
+    _same(got, ow.state())
+    assert st["careful_ticks"] == 0 and st["fast_ticks"] == steps, st      # the fused path (step_contacts) made every tick
+    assert contacts == ow.n_contacts()
+
+
 def _boxes_across_a_plank(n=24):
     """boxes lying diagonally across a plank narrower than themselves -> (pos, quat, mass, inertia, sides), the plank"""
     rng = np.random.default_rng(5)
