@@ -349,7 +349,8 @@ typedef struct dmxContactJoint {
  * is without the bits: mu = +inf with a bit set is the unbounded row (ODE's |inf * 0| would be NaN), mu <= 0 still makes one row.
  * Row count, row order (creation order, a contact's friction rows directly behind its normal row), island building and the set of
  * rows that can never clamp depend on mu alone, not on the bits.  ODE's dContactApprox1_N (0x4000, rolling friction) has no meaning:
- * there are no rolling rows; there is no field for dContactMu2 or dContactFDir1.
+ * there are no rolling rows.  dContactMu2, dContactFDir1, dContactMotion* and dContactSlip* have no field here and are ignored by
+ * dmxBatchStepJoints: they travel in dmxContactSurface, through dmxBatchStepJointsSurface (below), which makes mu a per-row mu_r.
  *   QuickStep (DMX_STEPPER_QUICK, DMX_ORDER_CREATION): when a sweep visits a pyramid row, hi = |mu lambda_n|, lo = -hi, lambda_n = the
  *     CURRENT multiplier of the contact's normal row, already updated in this sweep (ODE's SOR_LCP); nothing else about the update
  *     changes.  ODE moves such rows to the end of its row order; this library keeps creation order.  Under DMX_ORDER_ODE with
@@ -363,6 +364,46 @@ typedef struct dmxContactJoint {
  *   The single-launch tick honours pyramid rows under QuickStep; under dWorldStep a tick with a pyramid row takes the general path,
  *   whole, and counts under DMX_SMALL_TICK_STAT_LDS_FIT. */
 int dmxBatchStepJoints(dmxBatchID b, double h, int64_t n_joints, const dmxContactJoint *joints);
+/* The rest of ODE's contact surface (dContactMu2, dContactFDir1, dContactMotion1 / 2 / N, dContactSlip1 / 2).  dmxContactJoint is ABI
+ * and has no spare field, so the seven fields travel beside it: surfaces[k] belongs to joints[k], and bit X of joints[k].mode says
+ * that field X of surfaces[k] is read.  Fields without their bit are never read.  The values of the bits are ODE's.
+ *   surfaces == NULL is dmxBatchStepJoints, call for call; and dmxBatchStepJoints itself goes on ignoring the seven bits.
+ *   A tick is an EXTENDED TICK when some contact that survives canonicalisation and the auto-disable drop has a bit of
+ *   DMX_CONTACT_SURFACE_EXT set.  A tick with surfaces != NULL that is not extended stages, launches and loads exactly what
+ *   dmxBatchStepJoints does; an extended tick launches the kernels a tick with a pyramid row launches (DMX_CONTACT_APPROX1).
+ * This library's definition ([ODE-recall] where it follows ODE's dxJointContact::getInfo2):
+ *   Coefficients.  mu_1 = max(mu, 0); mu_2 = max(surface.mu2, 0) with MU2, else mu_1.  The contact has three rows when
+ *     max(mu_1, mu_2) > 0, else one.  [ODE-recall] ODE leaves out a friction row whose coefficient is 0; this library keeps three
+ *     rows per contact and builds that row with lo = hi = 0: its multiplier is 0 under both steppers, the velocities are the same.
+ *   Sides.  Canonicalisation is dmxBatchStepJoints': when body1 is not a live slot the sides are exchanged and the normal negated;
+ *     n is the canonical normal.
+ *   Directions.  Row 0 is along n.  With FDIR1: d_1 = fdir1 as given, d_2 = n x d_1 [ODE-recall]; fdir1 is neither normalised nor
+ *     projected -- unit length and orthogonality to the normal are the caller's duty, as in ODE.  Without: dPlaneSpace(n), as before.
+ *   Bounds of friction row r (1 or 2) with coefficient mu_r: 0 gives lo = hi = 0; +inf the unbounded row, whatever the Approx1 bit;
+ *     otherwise a pyramid row with coefficient mu_r when DMX_CONTACT_APPROX1_r is set, else the box row -/+ mu_r.  dWorldStep's
+ *     two passes and QuickStep's moving bound (above) apply with mu_r in place of mu.
+ *   Right-hand side.  Row 0: c = erp / h * max(depth - surface_layer, 0) + (MOTIONN ? motionN : 0), then the max_correcting_vel cap,
+ *     then the bounce rule.  Row 1: c = MOTION1 ? motion1 : 0.  Row 2: c = MOTION2 ? motion2 : 0.  The meaning, in CANONICAL
+ *     sides: (v_p1 - v_p2) . d_r = c_r, v_pi = the velocity of body i's material point at pos (0 for the world), body 1 the live
+ *     body the canonical normal points into, d_2 = n x d_1.  No motion changes sign where the sides were exchanged, whatever made
+ *     d_1: a body on a belt (the world, fdir1 along the belt, motion1 = u) is carried along +fdir1 at u whether the joint was
+ *     given as (body, world) or as (world, body).  That keeps a belt's direction independent of the order of the two bodies (of
+ *     dJointAttach's arguments); what stock ODE does on this point is not checked.
+ *   Slip.  Row r's CFM is slip_r with SLIPr, else the world's CFM.  It is divided by h like every row's; the multiplier is a force,
+ *     so the row slides at slip_r times its friction force [ODE-recall].
+ *   Refused with DMX_EINVAL, one line on stderr, the state and the last tick's feedback untouched: a read field of any joint given
+ *     that is NaN; a read slip that is negative or not finite; a read motion or fdir1 component that is not finite -- each judged
+ *     as the batch will hold it: in a DMX_F32 batch a double above float's largest is an infinity; an extended tick under
+ *     DMX_ORDER_ODE with QuickStep.  (mu and mu2 are likewise taken rounded to the batch's precision when rows are counted.)  Bits of
+ *     the mode above ODE's (0x10000 and up) mean nothing and are not passed on.  (A tick of a subset of the bodies cannot receive surfaces: the ticks that find
+ *     their own contacts do not come through here.)
+ *   The one-body forms know box friction only: an extended tick's one-body islands take the row form.  The single-launch tick
+ *   honours an extended QuickStep tick; an extended dWorldStep tick takes the general path, whole, and counts under
+ *   DMX_SMALL_TICK_STAT_LDS_FIT.  Feedback, auto-disable and damping work as in every dmxBatchStepJoints tick. */
+enum { DMX_CONTACT_MU2 = 0x001, DMX_CONTACT_FDIR1 = 0x002, DMX_CONTACT_MOTION1 = 0x020, DMX_CONTACT_MOTION2 = 0x040,
+       DMX_CONTACT_MOTIONN = 0x080, DMX_CONTACT_SLIP1 = 0x100, DMX_CONTACT_SLIP2 = 0x200, DMX_CONTACT_SURFACE_EXT = 0x3e3 };
+typedef struct dmxContactSurface { double mu2, fdir1[3], motion1, motion2, motionN, slip1, slip2; } dmxContactSurface;  /* 72 bytes */
+int dmxBatchStepJointsSurface(dmxBatchID b, double h, int64_t n_joints, const dmxContactJoint *joints, const dmxContactSurface *surfaces);
 /* Which of ODE's two steppers dmxBatchStepJoints is.  DMX_STEPPER_QUICK (default): dWorldQuickStep, QuickStep's SOR sweeps.
  * DMX_STEPPER_EXACT: dWorldStep, the reference's own call (main.c:213): every island's system
  *   A lambda = b + w,  A = J M^-1 J^T + cfm / h,  lo <= lambda <= hi,  w complementary to lambda
@@ -393,8 +434,8 @@ int dmxBatchLcpStats(dmxBatchID b, int64_t out[8]);
 int dmxBatchSetSmallTick(dmxBatchID b, int mode);
 /* Counters since the batch was created: ticks on the single-launch path, ticks of dmxBatchStepJoints on the general path,
  * then per reason the ticks that were not eligible (a tick counts under the first reason that applies, in this order).
- * DMX_SMALL_TICK_STAT_LDS_FIT also counts the dWorldStep ticks that have a pyramid row (DMX_CONTACT_APPROX1): their two passes are
- * the general path's. */
+ * DMX_SMALL_TICK_STAT_LDS_FIT also counts the dWorldStep ticks that have a pyramid row (DMX_CONTACT_APPROX1) -- their two passes are
+ * the general path's -- and the extended dWorldStep ticks of dmxBatchStepJointsSurface. */
 enum {
     DMX_SMALL_TICK_STAT_SMALL = 0, DMX_SMALL_TICK_STAT_GENERAL = 1, DMX_SMALL_TICK_STAT_MODE = 2, DMX_SMALL_TICK_STAT_ROW_ORDER = 3,
     DMX_SMALL_TICK_STAT_SUBSET = 4, DMX_SMALL_TICK_STAT_BODIES = 5, DMX_SMALL_TICK_STAT_ISLANDS = 6, DMX_SMALL_TICK_STAT_SOR_ROWS = 7,

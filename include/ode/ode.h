@@ -30,7 +30,8 @@ extern "C" {
  * friction (rho, rho2, rhoN; dContactRolling, dContactApprox1_N) sits between mu2 and bounce, so an object compiled against
  * stock 0.16 headers writes `bounce` where this library reads it (tests/test_ode_compat.py checks every offset).  ODE <= 0.12
  * had no rho fields: objects built against those headers must be recompiled against these.  The rolling-friction fields are
- * accepted and ignored (the reference never sets them, main.c:684-687). */
+ * accepted and ignored (the reference never sets them, main.c:684-687).  dContactMu2, dContactFDir1, dContactMotion1 / 2 / N and
+ * dContactSlip1 / 2 are honoured, by the definition of include/dmx_batch.h at DMX_CONTACT_MU2. */
 enum {
     dContactMu2      = 0x001,
     dContactAxisDep  = 0x001,

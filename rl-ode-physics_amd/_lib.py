@@ -18,7 +18,7 @@ BATCH_SYMBOLS = [
     "dmxBatchDevicePtr", "dmxBatchStride", "dmxBatchStep", "dmxBatchSynchronize", "dmxBatchSetStream",
     "dmxBatchStepTimed", "dmxBatchLastContactCount", "dmxBatchLastResidual", "dmxBatchPackTransforms",
     "dmxBatchDownloadTransforms", "dmxBatchGatherBodies", "dmxBatchScatterBodies",
-    "dmxBatchStepJoints", "dmxBatchUploadBodyFlags", "dmxBatchSetActiveCount", "dmxBatchStepRange",
+    "dmxBatchStepJoints", "dmxBatchStepJointsSurface", "dmxBatchUploadBodyFlags", "dmxBatchSetActiveCount", "dmxBatchStepRange",
     "dmxBatchGetStream", "dmxBatchSetBodyCollisions", "dmxBatchCollisionStats",
     "dmxBatchScatterBodiesOnStream", "dmxBatchSetBoundaryPack",
     "dmxBatchChunkBegin", "dmxBatchChunkTick", "dmxBatchCheckZonesOnStream", "dmxBatchChunkEnd",
@@ -91,6 +91,7 @@ def load():
     sig("dmxBatchGatherBodies", I, P, P, L, P)
     sig("dmxBatchScatterBodies", I, P, P, L, P)
     sig("dmxBatchStepJoints", I, P, D, L, P)
+    sig("dmxBatchStepJointsSurface", I, P, D, L, P, P)
     sig("dmxBatchUploadBodyFlags", I, P, P, L, L)
     sig("dmxBatchSetActiveCount", I, P, L)
     sig("dmxBatchStepRange", I, P, D, L, L, I)

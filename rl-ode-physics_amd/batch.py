@@ -36,6 +36,16 @@ CONTACT_JOINT_DTYPE = np.dtype({
                 np.float64, np.float64, np.float64],
     "offsets": [0, 24, 48, 56, 60, 64, 72, 80, 88, 96, 104],
     "itemsize": 112})
+# dmxContactSurface (include/dmx_batch.h): the rest of ODE's contact surface, one per contact joint (step_joints' `surfaces`); bit X
+# of a joint's mode says that field X of its surface is read.  The bits' values are ODE's.
+CONTACT_MU2, CONTACT_FDIR1, CONTACT_MOTION1, CONTACT_MOTION2, CONTACT_MOTIONN = 0x001, 0x002, 0x020, 0x040, 0x080
+CONTACT_SLIP1, CONTACT_SLIP2 = 0x100, 0x200
+CONTACT_SURFACE_EXT = 0x3e3
+CONTACT_SURFACE_DTYPE = np.dtype({
+    "names": ["mu2", "fdir1", "motion1", "motion2", "motionN", "slip1", "slip2"],
+    "formats": [np.float64, (np.float64, 3), np.float64, np.float64, np.float64, np.float64, np.float64],
+    "offsets": [0, 8, 32, 40, 48, 56, 64],
+    "itemsize": 72})
 # dmxJoint (include/dmx_batch.h): an articulation joint -- a ball, a hinge, a slider or a fixed joint -- of the persistent set
 # (set_joints)
 JOINT_BALL, JOINT_HINGE, JOINT_SLIDER, JOINT_FIXED = 1, 2, 3, 4
@@ -215,11 +225,22 @@ class BatchWorld:
         _check(self.lib.dmxBatchStep(self.h, h, nsteps), "dmxBatchStep")
 
     # -- explicit contact joints: the callback form of the tick (dJointCreateContact + dWorldStep, include/dmx_batch.h) --
-    def step_joints(self, h, joints):
-        """one tick driven by `joints`, an array of CONTACT_JOINT_DTYPE (or anything with its fields)"""
+    def step_joints(self, h, joints, surfaces=None):
+        """one tick driven by `joints`, an array of CONTACT_JOINT_DTYPE (or anything with its fields); `surfaces`: one
+        CONTACT_SURFACE_DTYPE per joint, whose fields are read where the joint's mode has their bit (dmxBatchStepJointsSurface)"""
         j = np.ascontiguousarray(np.asarray(joints).astype(CONTACT_JOINT_DTYPE, copy=False))
-        _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
-               "dmxBatchStepJoints")
+        if surfaces is None:
+            _check(self.lib.dmxBatchStepJoints(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None),
+                   "dmxBatchStepJoints")
+        else:
+            s = np.ascontiguousarray(np.asarray(surfaces).astype(CONTACT_SURFACE_DTYPE, copy=False))
+            if s.shape[0] != j.shape[0]:
+                raise ValueError("step_joints: %d surfaces for %d joints" % (s.shape[0], j.shape[0]))
+            # (an empty array has no address worth passing; one spare entry keeps `surfaces` non-NULL, which is what selects the call)
+            if s.shape[0] == 0:
+                s = np.zeros(1, CONTACT_SURFACE_DTYPE)
+            _check(self.lib.dmxBatchStepJointsSurface(self.h, h, j.shape[0], j.ctypes.data if j.shape[0] else None, s.ctypes.data),
+                   "dmxBatchStepJointsSurface")
         self._last_n_joints = int(j.shape[0])
 
     # -- articulation joints: ball, hinge, slider and fixed (dJointCreateBall / Hinge / Slider / Fixed), a set that persists

@@ -348,7 +348,7 @@ struct DmxPhase {          // adds the scope's wall time to b->prof[k]
 // contact geometry that already lives on the device (device narrowphase): joint k's pos/normal/depth are entry src[k]
 struct DevGeometry { const void *pos, *normal, *depth; const int32_t *src; };
 int dmx_step_joints(dmxBatch *b, double h, int64_t n_joints, const dmxContactJoint *joints, const uint8_t *include,
-                    const DevGeometry *geo);
+                    const DevGeometry *geo, const dmxContactSurface *surfaces = nullptr);      // (surfaces: dmxBatchStepJointsSurface only)
 // body-body collision handling of the batch tick (dmx_general.cpp)
 int dmx_step_collide(dmxBatch *b, double h, int nsteps);
 // close the chunk dmxBatchStep may have left open (flag read; rollback + replay on a violation).  Every entry point that

@@ -84,6 +84,14 @@ constexpr int CONVEX_MAXC = 8;      // contact slots per convex body per tick (t
 enum : int { SURF_BOUNCE = 0x004, SURF_SOFT_ERP = 0x008, SURF_SOFT_CFM = 0x010 };
 // DMX_CONTACT_APPROX1_1 / _2: friction row 1 / 2 is bounded by mu times the contact's normal force (include/dmx_batch.h)
 enum : int { SURF_APPROX1_1 = 0x1000, SURF_APPROX1_2 = 0x2000, SURF_APPROX1 = 0x3000 };
+// the extended surface of dmxBatchStepJointsSurface (include/dmx_batch.h at DMX_CONTACT_MU2).  SURF_FDIR1 = DMX_CONTACT_FDIR1, the one
+// bit of the seven the row builder looks at itself: what the other six select the host has resolved when it stages IslandSet::cext.
+// SURF_EXT_MU1_ZERO is the host's own mark, above every bit of ODE's: mu_1 = 0 < mu_2, and cmu carries mu_2 so that the entry still
+// counts three rows wherever rows are counted from cmu (contact_rpc, entry_feedback).
+enum : int { SURF_FDIR1 = 0x002, SURF_EXT_MU1_ZERO = 0x10000 };
+// IslandSet::cext, EXT_REALS reals per entry: mu_2 (mu_1 again without DMX_CONTACT_MU2), fdir1 as given, motion1, motion2, motionN (0
+// without their bits), slip1, slip2 (-1 without their bits: the world's CFM)
+enum : int { EXT_MU2 = 0, EXT_FDIR1 = 1, EXT_MOTION1 = 4, EXT_MOTION2 = 5, EXT_MOTIONN = 6, EXT_SLIP1 = 7, EXT_SLIP2 = 8, EXT_REALS = 9 };
 // per-slot body flags (uint8 array)
 enum : int { BF_ALIVE = 1, BF_KINEMATIC = 2, BF_NOGRAVITY = 4, BF_NOGYRO = 8 };
 
@@ -126,6 +134,12 @@ template <class T> struct IslandSet {
     // scratch grows over the parent's, at the end of the struct three instantiations' did -- profiles/stability_kernel_resources.txt.)
     T surface_layer = T(0), max_corr_vel = (T)__builtin_huge_val();
     const T *damping = nullptr;
+    // an extended tick (dmxBatchStepJointsSurface with some bit of DMX_CONTACT_SURFACE_EXT honoured): EXT_REALS reals per entry behind
+    // the contact arrays' twelve, read by contact_rows' APX instantiations only; null in every other tick.  (Here, behind the damping
+    // table, and not at the end of the struct, for the reason given above: at the end small_world_tick<float, true, false, false, true>
+    // gains 32 bytes of scratch and the two solve_singles kernels change registers; here every kernel that is not an APX
+    // instantiation keeps the parent's registers, scratch, occupancy and LDS -- profiles/surface_kernel_resources.txt.)
+    const T *cext = nullptr;
     int singles;           // 1: islands of one body with 1..8 contacts are left to solve_singles / solve_singles_lds (one lane each);
                            // whoever builds `big` must then keep such islands out of it
     // 1: some entries of the contact arrays are units of articulation joints (dmx_island_rows.hpp: joint_unit_rows), marked by

@@ -17,8 +17,8 @@ namespace dmx {
 enum : int { RW_J = 0, RW_IMJ = 12, RW_RHS = 24, RW_AD = 25, RW_LO = 26, RW_HI = 27, RW_LAM = 28, RW_COUNT = ISLAND_ROW_REALS };
 // the first of the three spare reals: in a tick made with feedback on (the FB instantiations) QuickStep's row_setup leaves the factor Ad it scaled J by here
 enum : int { RW_UNSCALE = 29 };
-// the other two, in a tick with pyramid rows (DMX_CONTACT_APPROX1; the APX instantiations, which alone write and read them): RW_FMU =
-// mu on a pyramid row, -1 on the normal row of a contact that has one, 0 on every other row; RW_FDIR = the pyramid row's direction
+// the other two, in a tick with pyramid rows or extended surfaces (DMX_CONTACT_APPROX1, DMX_CONTACT_SURFACE_EXT; the APX instantiations,
+// which alone write and read them): RW_FMU = the row's mu on a pyramid row, -1 on the normal row of a contact that has one, 0 on every other row; RW_FDIR = the pyramid row's direction
 // (1 or 2): its contact's normal row is that many rows before it
 enum : int { RW_FMU = 30, RW_FDIR = 31 };
 static_assert(RW_COUNT >= 29 && RW_COUNT % 4 == 0, "a row is read in 16-byte pieces");
@@ -484,7 +484,12 @@ DMX_HD void single_contact_row(const IslandSet<T> &I, const StepParams<T> &P, in
 // mode has DMX_CONTACT_APPROX1_d and whose mu is positive and finite is marked (RW_FMU, RW_FDIR) and built with lo = hi = 0 -- what
 // dWorldStep's pass A solves; QuickStep's sweeps and dWorldStep's pass B make its bounds from the normal row's multiplier -- and
 // every other row of the tick gets RW_FMU <= 0
-// (host too: tests/harness/friction_sweep_harness.cpp)
+// APX with I.cext set (an extended tick, dmxBatchStepJointsSurface; the definition: include/dmx_batch.h at DMX_CONTACT_MU2): a
+// coefficient per friction row (mu_1, mu_2: all of the above with mu_d in place of mu; a row with mu_d = 0 is built with lo = hi = 0),
+// d_1 = fdir1 and d_2 = n x d_1 where the contact's mode has DMX_CONTACT_FDIR1, c of the friction rows from motion1 / motion2 and
+// motionN added to the normal row's before the cap, the friction rows' cfm from slip1 / slip2 -- all as the host staged them behind
+// I.cext (dmx_internal.hpp at EXT_MU2).  With I.cext null, and in every instantiation without APX, the rows are what they were.
+// (host too: tests/harness/friction_sweep_harness.cpp, tests/harness/surface_rows_harness.cpp)
 template <class T, int RPCK = 0, bool APX = false>
 DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P,
                                              T *rows, int *jb, int ci, int m, T hinv)
@@ -514,10 +519,29 @@ DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, cons
     T mu = own_surface ? I.cmu[ci] : P.mu;
     if (mu < 0) mu = 0;
     const int rpc = RPCK ? RPCK : (mu > 0 ? 3 : 1);
+    // the extended surface (an extended tick only: the pointer is a kernel argument, a wave-uniform test): mu_r per friction row,
+    // and below the rows' directions, right-hand sides and CFM.  (cmu > 0 when either coefficient is: see SURF_EXT_MU1_ZERO.)
+    const T *ext = nullptr;
+    T mu1 = mu, mu2 = mu;
+    if (APX) {
+        if (I.cext != nullptr) {
+            ext = I.cext + (size_t)EXT_REALS * (size_t)ci;
+            if (mode & SURF_EXT_MU1_ZERO) mu1 = T(0);
+            mu2 = ext[EXT_MU2];
+        }
+    }
     V3<T> dir[3];
     dir[0] = normal;
-    if (rpc == 3) plane_space(normal, dir[1], dir[2]);
-    const int pyr = (APX && rpc == 3 && mu < Limits<T>::inf()) ? (mode & SURF_APPROX1) : 0;      // bit SURF_APPROX1_d: row d is a pyramid row
+    if (rpc == 3) {
+        if (APX && ext != nullptr && (mode & SURF_FDIR1)) { dir[1] = ld3(ext + EXT_FDIR1); dir[2] = cross(normal, dir[1]); }
+        else plane_space(normal, dir[1], dir[2]);
+    }
+    // bit SURF_APPROX1_d: row d is a pyramid row
+    int pyr = 0;
+    if (APX && rpc == 3) {
+        if (mu1 > 0 && mu1 < Limits<T>::inf()) pyr |= mode & SURF_APPROX1_1;
+        if (mu2 > 0 && mu2 < Limits<T>::inf()) pyr |= mode & SURF_APPROX1_2;
+    }
 #pragma unroll
     for (int dnum = 0; dnum < rpc; dnum++) {
         T *row = rows + (size_t)(m + dnum) * RW_COUNT;
@@ -542,6 +566,7 @@ DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, cons
             T depth = (ind ? I.gdepth[gi] : I.cdepth[ci]) - I.surface_layer;      // (dmxBatchSetContactCorrection; 0 and +inf by default)
             if (depth < 0) depth = 0;
             cval = (hinv * erp) * depth;
+            if (APX) { if (ext != nullptr) cval += ext[EXT_MOTIONN]; }
             if (cval > I.max_corr_vel) cval = I.max_corr_vel;
             if (mode & SURF_BOUNCE) {
                 T outgoing = dot3p(J, ldS(S, stride, C_LVEL, s1)) + dot3p(J + 3, ldS(S, stride, C_AVEL, s1));
@@ -555,11 +580,17 @@ DMX_HD void contact_rows(const T *S, int64_t stride, const IslandSet<T> &I, cons
             row[RW_LO] = T(0); row[RW_HI] = Limits<T>::inf();
             if (APX) row[RW_FMU] = pyr ? T(-1) : T(0);
         } else {
-            row[RW_LO] = -mu; row[RW_HI] = mu;
+            const T mud = APX ? (dnum == 1 ? mu1 : mu2) : mu;
+            row[RW_LO] = -mud; row[RW_HI] = mud;
             if (APX) {
                 const bool p = (pyr & (SURF_APPROX1_1 << (dnum - 1))) != 0;
                 if (p) { row[RW_LO] = T(0); row[RW_HI] = T(0); }
-                row[RW_FMU] = p ? mu : T(0); row[RW_FDIR] = T(dnum);
+                row[RW_FMU] = p ? mud : T(0); row[RW_FDIR] = T(dnum);
+                if (ext != nullptr) {
+                    cval = ext[EXT_MOTION1 + dnum - 1];
+                    const T slip = ext[EXT_SLIP1 + dnum - 1];
+                    if (slip >= 0) cfm = slip;
+                }
             }
         }
         row[RW_RHS] = cval;     // c for now

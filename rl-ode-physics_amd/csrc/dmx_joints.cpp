@@ -61,7 +61,7 @@ int ensure_mapped(void **p, void **dev, size_t *have, size_t bytes)
 }
 
 template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const dmxContactJoint *joints,
-                                     const uint8_t *include, const DevGeometry *geo)
+                                     const uint8_t *include, const DevGeometry *geo, const dmxContactSurface *surfaces)
 {
     const int n = (int)b->n;
     // feedback (dmxBatchSetFeedback): for dmxBatchStepJoints' own ticks only -- the ticks that find their contacts themselves come
@@ -125,12 +125,42 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     int n_units = (int)cj.size();
     // rows of an entry, and how many of them can clamp (a limot unit's one row is counted as able to, whatever its state will be)
     auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT; };
-    auto rpc_of = [&](const CJ &c) { return c.unit ? ((c.unit == UNIT_HINGE2 || c.unit == UNIT_SLIDER2) ? 2 : is_limot(c.unit) ? 1 : 3) : (c.j->mu > 0 ? 3 : 1); };
-    auto nbd_rows_of = [&](const CJ &c) { return c.unit ? (is_limot(c.unit) ? 1 : 0) : ((c.j->mu > 0 && c.j->mu < __builtin_huge_val()) ? 3 : 1); };
-    // pyramid rows (DMX_CONTACT_APPROX1): friction row d of a contact whose mode has bit APPROX1_d and whose mu is positive and finite.
+    // the coefficient of friction row r (1 or 2) of a contact joint: mu_1 = max(mu, 0); mu_2 = max(surface.mu2, 0) where the caller
+    // came with surfaces (dmxBatchStepJointsSurface) and the joint's mode has DMX_CONTACT_MU2, else mu_1 (include/dmx_batch.h).
+    // Row count, island building and the rows that can never clamp depend on these two alone.
+    const double inf_d = __builtin_huge_val();
+    // (taken as the device will hold them, rounded to the batch's precision: a positive coefficient below float's smallest is 0 there
+    //  too, so the host and the device count the same rows)
+    auto mu_row = [&](const dmxContactJoint &j, int r) {
+        double m = j.mu;
+        if (r == 2 && surfaces && (j.mode & DMX_CONTACT_MU2)) m = surfaces[&j - joints].mu2;
+        m = (double)(T)m;
+        return m > 0 ? m : 0.0;
+    };
+    // (without surfaces -- dmxBatchStepJoints and the ticks that find their own contacts -- all of it is the one test of mu it was)
+    auto rpc_of = [&](const CJ &c) {
+        if (c.unit) return (c.unit == UNIT_HINGE2 || c.unit == UNIT_SLIDER2) ? 2 : is_limot(c.unit) ? 1 : 3;
+        if (!surfaces) return c.j->mu > 0 ? 3 : 1;
+        return (mu_row(*c.j, 1) > 0 || mu_row(*c.j, 2) > 0) ? 3 : 1;
+    };
+    auto nbd_rows_of = [&](const CJ &c) {
+        if (c.unit) return is_limot(c.unit) ? 1 : 0;
+        if (!surfaces) return (c.j->mu > 0 && c.j->mu < inf_d) ? 3 : 1;
+        const double m1 = mu_row(*c.j, 1), m2 = mu_row(*c.j, 2);
+        return (m1 > 0 || m2 > 0) ? 1 + (m1 < inf_d ? 1 : 0) + (m2 < inf_d ? 1 : 0) : 1;
+    };
+    // pyramid rows (DMX_CONTACT_APPROX1): friction row d of a contact whose mode has bit APPROX1_d and whose mu_d is positive and finite.
     // A tick that has one launches the kernels' APX instantiations; a tick without one launches what it launched before they existed.
-    auto pyramid_bits = [](const dmxContactJoint &j) { return (j.mu > 0 && j.mu < __builtin_huge_val()) ? (j.mode & DMX_CONTACT_APPROX1) : 0; };
+    auto pyramid_bits = [&](const dmxContactJoint &j) {
+        if (!surfaces) return (j.mu > 0 && j.mu < inf_d) ? (j.mode & DMX_CONTACT_APPROX1) : 0;
+        const double m1 = mu_row(j, 1), m2 = mu_row(j, 2);
+        return ((m1 > 0 && m1 < inf_d) ? (j.mode & DMX_CONTACT_APPROX1_1) : 0) | ((m2 > 0 && m2 < inf_d) ? (j.mode & DMX_CONTACT_APPROX1_2) : 0);
+    };
     bool pyramid = false;
+    // an extended tick: some contact that survives brings a bit of DMX_CONTACT_SURFACE_EXT along with its surface.  It takes the APX
+    // instantiations too, and stages EXT_REALS more reals per entry (IslandSet::cext); every other tick does neither.
+    auto extended_bits = [&](const dmxContactJoint &j) { return surfaces ? (j.mode & DMX_CONTACT_SURFACE_EXT) : 0; };
+    bool extended = false;
     for (int64_t k = 0; k < nj_in; k++) {
         const dmxContactJoint &j = joints[k];
         int b1 = live(j.body1) ? j.body1 : -1, b2 = live(j.body2) ? j.body2 : -1;
@@ -141,6 +171,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         DmxCanonicalJoint c; c.b1 = b1; c.b2 = b2; c.j = &j; c.rev = rev;
         cj.push_back(c);
         if (pyramid_bits(j)) pyramid = true;
+        if (extended_bits(j)) extended = true;
     }
     // ---- auto-disable: an island without an awake body is left out of the tick, whole; in an awake island every member is awake.
     // Only while some live slot is asleep: a batch without one does nothing here but compare a count.
@@ -168,12 +199,12 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         if (!ad_dropped.empty()) {
             // their joints make no rows: the entries go before anything is counted, scheduled or staged (order kept: units first)
             size_t keep = 0;
-            n_units = 0; n_limots = 0; pyramid = false;
+            n_units = 0; n_limots = 0; pyramid = false; extended = false;
             for (size_t k = 0; k < cj.size(); k++) {
                 const CJ &c = cj[k];
                 if (!awake[(size_t)uf.find(c.b1)]) continue;
                 if (c.unit) { n_units++; if (c.unit == UNIT_LIMOT || c.unit == UNIT_SLIMOT) n_limots++; }
-                else if (pyramid_bits(*c.j)) pyramid = true;
+                else { if (pyramid_bits(*c.j)) pyramid = true; if (extended_bits(*c.j)) extended = true; }
                 cj[keep++] = c;
             }
             cj.resize(keep);
@@ -200,6 +231,20 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         b->fb_valid = fb_was_valid;
         return DMX_EINVAL;
     }
+    if (extended && b->row_order_ode && !exact) {
+        fprintf(stderr, "libode_mi355: dmxBatchStepJointsSurface under DMX_ORDER_ODE with QuickStep does not honour mu2, fdir1, motion or slip "
+                        "(DMX_CONTACT_SURFACE_EXT): use DMX_ORDER_CREATION\n");
+        b->fb_valid = fb_was_valid;
+        return DMX_EINVAL;
+    }
+    // (a guard only: no caller that steps a subset comes with surfaces -- dmxBatchStepJointsSurface alone passes them, with neither
+    //  `include` nor `geo` -- so this refusal cannot be reached through the public interface, and has no test for that reason)
+    if (extended && (include || geo)) {
+        fprintf(stderr, "libode_mi355: a tick of a subset of the bodies does not honour mu2, fdir1, motion or slip (DMX_CONTACT_SURFACE_EXT)\n");
+        b->fb_valid = fb_was_valid;
+        return DMX_EINVAL;
+    }
+    const bool apx = pyramid || extended;       // the kernels' APX instantiations: a tick whose contacts carry more than box friction
 
     // ---- the bodies this tick steps, ascending: the caller's subset (`include`, with its list) or every live slot ----
     std::vector<int> &slots = b->sc_slots;
@@ -436,7 +481,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     else if (ni > SMALL_MAX_ISLANDS) why = DMX_SMALL_TICK_STAT_ISLANDS;
     else if (!exact && big_max_rows > WAVE_ISLAND_ROWS) why = DMX_SMALL_TICK_STAT_SOR_ROWS;            // (the one-wavefront form of solve_island_wg)
     else if (exact && !grid_list.empty()) why = DMX_SMALL_TICK_STAT_LDS_FIT;
-    else if (exact && pyramid) why = DMX_SMALL_TICK_STAT_LDS_FIT;      // (dWorldStep's two passes: the general path's kernels only)
+    else if (exact && apx) why = DMX_SMALL_TICK_STAT_LDS_FIT;      // (dWorldStep's two passes, and its APX rows: the general path's kernels only)
     const bool small = why < 0;
     b->small_stats[small ? DMX_SMALL_TICK_STAT_SMALL : DMX_SMALL_TICK_STAT_GENERAL]++;
     if (!small) b->small_stats[why]++;
@@ -449,7 +494,8 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // feedback: 12 reals per joint of the set and per contact joint given; a small tick keeps them behind its tables' reals
     const size_t n_fb = fb ? (size_t)12 * (b->art.size() + (size_t)nj_in) : 0;
     // real staging: cpos[3nc] cnormal[3nc] cdepth cmu cbounce cbounce_vel csoft_erp csoft_cfm [nc each]
-    const size_t n_real = (size_t)12 * nc;
+    //               and in an extended tick cext[EXT_REALS nc] behind them
+    const size_t n_real = (size_t)(extended ? 12 + EXT_REALS : 12) * nc;
     int rc;
     int *hi; T *hr;
     const int sp = b->sm_parity;
@@ -490,7 +536,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         memcpy(lev_rows + lev_rows_h.size(), lvl_all.data(), lev_rows_h.size() * sizeof(int));      // row_level, same layout
     }
     T *cpos = hr, *cnormal = cpos + 3 * (size_t)nc, *cdepth = cnormal + 3 * (size_t)nc, *cmu = cdepth + nc,
-      *cbounce = cmu + nc, *cbv = cbounce + nc, *cserp = cbv + nc, *cscfm = cserp + nc;
+      *cbounce = cmu + nc, *cbv = cbounce + nc, *cserp = cbv + nc, *cscfm = cserp + nc, *cext = extended ? cscfm + nc : nullptr;
 
     // a slider's limot entry reads its anchors from the entry before it, which must be its own joint's linear unit: units are
     // emitted back to back and the sort by island is stable (and the ODE row order, which is not, is refused with joints set)
@@ -520,6 +566,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         dmx_parallel_for(nc, 8192, [&](int64_t lo, int64_t hi, int) {
             for (int64_t d = lo; d < hi; d++) {
                 const CJ &c = cj[(size_t)con_sorted[(size_t)d]];
+                if (cext) for (int k = 0; k < EXT_REALS; k++) cext[(size_t)EXT_REALS * (size_t)d + k] = T(0);      // (a unit's are never read)
                 if (c.unit) {
                     // a unit's six reals ride in the contact arrays: the first side's anchor (axis) where a contact has its
                     // position, the second side's where it has its normal; cmu says which unit it is
@@ -573,7 +620,8 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                     continue;
                 }
                 const dmxContactJoint &j = *c.j;
-                cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = j.mode;
+                // (with surfaces, bit SURF_EXT_MU1_ZERO of the staged mode is the host's own: a stray one in the caller's mode goes)
+                cb1[d] = c.b1; cb2[d] = c.b2; cmode[d] = surfaces ? (j.mode & ~SURF_EXT_MU1_ZERO) : j.mode;
                 csrc[d] = geo ? geo->src[(size_t)(c.j - joints)] : 0;
                 for (int k = 0; k < 3; k++) {
                     cpos[3 * (size_t)d + k] = (T)j.pos[k];
@@ -583,6 +631,20 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                 cdepth[d] = (T)j.depth; cmu[d] = (T)j.mu; cbounce[d] = (T)j.bounce; cbv[d] = (T)j.bounce_vel;
                 cserp[d] = (T)j.soft_erp; cscfm[d] = (T)j.soft_cfm;
                 if (n_units && j.mu < 0) cmu[d] = T(0);      // (what the kernels make of it anyway; below zero marks a unit)
+                if (cext) {
+                    // the extended surface, resolved: what a bit selects, or what the row is without it (dmx_internal.hpp at EXT_MU2)
+                    const dmxContactSurface &sf = surfaces[&j - joints];
+                    T *e = cext + (size_t)EXT_REALS * (size_t)d;
+                    const double m1 = mu_row(j, 1), m2 = mu_row(j, 2);
+                    if (!(m1 > 0) && m2 > 0) { cmu[d] = (T)m2; cmode[d] |= SURF_EXT_MU1_ZERO; }      // (three rows wherever cmu counts them)
+                    e[EXT_MU2] = (T)m2;
+                    if (j.mode & DMX_CONTACT_FDIR1) for (int k = 0; k < 3; k++) e[EXT_FDIR1 + k] = (T)sf.fdir1[k];
+                    if (j.mode & DMX_CONTACT_MOTION1) e[EXT_MOTION1] = (T)sf.motion1;      // (no motion changes sign where the sides were exchanged: the header's rule)
+                    if (j.mode & DMX_CONTACT_MOTION2) e[EXT_MOTION2] = (T)sf.motion2;
+                    if (j.mode & DMX_CONTACT_MOTIONN) e[EXT_MOTIONN] = (T)sf.motionN;
+                    e[EXT_SLIP1] = (j.mode & DMX_CONTACT_SLIP1) ? (T)sf.slip1 : T(-1);
+                    e[EXT_SLIP2] = (j.mode & DMX_CONTACT_SLIP2) ? (T)sf.slip2 : T(-1);
+                }
             }
         });
     }
@@ -636,9 +698,10 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     I.gdepth = geo ? (const T *)geo->depth : nullptr;
     I.cpos = dr; I.cnormal = dr + 3 * (size_t)nc; I.cdepth = I.cnormal + 3 * (size_t)nc; I.cmu = I.cdepth + nc;
     I.cbounce = I.cmu + nc; I.cbounce_vel = I.cbounce + nc; I.csoft_erp = I.cbounce_vel + nc; I.csoft_cfm = I.csoft_erp + nc;
+    I.cext = extended ? I.csoft_cfm + nc : nullptr;
     I.rows = (T *)b->jd_rows.p; I.rowjb = (int *)b->jd_rowjb.p; I.bscr = (T *)b->jd_bscr.p; I.local = (int *)b->jd_local.p;
     I.singles = (exact || ode_order) ? 0 : 1;
-    if (pyramid) I.singles = 0;      // (the one-body forms know box friction only: solve_islands' row form takes their islands, as with feedback on)
+    if (apx) I.singles = 0;      // (the one-body forms know box friction only: solve_islands' row form takes their islands, as with feedback on)
     FeedbackSet<T> F;
     if (fb) {
         // every solve must leave lambda in the row table: the one-body forms keep their rows in registers, so their islands take
@@ -742,7 +805,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             K.ad_flags = b->bflags; K.ad_mirror = b->ad_mirror_dev;
             K.ad_steps = b->ad_steps_dev; K.ad_time = b->ad_time_dev; K.ad = ad_params;
         }
-        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream, pyramid, ad_kernel));
+        HIP_TRY(launch_small_tick<T>((T *)b->slab, b->bflags, b->stride, I, P, b->sm_diag + cur, K, F, exact, lds, b->stream, apx, ad_kernel));
         HIP_TRY(hipEventRecord(b->sm_ev[sp], b->stream));
         if (ad_tick) { b->ad_wait_ev = b->sm_ev[sp]; b->ad_pending = true; }      // (the tick's own event gates the flag mirror too)
         b->sm_ev_pending[sp] = true;
@@ -762,7 +825,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     HIP_TRY(hipMemsetAsync(b->diag_isl, 0, sizeof(StepDiag), b->stream));
     if (exact) {
         HIP_TRY(launch_islands_without_rows<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream));
-        HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream, pyramid));
+        HIP_TRY(launch_lcp_lds<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, lds_need, b->stream, apx));
         // Written for a copy from pageable host memory that is gone; but the grid solves' host loop below and the next tick's
         // rewrite of the host staging have run behind this wait ever since, and no test tells a missing wait from a present one.
         // Taking it out is a change of speed, to be made and measured on its own.
@@ -773,7 +836,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             lcp_grid_begin_tick(b);
             LcpIslandRows R;
             R.limots = n_limots > 0;
-            R.pyramid_tick = pyramid;
+            R.pyramid_tick = apx;
             std::vector<std::pair<uint64_t, int>> &ord = b->sc_pair_ord;
             for (int isl : grid_list) {
                 R.isl = isl; R.m = b->sc_iv[10][(size_t)isl]; R.row_base = 3 * con_start[(size_t)isl];
@@ -797,7 +860,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                         // (a limot's row: low bits 1, as a bounded friction row's -- clamped, its value need not be zero.  The
                         //  ordinal within the pair is stable while the set and the limots' presence are)
                         R.key[(size_t)(r + q)] = base | (uint64_t)(is_limot(c.unit) ? 1 : q);
-                        R.unbounded[(size_t)(r + q)] = c.unit ? !is_limot(c.unit) : (q > 0 && !(c.j->mu < __builtin_huge_val()));
+                        R.unbounded[(size_t)(r + q)] = c.unit ? !is_limot(c.unit) : (q > 0 && !((surfaces ? mu_row(*c.j, q) : c.j->mu) < inf_d));
                         if (!c.unit && q > 0 && (pyramid_bits(*c.j) & (DMX_CONTACT_APPROX1_1 << (q - 1)))) { R.pyramid_row[(size_t)(r + q)] = 1; R.pyramid = true; }
                     }
                 }
@@ -835,7 +898,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         }
         if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
     } else {
-        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb, pyramid));
+        HIP_TRY(launch_islands<T>((T *)b->slab, b->bflags, b->stride, I, P, b->diag_isl, b->stream, fb, apx));
         if (fb) HIP_TRY(launch_feedback<T>(I, P, F, nc, b->stream));
         if (ode_order) HIP_TRY(hipStreamSynchronize(b->stream));      // the order table came from pageable host memory
     }
@@ -857,11 +920,11 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
 }  // namespace
 
 int dmx_step_joints(dmxBatch *b, double h, int64_t n_joints, const dmxContactJoint *joints, const uint8_t *include,
-                    const DevGeometry *geo)
+                    const DevGeometry *geo, const dmxContactSurface *surfaces)
 {
     b->fix.brk();       // the joints tick, single-launch or not, steps bodies behind the fixed-axis words' back (dmx_fixed.hpp)
-    return b->precision == DMX_F32 ? step_joints_t<float>(b, h, n_joints, joints, include, geo)
-                                   : step_joints_t<double>(b, h, n_joints, joints, include, geo);
+    return b->precision == DMX_F32 ? step_joints_t<float>(b, h, n_joints, joints, include, geo, surfaces)
+                                   : step_joints_t<double>(b, h, n_joints, joints, include, geo, surfaces);
 }
 
 extern "C" int dmxBatchStepJoints(dmxBatchID b, double h, int64_t n_joints, const dmxContactJoint *joints)
@@ -875,4 +938,43 @@ extern "C" int dmxBatchStepJoints(dmxBatchID b, double h, int64_t n_joints, cons
         return DMX_EINVAL;
     }
     return dmx_step_joints(b, h, n_joints, joints, nullptr, nullptr);
+}
+
+// dmxBatchStepJoints with the rest of ODE's contact surface beside every joint (include/dmx_batch.h at DMX_CONTACT_MU2)
+extern "C" int dmxBatchStepJointsSurface(dmxBatchID b, double h, int64_t n_joints, const dmxContactJoint *joints, const dmxContactSurface *surfaces)
+{
+    if (!surfaces) return dmxBatchStepJoints(b, h, n_joints, joints);
+    if (!b || !(h > 0) || n_joints < 0 || (n_joints > 0 && !joints)) return DMX_EINVAL;
+    // the fields the tick would read, before anything is touched -- as the device will hold them: in a float32 batch a double above
+    // float's largest is an infinity there, and is refused as one
+    const double inf = __builtin_huge_val();
+    const bool f32 = b->precision == DMX_F32;
+    auto held = [&](double x) { return f32 ? (double)(float)x : x; };
+    auto finite = [&](double x) { x = held(x); return x > -inf && x < inf; };
+    for (int64_t k = 0; k < n_joints; k++) {
+        const int mode = joints[k].mode;
+        if (!(mode & DMX_CONTACT_SURFACE_EXT)) continue;
+        dmxContactSurface s = surfaces[k];
+        s.slip1 = held(s.slip1); s.slip2 = held(s.slip2);
+        const char *what = nullptr;
+        if ((mode & DMX_CONTACT_MU2) && s.mu2 != s.mu2) what = "mu2 is NaN";
+        else if ((mode & DMX_CONTACT_FDIR1) && !(finite(s.fdir1[0]) && finite(s.fdir1[1]) && finite(s.fdir1[2]))) what = "fdir1 is not finite";
+        else if ((mode & DMX_CONTACT_MOTION1) && !finite(s.motion1)) what = "motion1 is not finite";
+        else if ((mode & DMX_CONTACT_MOTION2) && !finite(s.motion2)) what = "motion2 is not finite";
+        else if ((mode & DMX_CONTACT_MOTIONN) && !finite(s.motionN)) what = "motionN is not finite";
+        else if ((mode & DMX_CONTACT_SLIP1) && !(s.slip1 >= 0 && s.slip1 < inf)) what = "slip1 is negative or not finite";
+        else if ((mode & DMX_CONTACT_SLIP2) && !(s.slip2 >= 0 && s.slip2 < inf)) what = "slip2 is negative or not finite";
+        if (what) {
+            fprintf(stderr, "libode_mi355: dmxBatchStepJointsSurface: contact joint %lld: %s\n", (long long)k, what);
+            return DMX_EINVAL;
+        }
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if (b->row_order_ode && !b->stepper_exact && !b->art.empty()) {      // (as dmxBatchStepJoints)
+        fprintf(stderr, "libode_mi355: dmxBatchStepJoints under DMX_ORDER_ODE does not honour articulation joints (dmxBatchSetJoints): "
+                        "%lld are set\n", (long long)b->art.size());
+        return DMX_EINVAL;
+    }
+    return dmx_step_joints(b, h, n_joints, joints, nullptr, nullptr, surfaces);
 }

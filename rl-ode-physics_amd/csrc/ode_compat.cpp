@@ -131,6 +131,7 @@ struct dxWorld {
     std::vector<double> dev_statics;   // the static boxes the device holds (18 doubles each), for the device pair search
     std::vector<dReal> buf;
     std::vector<dmxContactJoint> cj;
+    std::vector<dmxContactSurface> cs;         // the rest of the tick's surfaces; handed over only when some contact sets one of its bits
     // auto-disable (dWorldSetAutoDisable*).  The four values are the world's and hold for all its bodies (stock ODE copies them
     // into a body at creation); the flag is what dBodyCreate copies.  ad_dirty: the batch has not been told the values yet.
     // n_ad: bodies whose flags carry DMX_BODY_AUTODISABLE or DMX_BODY_DISABLED -- only while there is one does to_host() ask the
@@ -460,6 +461,8 @@ static int world_step(dWorldID w, dReal h, int stepper)
         w->limot_dirty = false;
     }
     w->cj.clear();
+    w->cs.clear();
+    bool extended = false;      // dContactMu2 / FDir1 / Motion1 / 2 / N / Slip1 / 2 somewhere in this tick's contacts
     for (const dxJoint *j : w->joints) {
         dmxContactJoint c;
         const dContact &ct = j->contact;
@@ -471,15 +474,26 @@ static int world_step(dWorldID w, dReal h, int stepper)
         c.mu = ct.surface.mu; c.bounce = ct.surface.bounce; c.bounce_vel = ct.surface.bounce_vel;
         c.soft_erp = ct.surface.soft_erp; c.soft_cfm = ct.surface.soft_cfm;
         w->cj.push_back(c);
+        dmxContactSurface sf;
+        sf.mu2 = ct.surface.mu2; sf.motion1 = ct.surface.motion1; sf.motion2 = ct.surface.motion2; sf.motionN = ct.surface.motionN;
+        sf.slip1 = ct.surface.slip1; sf.slip2 = ct.surface.slip2;
+        for (int k = 0; k < 3; k++) sf.fdir1[k] = ct.fdir1[k];
+        w->cs.push_back(sf);
+        if (c.mode & DMX_CONTACT_SURFACE_EXT) extended = true;
     }
     // feedback: on in the batch only while some joint of the world has a struct set -- a world without one ticks as it always did
     const bool feedback = w->n_feedback > 0;
     if (feedback != w->feedback_sent) { DMX_MUST(dmxBatchSetFeedback(w->batch, feedback ? 1 : 0)); w->feedback_sent = feedback; }
     {
-        const int rc = dmxBatchStepJoints(w->batch, h, (int64_t)w->cj.size(), w->cj.data());
+        // (a tick none of whose contacts sets one of the seven bits makes the call it always made)
+        const int rc = extended ? dmxBatchStepJointsSurface(w->batch, h, (int64_t)w->cj.size(), w->cj.data(), w->cs.data())
+                                : dmxBatchStepJoints(w->batch, h, (int64_t)w->cj.size(), w->cj.data());
         // ball / hinge joints under DMX_ROW_ORDER=ode with QuickStep: the batch has said so on stderr; the step fails, the process lives
         if (rc == DMX_EINVAL && !w->arts.empty()) return 0;
-        if (rc != DMX_OK) fatal("dmxBatchStepJoints", rc);
+        // an extended surface the batch refuses (a NaN, a negative or infinite slip, an infinite motion or fdir1 in a dContact; such a
+        // tick under DMX_ROW_ORDER=ode with QuickStep): likewise -- one line on stderr from the batch, the bodies where they were
+        if (rc == DMX_EINVAL && extended) return 0;
+        if (rc != DMX_OK) fatal(extended ? "dmxBatchStepJointsSurface" : "dmxBatchStepJoints", rc);
     }
     w->dev_newer = true;
     if (feedback) {
