@@ -453,7 +453,7 @@ int dmxBatchSmallTickStats(dmxBatchID b, int64_t out[DMX_SMALL_TICK_NSTATS]);
 enum { DMX_ORDER_CREATION = 0, DMX_ORDER_ODE = 1 };
 int dmxBatchSetRowOrder(dmxBatchID b, int order, uint32_t seed);
 
-/* ---- articulation joints: ball-and-socket and hinge (dJointCreateBall / dJointCreateHinge); slider and fixed: further below.  Unlike contact joints, which
+/* ---- articulation joints: ball-and-socket and hinge (dJointCreateBall / dJointCreateHinge); slider and fixed, and angular motors: further below.  Unlike contact joints, which
  * live for one tick, the set given to dmxBatchSetJoints persists until it is replaced and takes part in every
  * dmxBatchStepJoints tick -- both steppers, both precisions, the general path and the single-launch tick of small worlds.
  * Anchors and axes are stored in the frames of the two bodies (world frame for a side that is -1, the world).
@@ -548,6 +548,59 @@ int dmxBatchHingeAngles(dmxBatchID b, double *angle, double *rate);
 /* s and s_dot per joint of the set, from the current state, computed on the device in the batch's precision (other kinds and
  * inactive joints report 0); either array may be NULL */
 int dmxBatchSliderPositions(dmxBatchID b, double *pos, double *rate);
+
+/* ---- angular motors (dJointCreateAMotor): DMX_JOINT_AMOTOR in dmxBatchSetJoints, usually beside a ball joint on the same two bodies.
+ * An AMotor is a joint of the set like every other -- island building, row order, the activity rules, auto-disable, damping, feedback --
+ * but its dmxJoint anchors and axes and its entry in dmxBatchSetHingeLimots are ignored: its own data is its dmxAMotor, one entry per
+ * joint of the set in a table that runs beside it (dmxBatchSetAMotors), read for this kind only.  R_i = side i's rotation, the identity
+ * for a world side; everything is in the sides AS GIVEN.
+ *   user mode   num_axes = 1..3.  a_i = axis[i] turned by the rotation of the side rel[i] names (0: the world, as given; 1: side 1;
+ *               2: side 2; a world side's frame is the world).  theta_i = angle[i], as the caller supplies it.
+ *   Euler mode  num_axes = 3.  a_0 = R_1 axis[0], a_2 = R_2 axis[2], a_1 = (a_2 x a_0) / |a_2 x a_0| (the zero vector when that length
+ *               is 0: nothing becomes NaN; keeping theta_1 away from +-pi/2 is the caller's duty, by stops, as in ODE).
+ *               r_1 = R_1 ref1, r_2 = R_2 ref2, and
+ *                   theta_0 = -atan2(a_2 . (a_0 x r_1), a_2 . r_1)
+ *                   theta_1 = -atan2(a_2 . a_0, a_2 . (a_0 x a_1))
+ *                   theta_2 = -atan2(r_2 . a_1, r_2 . (a_1 x a_2))           [ODE-recall: amotorComputeEulerAngles]
+ *               With Z the zero pose (where ref1 = R_1^T a_2, ref2 = R_2^T a_0 were taken) and a_1 = a_2 x a_0 there: side 1 standing
+ *               at Rot(a_2, theta_2) Rot(a_1, theta_1) Rot(a_0, theta_0) relative to where it stood against side 2 has these angles;
+ *               each grows when side 1 turns about +a_i against side 2, the hinge angle's sign.
+ *   rows        axis i < num_axes has one row when its limot is PRESENT by the hinge's rule: fmax[i] > 0 or a finite stop.  Rows come
+ *               in axis order, each a unit of one row.  In the sides as given J = [ 0, a_i | 0, -a_i ] (after an exchange of sides
+ *               both angular blocks change sign); c, lo, hi from the hinge's five-line table above with theta_i, k = ERP / h, cfm = the
+ *               world's.  The axes and angles are those at the tick's start.
+ *   rate        the row's velocity a_i . (omega_1 - omega_2): exactly theta_1's derivative for the middle Euler axis, for axes 0 and
+ *               2 theta_i's only near theta_1 = 0 [ODE-recall: ODE builds the same rows].  dmxBatchAMotorAngles reports exactly this
+ *               quantity as the rate -- the velocity the row acts on, not d theta_i / dt.
+ * An AMotor none of whose limots is present makes no row; it still links its two bodies into one island.  A tick whose set holds no
+ * AMotor with a present limot stages, launches and loads exactly what it did before this kind existed.
+ * Out of scope: dJointCreateLMotor; dParamFudgeFactor, dParamBounce, dParamCFM, dParamStopERP, dParamStopCFM (fudge 1, no bounce, the
+ * world's ERP / CFM, as for the hinge); an Euler-mode angle with a world side on both ends (such a joint is inactive anyway). */
+enum { DMX_JOINT_AMOTOR = 5 };
+enum { DMX_AMOTOR_USER = 0, DMX_AMOTOR_EULER = 1 };          /* dAMotorUser, dAMotorEuler */
+typedef struct dmxAMotor {
+    int32_t mode, num_axes;        /* user: 1..3; Euler: 3 */
+    int32_t rel[3], pad;           /* user mode: the frame axis[i] is given in: 0 the world, 1 side 1, 2 side 2 (sides AS GIVEN; a world side's frame is the world) */
+    double axis[3][3];             /* user: unit axes.  Euler: axis[0] in the frame of side 1, axis[2] in the frame of side 2, axis[1] ignored */
+    double ref1[3], ref2[3];       /* Euler: reference vectors in the frames of side 1 / side 2 */
+    double angle[3];               /* user mode: the angle the caller supplies per axis (dJointSetAMotorAngle); Euler: ignored */
+    double lo_stop[3], hi_stop[3], vel[3], fmax[3];
+} dmxAMotor;
+/* one entry per joint of the current set, whatever its kind (only an AMotor's is read and checked); n must equal dmxBatchJointCount
+ * or be 0 (removes them: every AMotor of the set then makes no row); copied; may be replaced every tick; dmxBatchSetJoints drops it.
+ * DMX_EINVAL, one line on stderr, nothing changed: another n; for an AMotor's entry a mode or num_axes out of range, Euler with
+ * num_axes != 3, a rel outside 0..2, a non-finite axis, reference, angle, vel or fmax, a NaN stop. */
+int dmxBatchSetAMotors(dmxBatchID b, int64_t n, const dmxAMotor *motors);
+/* an entry from world-frame axes at the bodies' CURRENT poses (what dJointSetAMotorAxis means): axes are normalised; user mode stores
+ * axis[i] in the frame rel[i] names; Euler mode (rel ignored) stores axis[0] in side 1's frame, axis[2] in side 2's, and the
+ * reference vectors ref1 = R_1^T a_2, ref2 = R_2^T a_0: "this pose is angles zero".  Stops -+inf, vel = fmax = angle = 0.
+ * DMX_EINVAL: a bad mode, num_axes, rel or slot, a zero or non-finite axis, Euler axes 0 and 2 not perpendicular (|a_0 . a_2| > 1e-9). */
+int dmxBatchAMotorFromWorld(dmxBatchID b, int32_t body1, int32_t body2, int mode, int num_axes, const int32_t rel[3],
+                            const double axes_w[3][3], dmxAMotor *out);
+/* three angles and three rates per joint of the set, from the current state, computed on the device in the batch's precision by the
+ * kernel that prepares a tick's AMotor rows; other kinds, unused axes and inactive joints report 0; either array may be NULL.  The
+ * rate is a_i . (omega_1 - omega_2), see "rate" above.  Without dmxBatchSetAMotors everything reports 0. */
+int dmxBatchAMotorAngles(dmxBatchID b, double *angles3, double *rates3);
 
 /* ---- feedback: the force and torque every joint and contact joint applied in the last tick (dJointSetFeedback).
  * A constraint with rows r = 0..m-1 in canonical sides has, per row, the Jacobian J_r = [ Jl1, Ja1 | Jl2, Ja2 ] at the tick's start,

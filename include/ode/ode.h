@@ -259,7 +259,8 @@ void dJointAttach(dJointID, dBodyID body1, dBodyID body2);       /* main.c:691 *
  * parameters print one line to stderr and are ignored on set, and read as 0.  dJointSetHingeAnchor / dJointSetHingeAxis take the
  * bodies' current relative pose as angle zero, as ODE does.  Angle, rate, stops, motor and dJointAddHingeTorque are those of the
  * sides as attached: body 1 relative to body 2 about the axis, also after dJointAttach(j, 0, body).  Balls have none of these. */
-enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeSlider = 3, dJointTypeContact = 4, dJointTypeFixed = 7 };
+enum { dJointTypeNone = 0, dJointTypeBall = 1, dJointTypeHinge = 2, dJointTypeSlider = 3, dJointTypeContact = 4, dJointTypeFixed = 7,
+       dJointTypeAMotor = 9 };
 dJointID dJointCreateBall(dWorldID, dJointGroupID);
 dJointID dJointCreateHinge(dWorldID, dJointGroupID);
 dJointID dJointCreateSlider(dWorldID, dJointGroupID);
@@ -278,6 +279,14 @@ void dJointGetHingeAxis(dJointID, dVector3 result);
 /* [ODE-recall common.h D_ALL_PARAM_NAMES, 0.13 - 0.16] */
 enum { dParamLoStop = 0, dParamHiStop, dParamVel, dParamLoVel, dParamHiVel, dParamFMax, dParamFudgeFactor, dParamBounce, dParamCFM,
        dParamStopERP, dParamStopCFM, dParamSuspensionERP, dParamSuspensionCFM, dParamERP };
+/* the second and third axis of a joint with several (an angular motor): dParamXxx2 = dParamGroup + dParamXxx, dParamXxx3 = 2 dParamGroup + dParamXxx */
+enum { dParamGroup = 0x100 };
+enum { dParamLoStop1 = 0x000, dParamHiStop1, dParamVel1, dParamLoVel1, dParamHiVel1, dParamFMax1, dParamFudgeFactor1, dParamBounce1, dParamCFM1,
+       dParamStopERP1, dParamStopCFM1, dParamSuspensionERP1, dParamSuspensionCFM1, dParamERP1 };
+enum { dParamLoStop2 = 0x100, dParamHiStop2, dParamVel2, dParamLoVel2, dParamHiVel2, dParamFMax2, dParamFudgeFactor2, dParamBounce2, dParamCFM2,
+       dParamStopERP2, dParamStopCFM2, dParamSuspensionERP2, dParamSuspensionCFM2, dParamERP2 };
+enum { dParamLoStop3 = 0x200, dParamHiStop3, dParamVel3, dParamLoVel3, dParamHiVel3, dParamFMax3, dParamFudgeFactor3, dParamBounce3, dParamCFM3,
+       dParamStopERP3, dParamStopCFM3, dParamSuspensionERP3, dParamSuspensionCFM3, dParamERP3 };
 void dJointSetHingeParam(dJointID, int parameter, dReal value);
 dReal dJointGetHingeParam(dJointID, int parameter);
 dReal dJointGetHingeAngle(dJointID);
@@ -298,6 +307,33 @@ void dJointSetSliderParam(dJointID, int parameter, dReal value);
 dReal dJointGetSliderParam(dJointID, int parameter);
 void dJointAddSliderForce(dJointID, dReal force);
 void dJointSetFixed(dJointID);
+/* Angular motors (include/dmx_batch.h, DMX_JOINT_AMOTOR), usually beside a ball joint on the same two bodies.  dAMotorUser: one to three
+ * axes, each given in world coordinates and kept in the frame `rel` names (0: the world, 1: the first body, 2: the second), with the
+ * angle the caller supplies (dJointSetAMotorAngle).  dAMotorEuler: three axes; axis 0 goes with the first body and axis 2 with the
+ * second (they must be perpendicular when they are set), axis 1 and the three Euler angles are computed; the pose at which axis 0 or 2
+ * is set, with both known, is angles zero.  Every axis has a stop and a motor: dJointSetAMotorParam honours dParamLoStop, dParamHiStop,
+ * dParamVel and dParamFMax and their ...2 / ...3 groups; the other parameters print one line to stderr and are ignored on set, and read
+ * as 0 (dParamFudgeFactor, dParamBounce, dParamCFM, dParamStopERP, dParamStopCFM: fudge 1, no bounce, the world's ERP / CFM, as for the
+ * hinge).  dJointGetAMotorAngleRate is a_i . (omega_1 - omega_2), the velocity the axis's row acts on: the angle's own rate for the
+ * middle Euler axis, for axes 0 and 2 only near a middle angle of 0.  Axes, angles, rates, stops, motors and dJointAddAMotorTorques
+ * (+sum t_i a_i on the first body, the opposite on the second) are those of the sides as attached, also after dJointAttach(j, 0, body).
+ * dJointSetFeedback reports torques only: the forces are zero.  Not provided: dJointCreateLMotor; an Euler-mode angle with the world
+ * on both ends. */
+enum { dAMotorUser = 0, dAMotorEuler = 1 };
+dJointID dJointCreateAMotor(dWorldID, dJointGroupID);
+void dJointSetAMotorMode(dJointID, int mode);
+int dJointGetAMotorMode(dJointID);
+void dJointSetAMotorNumAxes(dJointID, int num);
+int dJointGetAMotorNumAxes(dJointID);
+void dJointSetAMotorAxis(dJointID, int anum, int rel, dReal x, dReal y, dReal z);
+void dJointGetAMotorAxis(dJointID, int anum, dVector3 result);
+int dJointGetAMotorAxisRel(dJointID, int anum);
+void dJointSetAMotorAngle(dJointID, int anum, dReal angle);
+dReal dJointGetAMotorAngle(dJointID, int anum);
+dReal dJointGetAMotorAngleRate(dJointID, int anum);
+void dJointSetAMotorParam(dJointID, int parameter, dReal value);
+dReal dJointGetAMotorParam(dJointID, int parameter);
+void dJointAddAMotorTorques(dJointID, dReal torque1, dReal torque2, dReal torque3);
 /* The force and torque a joint applied to its two bodies during the last dWorldStep / dWorldQuickStep, about each body's centre,
  * in world coordinates (ODE's layout and meaning; include/dmx_batch.h at dmxBatchSetFeedback has the definition).  The struct is
  * the caller's; a step fills it before it returns, for ball, hinge, slider and fixed joints and for contact joints created in the

@@ -28,12 +28,23 @@ BATCH_SYMBOLS = [
     "dmxBatchRayCast", "dmxBatchRayCastDevice", "dmxBatchSetRayForm",
     "dmxBatchSetJoints", "dmxBatchJointCount", "dmxBatchJointFromWorld", "dmxBatchJointErrors",
     "dmxBatchSetHingeLimots", "dmxBatchHingeLimotInit", "dmxBatchHingeAngles", "dmxBatchSliderPositions",
+    "dmxBatchSetAMotors", "dmxBatchAMotorFromWorld", "dmxBatchAMotorAngles",
     "dmxBatchSetFeedback", "dmxBatchJointFeedback", "dmxBatchContactFeedback", "dmxBatchFeedbackDevice",
     "dmxBatchSetAutoDisable", "dmxBatchGetAutoDisable", "dmxBatchDownloadBodyFlags", "dmxBatchIdleCounters", "dmxBatchAutoDisableStats",
     "dmxBatchSetDamping", "dmxBatchSetMaxAngularSpeed", "dmxBatchUploadBodyDamping", "dmxBatchDownloadBodyDamping",
     "dmxBatchSetContactCorrection", "dmxBatchGetContactCorrection",
 ]
 SHARD_SYMBOLS = ["dmxShardRcclUniqueId", "dmxShardRcclInfo", "dmxShardCreateRccl", "dmxShardCreate", "dmxShardRun", "dmxShardSettle", "dmxShardStats", "dmxShardDestroy"]
+
+
+
+class dmxAMotor(C.Structure):
+    """dmxAMotor (include/dmx_batch.h): an angular motor's mode, axes, reference vectors, supplied angles, stops and motors;
+    tests/test_amotor_abi.py holds the layout to the C compiler's"""
+    _fields_ = [("mode", C.c_int32), ("num_axes", C.c_int32), ("rel", C.c_int32 * 3), ("pad", C.c_int32),
+                ("axis", (C.c_double * 3) * 3), ("ref1", C.c_double * 3), ("ref2", C.c_double * 3), ("angle", C.c_double * 3),
+                ("lo_stop", C.c_double * 3), ("hi_stop", C.c_double * 3), ("vel", C.c_double * 3), ("fmax", C.c_double * 3)]
+
 
 _lib = None
 
@@ -152,6 +163,9 @@ def load():
     sig("dmxBatchHingeLimotInit", I, P, P, P)
     sig("dmxBatchHingeAngles", I, P, P, P)
     sig("dmxBatchSliderPositions", I, P, P, P)
+    sig("dmxBatchSetAMotors", I, P, L, P)
+    sig("dmxBatchAMotorFromWorld", I, P, C.c_int32, C.c_int32, I, I, P, P, P)
+    sig("dmxBatchAMotorAngles", I, P, P, P)
     sig("dmxBatchSetFeedback", I, P, I)
     sig("dmxBatchJointFeedback", I, P, P)
     sig("dmxBatchContactFeedback", I, P, L, P)

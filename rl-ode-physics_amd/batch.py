@@ -61,6 +61,16 @@ HINGE_LIMOT_DTYPE = np.dtype({
     "formats": [np.float64, np.float64, np.float64, np.float64, (np.float64, 4)],
     "offsets": [0, 8, 16, 24, 32],
     "itemsize": 64})
+# dmxAMotor (include/dmx_batch.h; _lib.dmxAMotor is the same layout): an angular motor -- a joint of kind JOINT_AMOTOR -- one entry
+# per joint of the set (set_amotors)
+JOINT_AMOTOR = 5
+AMOTOR_USER, AMOTOR_EULER = 0, 1
+AMOTOR_DTYPE = np.dtype({
+    "names": ["mode", "num_axes", "rel", "pad", "axis", "ref1", "ref2", "angle", "lo_stop", "hi_stop", "vel", "fmax"],
+    "formats": [np.int32, np.int32, (np.int32, 3), np.int32, (np.float64, (3, 3)), (np.float64, 3), (np.float64, 3), (np.float64, 3),
+                (np.float64, 3), (np.float64, 3), (np.float64, 3), (np.float64, 3)],
+    "offsets": [0, 4, 8, 20, 24, 96, 120, 144, 168, 192, 216, 240],
+    "itemsize": 264})
 LCP_STATS = ("solves", "rounds", "max_rounds", "last_m", "last_nu", "last_nbd", "single", "fallback")
 # the single-launch tick of small worlds (dmxBatchSetSmallTick); the counters of dmxBatchSmallTickStats, in its order: ticks on
 # that path, step_joints ticks on the general path, then one count per reason a tick was not eligible
@@ -304,6 +314,35 @@ class BatchWorld:
         s, rate = np.zeros(n), np.zeros(n)
         _check(self.lib.dmxBatchSliderPositions(self.h, s.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchSliderPositions")
         return s, rate
+
+    # -- angular motors (dJointCreateAMotor): joints of kind JOINT_AMOTOR, their data in a table beside the set --
+    def set_amotors(self, arr):
+        """the angular motors' modes, axes, angles, stops and motors: an array of AMOTOR_DTYPE, one entry per joint of the set
+        (only an AMotor's is read); empty or None removes them.  May be replaced every tick; set_joints drops them"""
+        m = np.zeros(0, AMOTOR_DTYPE) if arr is None else np.ascontiguousarray(np.asarray(arr).astype(AMOTOR_DTYPE, copy=False)).reshape(-1)
+        _check(self.lib.dmxBatchSetAMotors(self.h, m.shape[0], m.ctypes.data if m.shape[0] else None), "dmxBatchSetAMotors")
+
+    def amotor_from_world(self, body1, body2, mode, axes, rel=(0, 0, 0), num_axes=None):
+        """an AMOTOR_DTYPE record from world-frame axes (up to three rows) at the bodies' current poses; -1 = the world.  Euler
+        mode takes axes 0 and 2 (perpendicular) and makes the current pose angles zero; stops -+inf, no motor"""
+        ax = np.zeros((3, 3))
+        a = np.atleast_2d(np.asarray(axes, np.float64))
+        ax[:a.shape[0]] = a
+        n = int(a.shape[0] if num_axes is None else num_axes)
+        r = np.ascontiguousarray(rel, np.int32).reshape(3)
+        out = np.zeros(1, AMOTOR_DTYPE)
+        _check(self.lib.dmxBatchAMotorFromWorld(self.h, int(body1), int(body2), int(mode), n, r.ctypes.data, ax.ctypes.data, out.ctypes.data),
+               "dmxBatchAMotorFromWorld")
+        return out[0]
+
+    def amotor_angles(self):
+        """-> (theta [n, 3], rate [n, 3]) of the set's joints at the current state, computed on the device by the kernel that
+        prepares a tick's AMotor rows (other kinds, unused axes and inactive joints: 0).  The rate is a_i . (omega_1 - omega_2),
+        the velocity the axis's row acts on; user mode echoes the supplied angles"""
+        n = self.joint_count()
+        th, rate = np.zeros((n, 3)), np.zeros((n, 3))
+        _check(self.lib.dmxBatchAMotorAngles(self.h, th.ctypes.data if n else None, rate.ctypes.data if n else None), "dmxBatchAMotorAngles")
+        return th, rate
 
     # -- feedback: what every joint and contact joint applied in the last tick (dJointSetFeedback) --
     def set_feedback(self, on):

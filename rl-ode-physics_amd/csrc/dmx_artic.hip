@@ -12,6 +12,7 @@
 
 #include "dmx_batch_priv.hpp"
 #include "dmx_island_rows.hpp"
+#include "dmx_amotor.hpp"
 
 namespace dmx {
 
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void joint_errors(const T *__restrict__ S, con
         const int s1 = j.body1, s2 = j.body2;
         auto alive = [&](int s) { return s < n_slots && (bflags[s] & BF_ALIVE) != 0; };
         const bool active = !(s1 < 0 && s2 < 0) && s1 != s2 && (s1 < 0 || alive(s1)) && (s2 < 0 || alive(s2));
-        if (active) {
+        if (active && j.kind != DMX_JOINT_AMOTOR) {       // (an angular motor has neither anchors nor an axis to be off: 0)
             auto side = [&](int s, const double *anchor, const double *axis, V3<T> &p, V3<T> &u) {
                 const V3<T> a = { (T)anchor[0], (T)anchor[1], (T)anchor[2] }, ax = { (T)axis[0], (T)axis[1], (T)axis[2] };
                 if (s < 0) { p = a; u = ax; return; }
@@ -145,6 +146,45 @@ __global__ __launch_bounds__(256) void slider_positions(const T *__restrict__ S,
     if (rate != nullptr) rate[k] = (double)sd;
 }
 
+// One lane per joint of the set: an active angular motor's three axes and three angles (amotor_axes) from the state as it stands --
+// in front of a tick's first kernel on the tick's stream, that is the state at the tick's start -- into the table the island kernels'
+// amotor_unit_row reads; every other joint's AMOTOR_PREP_REALS reals are zero.  rates (dmxBatchAMotorAngles only): a_i . (omega_1 - omega_2).
+// The host has checked the records' slots against the batch's size.
+template <class T>
+__global__ __launch_bounds__(256) void amotor_prepare(const T *__restrict__ S, int64_t stride, const AMotorIn *__restrict__ in, int nj, T kerp,
+                                                      T *__restrict__ prep, T *__restrict__ rates)
+{
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= nj) return;
+    V3<T> a[3];
+    for (int i = 0; i < 3; i++) a[i] = { T(0), T(0), T(0) };
+    const int s1 = in[k].body1, s2 = in[k].body2;
+    const bool active = in[k].active != 0;
+    T *o = prep + (size_t)AMOTOR_PREP_REALS * (size_t)k;
+    if (active) {
+        const Q4<T> ident = { T(1), T(0), T(0), T(0) };
+        amotor_prepare_joint<T>(s1 >= 0, s1 >= 0 ? ldq(S, s1) : ident, s2 >= 0, s2 >= 0 ? ldq(S, s2) : ident, in[k].m, kerp, o, a);
+    } else {
+        for (int i = 0; i < AMOTOR_PREP_REALS; i++) o[i] = T(0);
+    }
+    if (rates != nullptr) {
+        const V3<T> zero = { T(0), T(0), T(0) };
+        const V3<T> w1 = active && s1 >= 0 ? ldS(S, stride, C_AVEL, s1) : zero, w2 = active && s2 >= 0 ? ldS(S, stride, C_AVEL, s2) : zero;
+        const V3<T> dw = { w1.x - w2.x, w1.y - w2.y, w1.z - w2.z };
+        for (int i = 0; i < 3; i++) rates[3 * (size_t)k + i] = dot(a[i], dw);
+    }
+}
+
+template <class T>
+hipError_t launch_amotor_prepare(const T *S, int64_t stride, const AMotorIn *in, int nj, T k, T *prep, T *rates, hipStream_t st)
+{
+    if (nj <= 0) return hipSuccess;
+    hipLaunchKernelGGL((amotor_prepare<T>), dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, S, stride, in, nj, k, prep, rates);
+    return hipGetLastError();
+}
+template hipError_t launch_amotor_prepare<float>(const float *, int64_t, const AMotorIn *, int, float, float *, float *, hipStream_t);
+template hipError_t launch_amotor_prepare<double>(const double *, int64_t, const AMotorIn *, int, double, double *, double *, hipStream_t);
+
 // Feedback on the general path, behind the tick's solves on the tick's stream: one lane per entry of the contact arrays; the lane
 // of a joint's first entry sums the joint's entries (they are adjacent), puts the sides back as given and writes the joint's 12
 // reals.  Reads the row table and the tick's tables, writes F.fb; no atomics.  (The single-launch tick calls the same
@@ -243,14 +283,167 @@ extern "C" int dmxBatchFeedbackDevice(dmxBatchID b, const void **joints_dev, con
     return DMX_OK;
 }
 
+// ---- angular motors (include/dmx_batch.h at DMX_JOINT_AMOTOR) ----------------------------------------------------------------------
+// amotor_prepare's records, one per joint of the set, by the activity rules of the tick (dmx_joints.cpp)
+void dmx_amotor_records(const dmxBatch *b, dmx::AMotorIn *out)
+{
+    const int64_t n = b->n;
+    auto live = [&](int s) { return s < n && (b->h_bflags[(size_t)s] & dmx::BF_ALIVE) != 0; };
+    for (size_t k = 0; k < b->art.size(); k++) {
+        const dmxJoint &j = b->art[k];
+        dmx::AMotorIn &r = out[k];
+        const int s1 = j.body1, s2 = j.body2;
+        r.body1 = s1; r.body2 = s2; r.pad = 0;
+        r.active = j.kind == DMX_JOINT_AMOTOR && !b->amotor.empty() && !(s1 < 0 && s2 < 0) && s1 != s2 && (s1 < 0 || live(s1)) && (s2 < 0 || live(s2));
+        if (r.active) r.m = b->amotor[k];
+        else memset(&r.m, 0, sizeof(r.m));
+    }
+}
+
+static const char *amotor_flaw(const dmxAMotor &m)
+{
+    auto fin3 = [](const double *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); };
+    if (m.mode != DMX_AMOTOR_USER && m.mode != DMX_AMOTOR_EULER) return "mode is neither DMX_AMOTOR_USER nor DMX_AMOTOR_EULER";
+    if (m.num_axes < 1 || m.num_axes > 3) return "num_axes is outside 1..3";
+    if (m.mode == DMX_AMOTOR_EULER && m.num_axes != 3) return "Euler mode needs num_axes = 3";
+    for (int i = 0; i < 3; i++) {
+        if (m.rel[i] < 0 || m.rel[i] > 2) return "rel is outside 0..2";
+        if (!fin3(m.axis[i])) return "an axis is not finite";
+        if (std::isnan(m.lo_stop[i]) || std::isnan(m.hi_stop[i])) return "a stop is NaN";
+    }
+    if (!fin3(m.ref1) || !fin3(m.ref2)) return "a reference vector is not finite";
+    if (!fin3(m.angle)) return "an angle is not finite";
+    if (!fin3(m.vel) || !fin3(m.fmax)) return "vel or fmax is not finite";
+    return nullptr;
+}
+
+extern "C" int dmxBatchSetAMotors(dmxBatchID b, int64_t n, const dmxAMotor *motors)
+{
+    if (!b || n < 0 || (n > 0 && !motors)) return DMX_EINVAL;
+    if (n != 0 && n != (int64_t)b->art.size()) {
+        fprintf(stderr, "libode_mi355: dmxBatchSetAMotors: n = %lld, but the set holds %lld joints\n", (long long)n, (long long)b->art.size());
+        return DMX_EINVAL;
+    }
+    for (int64_t k = 0; k < n; k++) {
+        if (b->art[(size_t)k].kind != DMX_JOINT_AMOTOR) continue;        // (only an AMotor's entry is read)
+        if (const char *why = amotor_flaw(motors[k])) {
+            fprintf(stderr, "libode_mi355: dmxBatchSetAMotors: entry %lld: %s\n", (long long)k, why);
+            return DMX_EINVAL;
+        }
+    }
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    if (n == 0) b->amotor.clear();
+    else b->amotor.assign(motors, motors + n);
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchAMotorFromWorld(dmxBatchID b, int32_t body1, int32_t body2, int mode, int num_axes, const int32_t rel[3],
+                                       const double axes_w[3][3], dmxAMotor *out)
+{
+    if (!b || !out || !axes_w) return DMX_EINVAL;
+    if (body1 < -1 || body2 < -1 || body1 >= b->n || body2 >= b->n) return DMX_EINVAL;
+    if (mode != DMX_AMOTOR_USER && mode != DMX_AMOTOR_EULER) return DMX_EINVAL;
+    if (num_axes < 1 || num_axes > 3 || (mode == DMX_AMOTOR_EULER && num_axes != 3)) return DMX_EINVAL;
+    if (mode == DMX_AMOTOR_USER && !rel) return DMX_EINVAL;
+    dmxAMotor m;
+    memset(&m, 0, sizeof(m));
+    m.mode = mode; m.num_axes = num_axes;
+    double ax[3][3] = { { 0 } };
+    for (int i = 0; i < num_axes; i++) {
+        if (mode == DMX_AMOTOR_EULER && i == 1) continue;
+        if (mode == DMX_AMOTOR_USER) { if (rel[i] < 0 || rel[i] > 2) return DMX_EINVAL; m.rel[i] = rel[i]; }
+        const double *a = axes_w[i];
+        const double l = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        if (!(l > 0) || !std::isfinite(l)) return DMX_EINVAL;
+        for (int k = 0; k < 3; k++) ax[i][k] = a[k] / l;
+    }
+    if (mode == DMX_AMOTOR_EULER) {
+        const double d = ax[0][0] * ax[2][0] + ax[0][1] * ax[2][1] + ax[0][2] * ax[2][2];
+        if (std::fabs(d) > 1e-9) {
+            fprintf(stderr, "libode_mi355: dmxBatchAMotorFromWorld: Euler axes 0 and 2 are not perpendicular (a_0 . a_2 = %g)\n", d);
+            return DMX_EINVAL;
+        }
+        m.rel[0] = 1; m.rel[1] = 0; m.rel[2] = 2;
+    }
+    // R of the two sides at the current poses (a world side: the identity)
+    dmx::M3<double> R[2];
+    const int32_t body[2] = { body1, body2 };
+    for (int s = 0; s < 2; s++) {
+        for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) R[s].m[i][k] = i == k ? 1.0 : 0.0;
+        if (body[s] < 0) continue;
+        double st[13];
+        if (b->precision == DMX_F32) {
+            float f[13];
+            const int rc = dmxBatchDownload(b, DMX_STATE, f, body[s], 1);
+            if (rc != DMX_OK) return rc;
+            for (int k = 0; k < 13; k++) st[k] = f[k];
+        } else {
+            const int rc = dmxBatchDownload(b, DMX_STATE, st, body[s], 1);
+            if (rc != DMX_OK) return rc;
+        }
+        const dmx::Q4<double> q = { st[3], st[4], st[5], st[6] };
+        R[s] = dmx::quat_to_R(q);
+    }
+    auto to_frame = [&](int side, const double *w, double *o) {           // R^T w
+        const dmx::M3<double> &M = R[side];
+        for (int k = 0; k < 3; k++) o[k] = M.m[0][k] * w[0] + M.m[1][k] * w[1] + M.m[2][k] * w[2];
+    };
+    for (int i = 0; i < num_axes; i++) {
+        if (m.rel[i] == 0) for (int k = 0; k < 3; k++) m.axis[i][k] = ax[i][k];
+        else to_frame(m.rel[i] - 1, ax[i], m.axis[i]);
+    }
+    if (mode == DMX_AMOTOR_EULER) { to_frame(0, ax[2], m.ref1); to_frame(1, ax[0], m.ref2); }
+    for (int i = 0; i < 3; i++) { m.lo_stop[i] = -__builtin_huge_val(); m.hi_stop[i] = __builtin_huge_val(); }
+    *out = m;
+    return DMX_OK;
+}
+
+extern "C" int dmxBatchAMotorAngles(dmxBatchID b, double *angles3, double *rates3)
+{
+    if (!b) return DMX_EINVAL;
+    { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
+    const int64_t nj = (int64_t)b->art.size();
+    if (nj == 0) return DMX_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    { const int rc = dmx_ad_merge(b); if (rc != DMX_OK) return rc; }
+    int rc;
+    const size_t rs = b->rsize;
+    if ((rc = dmx_ensure_dev(b->amotor_in, (size_t)nj * sizeof(dmx::AMotorIn))) != DMX_OK) return rc;
+    if ((rc = dmx_ensure_dev(b->amotor_prep, (size_t)(dmx::AMOTOR_PREP_REALS + 3) * nj * rs)) != DMX_OK) return rc;
+    b->am_rec.resize((size_t)nj);
+    dmx_amotor_records(b, b->am_rec.data());
+    // (the records live in pageable host memory: a plain copy, which has read them when it returns)
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->amotor_in.p, b->am_rec.data(), (size_t)nj * sizeof(dmx::AMotorIn), hipMemcpyHostToDevice));
+    char *d_prep = (char *)b->amotor_prep.p, *d_rate = d_prep + (size_t)dmx::AMOTOR_PREP_REALS * nj * rs;
+    if (b->precision == DMX_F32)
+        HIP_TRY(dmx::launch_amotor_prepare<float>((const float *)b->slab, b->stride, (const dmx::AMotorIn *)b->amotor_in.p, (int)nj, 0.0f, (float *)d_prep, (float *)d_rate, b->stream));
+    else
+        HIP_TRY(dmx::launch_amotor_prepare<double>((const double *)b->slab, b->stride, (const dmx::AMotorIn *)b->amotor_in.p, (int)nj, 0.0, (double *)d_prep, (double *)d_rate, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    // (amotor_prep is the table a tick's prepare pass writes too: every tick with an AMotor row prepares it again in front of its
+    //  first kernel, on the same stream, so nothing read it between this call and then)
+    std::vector<char> &tmp = b->am_tmp;
+    tmp.resize((size_t)(dmx::AMOTOR_PREP_REALS + 3) * nj * rs);
+    HIP_TRY(hipMemcpy(tmp.data(), d_prep, tmp.size(), hipMemcpyDeviceToHost));
+    auto real_at = [&](size_t i) { return b->precision == DMX_F32 ? (double)((const float *)tmp.data())[i] : ((const double *)tmp.data())[i]; };
+    for (int64_t k = 0; k < nj; k++)
+        for (int i = 0; i < 3; i++) {
+            if (angles3) angles3[3 * k + i] = real_at((size_t)dmx::AMOTOR_PREP_REALS * k + dmx::AMOTOR_AXIS_REALS * i + dmx::AMP_THETA);
+            if (rates3) rates3[3 * k + i] = real_at((size_t)dmx::AMOTOR_PREP_REALS * nj + 3 * k + i);
+        }
+    return DMX_OK;
+}
+
 extern "C" int dmxBatchSetJoints(dmxBatchID b, int64_t n, const dmxJoint *joints)
 {
     if (!b || n < 0 || (n > 0 && !joints)) return DMX_EINVAL;
     for (int64_t k = 0; k < n; k++)
-        if (joints[k].kind < DMX_JOINT_BALL || joints[k].kind > DMX_JOINT_FIXED) return DMX_EINVAL;
+        if (joints[k].kind < DMX_JOINT_BALL || joints[k].kind > DMX_JOINT_AMOTOR) return DMX_EINVAL;
     { const int rc = dmx_settle(b); if (rc != DMX_OK) return rc; }
     b->art.assign(joints, joints + n);
     b->limot.clear();                    // (they were entries of the old set's joints)
+    b->amotor.clear();
     b->fb_valid = false;                 // (so was the last tick's feedback: fb_nj of them, not joint_count())
     return DMX_OK;
 }

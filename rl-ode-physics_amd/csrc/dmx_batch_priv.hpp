@@ -18,6 +18,7 @@
 #include "dmx_fixed.hpp"
 #include "dmx_autodisable.hpp"
 #include "dmx_damping.hpp"
+#include "dmx_amotor.hpp"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -35,8 +36,9 @@ using namespace dmx;
 // ... or a unit of an articulation joint (unit != 0: j is null, art = its index in the batch's set): at most three rows on the
 // same two bodies, carried beside the contacts -- a ball is one DMX_UNIT_BALL, a hinge a DMX_UNIT_BALL and a DMX_UNIT_HINGE2
 // and, when its limot is present (dmxBatchSetHingeLimots), a UNIT_LIMOT of one row; a slider a UNIT_LOCK, a UNIT_SLIDER2 and, when
-// present, a UNIT_SLIMOT; a fixed joint a UNIT_BALL and a UNIT_LOCK.  The two limot units are the only ones whose row can clamp
-struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; int unit = 0; int art = -1; };
+// present, a UNIT_SLIMOT; a fixed joint a UNIT_BALL and a UNIT_LOCK.  An angular motor is one UNIT_AMOTOR
+// of one row per axis whose limot is present (dmxBatchSetAMotors).  The two limot units and UNIT_AMOTOR are the only ones whose row can clamp
+struct DmxCanonicalJoint { int b1, b2; const dmxContactJoint *j; bool rev; int unit = 0; int art = -1; int axis = 0; };      // (axis: a UNIT_AMOTOR's)
 
 struct dmxBatch {
     int64_t n = 0, stride = 0;
@@ -215,6 +217,14 @@ struct dmxBatch {
     // the hinges' limits and motors (dmxBatchSetHingeLimots): empty, or one entry per joint of `art`
     std::vector<dmxHingeLimot> limot;
     DevBuf limot_dev;
+    // the angular motors (dmxBatchSetAMotors): empty, or one entry per joint of `art`; amotor_in / amotor_prep: the device staging of
+    // dmxBatchAMotorAngles' records and the table amotor_prepare writes (a tick's records travel with its own tables); am_rec: the
+    // host's scratch for the records
+    std::vector<dmxAMotor> amotor;
+    DevBuf amotor_in, amotor_prep;
+    std::vector<dmx::AMotorIn> am_rec;
+    std::vector<char> am_tmp;                          // dmxBatchAMotorAngles' download
+    std::vector<std::pair<int, int>> sc_am_links;      // the tick in the making: body pairs its active AMotors link (dmx_joints.cpp)
     // feedback (dmxBatchSetFeedback): fb_valid = the last tick was a dmxBatchStepJoints tick made with it on (every other writer of
     // body state clears it: dmx_state_stepped); 12 reals per result in the batch's precision, the set's joints first, then the
     // tick's contact joints: on the device at fb_devp -- fb_dev on the general path, behind a small tick's tables in its host-mapped
@@ -266,6 +276,10 @@ int dmx_ad_ensure(dmxBatch *b);
 // the DISABLED bits a tick enqueued earlier has set -> h_bflags (waits for that tick; nothing to do when none is pending)
 int dmx_ad_merge(dmxBatch *b);
 inline bool dmx_limot_present(const dmxHingeLimot &l) { return dmx::limot_present(l.lo_stop, l.hi_stop, l.fmax); }
+// amotor_prepare's records, one per joint of the set (dmx_artic.hip)
+void dmx_amotor_records(const dmxBatch *b, dmx::AMotorIn *out);
+// is axis i of an AMotor a row?  The hinge's rule, on the parameters alone
+inline bool dmx_amotor_present(const dmxAMotor &m, int i) { return i < m.num_axes && dmx::limot_present(m.lo_stop[i], m.hi_stop[i], m.fmax[i]); }
 // the ticks that build their own islands on the device do not know articulation joints: they say so instead of ignoring them
 inline bool dmx_refuse_joints(const dmxBatch *b, const char *what)
 {

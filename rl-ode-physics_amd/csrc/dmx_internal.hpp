@@ -125,6 +125,13 @@ template <class T> struct IslandSet {
     const int *row_level;  // level of every scheduled row, laid out like lev_rows (an island's rows start at its lev_off[0])
     const int *order;      // optional (dmxBatchSetRowOrder, DMX_ORDER_ODE): sweep `it` visits row order[(it / 8) * order_stride +
     int order_stride;      //   row_off[island] + i] at its i-th step; null: rows in creation order (solve_islands only)
+    // the angular motors' prepared table (amotor_prepare, dmx_artic.hip): AMOTOR_PREP_REALS reals per joint of the set -- per axis
+    // a_i and theta_i at the tick's start, in the sides as given, and the row's c, lo, hi (dmx_amotor.hpp) -- read by amotor_unit_row
+    // through the index staged in the entry's cmode; null unless the tick has an AMotor row.  In IslandSet and not in StepParams for
+    // the reason given below; HERE because the place decides how the island kernels' scalar registers spill: behind cext one
+    // single-launch kernel gains 16 bytes of scratch, at the end of the struct another gains 32 and the solve_singles kernels change
+    // registers; here no kernel gains scratch or LDS or loses a wave (profiles/amotor_kernel_resources.txt).
+    const T *amotor = nullptr;
     // damping, angular speed cap, contact correction (include/dmx_batch.h, "damping").  They ride here and not in StepParams:
     // StepParams is an argument of every fused kernel too (integrate_free, step_plane, step_contacts, ...), and a field appended
     // there moves the arguments behind it in all of them.  surface_layer / max_corr_vel act on every contact's normal row; at
@@ -165,8 +172,15 @@ template <class T> struct FeedbackSet {
 // (UNIT_LOCK: the three angular rows of a slider or a fixed joint; UNIT_SLIDER2: a slider's two linear rows; UNIT_SLIMOT: a slider's
 //  limit / motor row, which can clamp as a hinge's can.  Their markers are distinct numbers below the others: a unit's row count
 //  comes from its kind, unit_rows_of in dmx_island_rows.hpp and rpc_of in dmx_joints.cpp)
-constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2, UNIT_LIMOT = 3, UNIT_LOCK = 4, UNIT_SLIDER2 = 5, UNIT_SLIMOT = 6;
-constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0, UNIT_LIMOT_MU = -1.0, UNIT_LOCK_MU = -4.0, UNIT_SLIDER2_MU = -5.0, UNIT_SLIMOT_MU = -6.0;
+// (UNIT_AMOTOR: one axis of an angular motor, dmxBatchSetAMotors -- one row that can clamp, below UNIT_SLIMOT_MU)
+constexpr int UNIT_BALL = 1, UNIT_HINGE2 = 2, UNIT_LIMOT = 3, UNIT_LOCK = 4, UNIT_SLIDER2 = 5, UNIT_SLIMOT = 6, UNIT_AMOTOR = 7;
+constexpr double UNIT_BALL_MU = -3.0, UNIT_HINGE2_MU = -2.0, UNIT_LIMOT_MU = -1.0, UNIT_LOCK_MU = -4.0, UNIT_SLIDER2_MU = -5.0, UNIT_SLIMOT_MU = -6.0,
+                 UNIT_AMOTOR_MU = -7.0;
+// the angular motors' prepared table (IslandSet::amotor; written by amotor_prepare_joint, dmx_amotor.hpp, read by amotor_unit_row,
+// dmx_island_rows.hpp): per joint of the set, per axis i = 0, 1, 2, eight reals -- a_i (3), theta_i, then c, lo, hi of the axis's row
+// by the five-line table, and a spare -- axis i of joint j stands at AMOTOR_PREP_REALS j + AMOTOR_AXIS_REALS i
+enum : int { AMOTOR_AXIS_REALS = 8, AMOTOR_PREP_REALS = 3 * AMOTOR_AXIS_REALS };
+enum : int { AMP_AXIS = 0, AMP_THETA = 3, AMP_C = 4, AMP_LO = 5, AMP_HI = 6 };
 // Is a hinge's limot row there?  fmax > 0, or a finite stop.  Decided on the parameters alone -- the host sizes islands, schedules and LCP
 // scratch before the device has looked at the angle, so the row count must not depend on the state -- and in this one place: the
 // batch's tick (dmx_joints.cpp) and the ODE face (ode_compat.cpp: whether to hand the batch limots at all) must agree.

@@ -74,7 +74,7 @@ DMX_HD void stage_body(const T *S, const uint8_t *bflags, int64_t stride, const 
 //  marker says how many rows the unit has)
 template <class T> DMX_HD int unit_rows_of(T mu)
 {
-    return (mu == T(UNIT_HINGE2_MU) || mu == T(UNIT_SLIDER2_MU)) ? 2 : (mu == T(UNIT_LIMOT_MU) || mu == T(UNIT_SLIMOT_MU)) ? 1 : 3;
+    return (mu == T(UNIT_HINGE2_MU) || mu == T(UNIT_SLIDER2_MU)) ? 2 : (mu == T(UNIT_LIMOT_MU) || mu <= T(UNIT_SLIMOT_MU)) ? 1 : 3;      // (<=: UNIT_AMOTOR_MU too)
 }
 template <class T> __device__ __forceinline__ int contact_rpc(const IslandSet<T> &I, const StepParams<T> &P, int ci)
 {
@@ -328,12 +328,41 @@ DMX_HD void slider_position(bool has1, const V3<T> &x1, const Q4<T> &q1, const V
     if (has2) s_dot -= dot(u, v2) + dot(cross(a2, u), w2);
 }
 
-// the slider's two linear units, by marker (both at or below UNIT_SLIDER2_MU)
+// One axis of an angular motor (include/dmx_batch.h at DMX_JOINT_AMOTOR), one row.  Its geometry was made in front of the tick
+// (amotor_prepare, dmx_artic.hip: no rotation and no atan2 here -- these kernels have no registers for them): cmode >> 1 = where the
+// axis's prepared reals (dmx_amotor.hpp: a_i in the sides AS GIVEN, theta_i, then c, lo, hi) stand in I.amotor; cmode & 1: the sides
+// were exchanged.  c, lo, hi are limot_table's, worked out by the prepare pass with the k = ERP / h this kernel would use: called
+// from here the table cost five island kernels scratch (profiles/amotor_kernel_resources.txt).  (The entry's four surface slots are zero.)  In the sides as given J = [ 0, a_i | 0, -a_i ].
+template <class T>
+DMX_HD int amotor_unit_row(const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
+{
+    const int s1 = I.cb1[ci], s2 = I.cb2[ci];
+    const int cm = I.cmode[ci];
+    T *row = rows + (size_t)m * RW_COUNT;
+    jb[2 * m] = I.local[s1]; jb[2 * m + 1] = s2 >= 0 ? I.local[s2] : -1;
+    const T *prep = I.amotor + (size_t)(cm >> 1);
+    row[RW_LO] = prep[AMP_LO]; row[RW_HI] = prep[AMP_HI];
+    row[RW_RHS] = prep[AMP_C];          // c for now
+    row[RW_AD] = P.cfm;                 // cfm for now
+    row[RW_LAM] = T(0);
+    V3<T> u = ld3(prep + AMP_AXIS);
+    if (cm & 1) u = { -u.x, -u.y, -u.z };      // (this entry's body 1 is the given body 2)
+    T *J = row + RW_J;
+    J[0] = J[1] = J[2] = T(0);
+    st3(J + 3, u);
+    for (int j = 6; j < 12; j++) J[j] = T(0);
+    if (s2 >= 0) { J[9] = -u.x; J[10] = -u.y; J[11] = -u.z; }
+    return 1;
+}
+
+// the slider's two linear units and an angular motor's unit, by marker (all at or below UNIT_SLIDER2_MU: contact_rows and
+// joint_unit_rows send them here with the one comparison they always made)
 template <class T>
 DMX_HD int slider_linear_unit_rows(const T *S, int64_t stride, const IslandSet<T> &I, const StepParams<T> &P, T *rows, int *jb, int ci, int m, T hinv)
 {
     const T mu = I.cmu[ci];
     if (mu == T(UNIT_SLIDER2_MU)) return slider_unit_rows(S, stride, I, P, rows, jb, ci, m, hinv);
+    if (mu == T(UNIT_AMOTOR_MU)) return amotor_unit_row(I, P, rows, jb, ci, m, hinv);
     return slimot_unit_row(S, stride, I, P, rows, jb, ci, m, hinv);
 }
 

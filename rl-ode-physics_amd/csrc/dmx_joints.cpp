@@ -96,6 +96,11 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     }
     { const int rc_ad = dmx_ad_merge(b); if (rc_ad != DMX_OK) return rc_ad; }      // (the islands below are judged by the bytes the last tick left)
     int n_limots = 0;
+    // angular motors (dmxBatchSetAMotors): one unit of one row per axis whose limot is present; n_amotor_rows > 0 is what sends
+    // amotor_prepare in front of the tick.  An active AMotor between two bodies links them whether it has a row or not: am_links
+    std::vector<std::pair<int, int>> &am_links = b->sc_am_links;
+    am_links.clear();
+    int n_amotor_rows = 0;
     if (!b->art.empty()) {
         for (size_t a = 0; a < b->art.size(); a++) {
             const dmxJoint &j = b->art[a];
@@ -105,6 +110,13 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
             const bool rev = b1 < 0;
             if (rev) { b1 = b2; b2 = -1; }
             DmxCanonicalJoint u; u.b1 = b1; u.b2 = b2; u.j = nullptr; u.rev = rev; u.unit = UNIT_BALL; u.art = (int)a;
+            if (j.kind == DMX_JOINT_AMOTOR) {
+                if (b2 >= 0) am_links.push_back({ b1, b2 });
+                if (b->amotor.empty()) continue;
+                for (int i = 0; i < 3; i++)
+                    if (dmx_amotor_present(b->amotor[a], i)) { u.unit = UNIT_AMOTOR; u.axis = i; cj.push_back(u); n_limots++; n_amotor_rows++; }
+                continue;
+            }
             const bool limot = !b->limot.empty() && dmx_limot_present(b->limot[a]);
             if (j.kind == DMX_JOINT_SLIDER) {
                 // lock (3), linear (2), limot (1 if present): the limot's entry reads its anchors from the linear unit before it
@@ -124,7 +136,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     }
     int n_units = (int)cj.size();
     // rows of an entry, and how many of them can clamp (a limot unit's one row is counted as able to, whatever its state will be)
-    auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT; };
+    auto is_limot = [](int unit) { return unit == UNIT_LIMOT || unit == UNIT_SLIMOT || unit == UNIT_AMOTOR; };
     // the coefficient of friction row r (1 or 2) of a contact joint: mu_1 = max(mu, 0); mu_2 = max(surface.mu2, 0) where the caller
     // came with surfaces (dmxBatchStepJointsSurface) and the joint's mode has DMX_CONTACT_MU2, else mu_1 (include/dmx_batch.h).
     // Row count, island building and the rows that can never clamp depend on these two alone.
@@ -181,6 +193,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     if (b->ad_n_disabled > 0 && !include && !geo) {
         UnionFind uf(b->sc_parent);
         for (const CJ &c : cj) if (c.b2 >= 0) uf.unite(c.b1, c.b2);
+        for (const std::pair<int, int> &l : am_links) uf.unite(l.first, l.second);
         std::vector<uint8_t> &awake = b->sc_awake;
         awake.assign((size_t)n, 0);
         for (int s = 0; s < n; s++) if (live(s) && !(b->h_bflags[(size_t)s] & BF_DISABLED)) awake[(size_t)uf.find(s)] = 1;
@@ -199,11 +212,16 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
         if (!ad_dropped.empty()) {
             // their joints make no rows: the entries go before anything is counted, scheduled or staged (order kept: units first)
             size_t keep = 0;
-            n_units = 0; n_limots = 0; pyramid = false; extended = false;
+            n_units = 0; n_limots = 0; n_amotor_rows = 0; pyramid = false; extended = false;
+            {
+                size_t lk = 0;
+                for (const std::pair<int, int> &l : am_links) if (awake[(size_t)uf.find(l.first)]) am_links[lk++] = l;
+                am_links.resize(lk);
+            }
             for (size_t k = 0; k < cj.size(); k++) {
                 const CJ &c = cj[k];
                 if (!awake[(size_t)uf.find(c.b1)]) continue;
-                if (c.unit) { n_units++; if (c.unit == UNIT_LIMOT || c.unit == UNIT_SLIMOT) n_limots++; }
+                if (c.unit) { n_units++; if (is_limot(c.unit)) n_limots++; if (c.unit == UNIT_AMOTOR) n_amotor_rows++; }
                 else { if (pyramid_bits(*c.j)) pyramid = true; if (extended_bits(*c.j)) extended = true; }
                 cj[keep++] = c;
             }
@@ -265,6 +283,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // ---- islands ----------------------------------------------------------------------------------------
     UnionFind uf(b->sc_parent);
     for (const CJ &c : cj) if (c.b2 >= 0) uf.unite(c.b1, c.b2);
+    for (const std::pair<int, int> &l : am_links) uf.unite(l.first, l.second);
     std::vector<int> &island_of = b->sc_island;
     int ni = 0;
     for (int s : slots) {
@@ -488,9 +507,13 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
 
     // int staging: body_off[ni+1] bodies[nlive] con_off[ni+1] row_off[ni+1] cb1[nc] cb2[nc] cmode[nc] csrc[nc] crow[nc]
     //              big[ni] big_list[n_big] lev_count[n_big] lev_off[..] lev_rows[..]
-    const size_t n_int = (size_t)3 * (ni + 1) + (size_t)nlive + (size_t)5 * nc + (size_t)ni + (size_t)2 * n_big +
-                         lev_off_h.size() + 2 * lev_rows_h.size() +      // ... lev_rows[..] row_level[..]
-                         (fb ? (size_t)3 * nc : 0);                     // feedback: fb_out[nc] fb_info[nc] fb_isl[nc]
+    const size_t n_int_tables = (size_t)3 * (ni + 1) + (size_t)nlive + (size_t)5 * nc + (size_t)ni + (size_t)2 * n_big +
+                                lev_off_h.size() + 2 * lev_rows_h.size() +      // ... lev_rows[..] row_level[..]
+                                (fb ? (size_t)3 * nc : 0);                     // feedback: fb_out[nc] fb_info[nc] fb_isl[nc]
+    // a tick with an AMotor row: amotor_prepare's records behind them, one per joint of the set, at an even index (they hold doubles)
+    const size_t am_nj = n_amotor_rows > 0 ? b->art.size() : 0;
+    const size_t am_at = (n_int_tables + 1) & ~(size_t)1;
+    const size_t n_int = am_nj ? am_at + am_nj * (sizeof(AMotorIn) / sizeof(int)) : n_int_tables;
     // feedback: 12 reals per joint of the set and per contact joint given; a small tick keeps them behind its tables' reals
     const size_t n_fb = fb ? (size_t)12 * (b->art.size() + (size_t)nj_in) : 0;
     // real staging: cpos[3nc] cnormal[3nc] cdepth cmu cbounce cbounce_vel csoft_erp csoft_cfm [nc each]
@@ -527,6 +550,7 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     int *big = crow + nc, *big_list = big + ni, *lev_count = big_list + n_big, *lev_off = lev_count + n_big;
     int *lev_rows = lev_off + lev_off_h.size();
     int *fb_out = lev_rows + 2 * lev_rows_h.size(), *fb_info = fb_out + nc, *fb_isl = fb_info + nc;      // (feedback on only)
+    if (am_nj) dmx_amotor_records(b, (AMotorIn *)(hi + am_at));
     if (nc) memcpy(crow, crow_h.data(), (size_t)nc * sizeof(int));
     if (ni) memcpy(big, big_h.data(), (size_t)ni * sizeof(int));
     if (n_big) { memcpy(big_list, big_list_h.data(), (size_t)n_big * sizeof(int)); memcpy(lev_count, lev_count_h.data(), (size_t)n_big * sizeof(int)); }
@@ -589,6 +613,16 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
                         for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = (T)a.axis1[k]; cnormal[3 * (size_t)d + k] = T(0); }
                         cdepth[d] = T(0); cmu[d] = (T)UNIT_SLIMOT_MU;
                         cbounce[d] = (T)l.lo_stop; cbv[d] = (T)l.hi_stop; cserp[d] = (T)l.vel; cscfm[d] = (T)l.fmax;
+                        continue;
+                    }
+                    if (c.unit == UNIT_AMOTOR) {
+                        // one axis of an angular motor: where its prepared reals stand in IslandSet::amotor and whether the sides
+                        // were exchanged, both in cmode; nothing else is read (the stops and the motor went into the prepare pass)
+                        cb1[d] = c.b1; cb2[d] = c.b2; csrc[d] = 0;
+                        cmode[d] = ((AMOTOR_PREP_REALS * c.art + AMOTOR_AXIS_REALS * c.axis) << 1) | (c.rev ? 1 : 0);
+                        for (int k = 0; k < 3; k++) { cpos[3 * (size_t)d + k] = T(0); cnormal[3 * (size_t)d + k] = T(0); }
+                        cdepth[d] = T(0); cmu[d] = (T)UNIT_AMOTOR_MU;
+                        cbounce[d] = T(0); cbv[d] = T(0); cserp[d] = T(0); cscfm[d] = T(0);
                         continue;
                     }
                     if (c.unit == UNIT_LOCK) {
@@ -759,6 +793,15 @@ template <class T> int step_joints_t(dmxBatch *b, double h, int64_t nj_in, const
     // first kernel -- the single-launch tick's one launch included, whose body list it reads where that launch reads it -- only
     // while some slot's scale is not zero.  (A tick of a subset comes from a caller that has refused any of this.)
     I.surface_layer = (T)b->surface_layer; I.max_corr_vel = (T)b->max_corr_vel;
+    if (am_nj) {
+        // the angular motors' axes and angles from the state at the tick's start: a dispatch of its own in front of the tick's first
+        // kernel -- of the single-launch tick's one launch too, whose staging it reads its records from, as the damping pass does
+        if ((rc = dmx_ensure_dev(b->amotor_prep, (size_t)(AMOTOR_PREP_REALS + 3) * am_nj * sizeof(T))) != DMX_OK) return rc;
+        I.amotor = (const T *)b->amotor_prep.p;
+        // (k as the island kernels form it: hinv * erp with hinv = 1 / h, in the batch's precision)
+        HIP_TRY(launch_amotor_prepare<T>((const T *)b->slab, b->stride, (const AMotorIn *)(di + am_at), (int)am_nj, (T(1) / P.h) * P.erp,
+                                         (T *)b->amotor_prep.p, (T *)nullptr, b->stream));
+    }
     if (!include && !geo) {
         if (b->damp_n_capped > 0) I.damping = (const T *)b->damp_dev;
         if (b->damp_n_scaled > 0) HIP_TRY(launch_damping<T>((T *)b->slab, b->bflags, (const T *)b->damp_dev, I.bodies, nlive, n, b->stream));

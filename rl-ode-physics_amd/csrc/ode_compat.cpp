@@ -20,6 +20,7 @@
 #include "dmx_ray.hpp"
 #include "dmx_math.hpp"
 #include "dmx_island_rows.hpp"      // hinge_angle: the function the device builds the limit / motor row with
+#include "dmx_amotor.hpp"           // amotor_axes: the function the device prepares an angular motor's axes and angles with
 
 using dmx::M3;
 using dmx::Q4;
@@ -101,6 +102,11 @@ struct dxJoint {
     double lo_stop = -__builtin_huge_val(), hi_stop = __builtin_huge_val(), vel = 0, fmax = 0;
     double qrel0[4] = { 1, 0, 0, 0 };
     dJointFeedback *fb = nullptr;      // dJointSetFeedback: the caller's struct, filled by every step while it is set
+    // an angular motor (dJointCreateAMotor): its dmxAMotor in the sides AS ATTACHED -- rel 1 / 2 name the bodies the caller attached
+    // first / second, also after dJointAttach(j, 0, body) -- with num_axes as the caller set it (0 .. 3: the batch is handed a blank
+    // entry for 0); am_set: bit i = axis i has been given
+    dmxAMotor am = {};
+    int am_set = 0;
 };
 
 struct dxJointGroup {
@@ -116,6 +122,8 @@ struct dxWorld {
     bool art_dirty = false;            // ... and changed since the batch last saw them
     bool limot_dirty = false;          // a hinge's limit / motor parameter or zero pose changed since the batch last saw them
     bool limots_sent = false;          // the batch holds limots (dmxBatchSetHingeLimots)
+    bool amotor_dirty = false;         // an angular motor's mode, axes, angles or parameters changed since the batch last saw them
+    std::vector<dmxAMotor> am;
     int n_feedback = 0;                // joints of the world with a feedback struct set (dJointSetFeedback)
     bool feedback_sent = false;        // the batch's feedback is switched on (dmxBatchSetFeedback): only while n_feedback > 0
     std::vector<dmxJointFeedback> fbuf;
@@ -426,7 +434,7 @@ static int world_step(dWorldID w, dReal h, int stepper)
             memset(&a, 0, sizeof a);
             // (the batch's enum does not take ODE's numbering: kind 7 stays refused there)
             a.kind = j->type == dJointTypeHinge ? DMX_JOINT_HINGE : j->type == dJointTypeSlider ? DMX_JOINT_SLIDER :
-                     j->type == dJointTypeFixed ? DMX_JOINT_FIXED : DMX_JOINT_BALL;
+                     j->type == dJointTypeFixed ? DMX_JOINT_FIXED : j->type == dJointTypeAMotor ? DMX_JOINT_AMOTOR : DMX_JOINT_BALL;
             a.body1 = j->b1 ? j->b1->slot : -1;
             a.body2 = j->b2 ? j->b2->slot : -1;
             for (int k = 0; k < 3; k++) { a.anchor1[k] = j->anchor1[k]; a.anchor2[k] = j->anchor2[k]; a.axis1[k] = j->axis1[k]; a.axis2[k] = j->axis2[k]; }
@@ -442,6 +450,23 @@ static int world_step(dWorldID w, dReal h, int stepper)
         w->art_dirty = false;
         w->limots_sent = false;        // (dmxBatchSetJoints drops them)
         w->limot_dirty = true;
+        w->amotor_dirty = true;        // (... and the angular motors' table)
+    }
+    if (w->amotor_dirty) {             // the angular motors' table, when the joints or one of its values changed; none: nothing is sent
+        w->am.clear();
+        bool any = false;
+        for (const dxJoint *j : w->arts) {
+            dmxAMotor m = j->am;
+            if (j->type != dJointTypeAMotor || m.num_axes < 1) {
+                memset(&m, 0, sizeof m);
+                m.num_axes = 1;
+                for (int i = 0; i < 3; i++) { m.lo_stop[i] = -__builtin_huge_val(); m.hi_stop[i] = __builtin_huge_val(); }
+            }
+            any = any || j->type == dJointTypeAMotor;
+            w->am.push_back(m);
+        }
+        if (any) DMX_MUST(dmxBatchSetAMotors(w->batch, (int64_t)w->am.size(), w->am.data()));
+        w->amotor_dirty = false;
     }
     if (w->limot_dirty) {              // ... and the hinges' limits and motors when the joints or a parameter changed
         w->al.clear();
@@ -1376,6 +1401,187 @@ extern "C" int dAreConnectedExcluding(dBodyID b1, dBodyID b2, int joint_type)
             if (j->type != joint_type && ((j->b1 == b1 && j->b2 == b2) || (j->b1 == b2 && j->b2 == b1))) return 1;
     return 0;
 }
+// ---- angular motors (include/dmx_batch.h, DMX_JOINT_AMOTOR).  Axes, angles, rates, stops, motors and dJointAddAMotorTorques are those
+// of the sides as attached, as a hinge's angle is: rel 1 / 2 name the body attached first / second, also after dJointAttach(j, 0, body).
+namespace {
+
+inline bool is_amotor(const dxJoint *j) { return j && j->type == dJointTypeAMotor; }
+void amotor_touch(dJointID j) { if (j->world) j->world->amotor_dirty = true; }
+// the body of the side `rel` names (1 / 2, the sides as attached; 0 or a world side: none)
+const dxBody *amotor_side(const dxJoint *j, int rel)
+{
+    const dxBody *g1 = j->rev ? nullptr : j->b1, *g2 = j->rev ? j->b1 : j->b2;
+    return rel == 1 ? g1 : rel == 2 ? g2 : nullptr;
+}
+// axes and angles of the sides as attached from the host mirrors, through the function the device uses
+void amotor_now(const dxJoint *j, dmx::V3<double> a[3], double th[3])
+{
+    const dxBody *g1, *g2;
+    dmx::Q4<double> q1, q2;
+    given_sides(j, g1, g2, q1, q2);
+    dmxAMotor m = j->am;
+    if (m.num_axes < 1) m.num_axes = 1;
+    dmx::amotor_axes<double>(g1 != nullptr, q1, g2 != nullptr, q2, m, a, th);
+    if (j->am.num_axes < 1) { a[0] = { 0, 0, 0 }; th[0] = 0; }
+}
+// Euler mode: axis 0 goes with side 1 and axis 2 with side 2 whatever rel the caller gave, and "this pose is angles zero" -- the
+// reference vectors -- is taken whenever axis 0 or 2 is set while both are known [ODE-recall amotorSetEulerReferenceVectors]
+void amotor_euler_refs(dJointID j)
+{
+    dmxAMotor &m = j->am;
+    if (m.mode != DMX_AMOTOR_EULER) return;
+    m.num_axes = 3;
+    dReal w0[4] = { 0, 0, 0, 0 }, w2[4] = { 0, 0, 0, 0 };
+    to_world(amotor_side(j, m.rel[0]), m.axis[0], false, w0);
+    to_world(amotor_side(j, m.rel[2]), m.axis[2], false, w2);
+    const double a0[3] = { (double)w0[0], (double)w0[1], (double)w0[2] }, a2[3] = { (double)w2[0], (double)w2[1], (double)w2[2] };
+    m.rel[0] = 1; m.rel[1] = 0; m.rel[2] = 2;
+    to_body(amotor_side(j, 1), a0, false, m.axis[0]);
+    to_body(amotor_side(j, 2), a2, false, m.axis[2]);
+    if ((j->am_set & 5) == 5) {
+        to_body(amotor_side(j, 1), a2, false, m.ref1);
+        to_body(amotor_side(j, 2), a0, false, m.ref2);
+    }
+}
+
+}  // namespace
+
+extern "C" dJointID dJointCreateAMotor(dWorldID w, dJointGroupID g)
+{
+    dJointID j = create_art(w, g, dJointTypeAMotor);
+    if (!j) return j;
+    j->am.mode = DMX_AMOTOR_USER;
+    for (int i = 0; i < 3; i++) { j->am.lo_stop[i] = -__builtin_huge_val(); j->am.hi_stop[i] = __builtin_huge_val(); }
+    amotor_touch(j);
+    return j;
+}
+extern "C" void dJointSetAMotorMode(dJointID j, int mode)
+{
+    if (!is_amotor(j) || (mode != dAMotorUser && mode != dAMotorEuler)) return;
+    if (j->world) j->world->to_host();
+    j->am.mode = mode == dAMotorEuler ? DMX_AMOTOR_EULER : DMX_AMOTOR_USER;
+    amotor_euler_refs(j);
+    amotor_touch(j);
+}
+extern "C" int dJointGetAMotorMode(dJointID j) { return is_amotor(j) && j->am.mode == DMX_AMOTOR_EULER ? dAMotorEuler : dAMotorUser; }
+extern "C" void dJointSetAMotorNumAxes(dJointID j, int num)
+{
+    if (!is_amotor(j)) return;
+    j->am.num_axes = j->am.mode == DMX_AMOTOR_EULER ? 3 : num < 0 ? 0 : num > 3 ? 3 : num;
+    amotor_touch(j);
+}
+extern "C" int dJointGetAMotorNumAxes(dJointID j) { return is_amotor(j) ? j->am.num_axes : 0; }
+extern "C" void dJointSetAMotorAxis(dJointID j, int anum, int rel, dReal x, dReal y, dReal z)
+{
+    if (!is_amotor(j) || anum < 0 || anum > 2 || rel < 0 || rel > 2) return;
+    const double l = sqrt((double)x * x + (double)y * y + (double)z * z);
+    if (!(l > 0) || !(l < __builtin_huge_val())) return;
+    if (j->world) j->world->to_host();
+    const double a[3] = { x / l, y / l, z / l };
+    j->am.rel[anum] = rel;
+    to_body(amotor_side(j, rel), a, false, j->am.axis[anum]);
+    j->am_set |= 1 << anum;
+    amotor_euler_refs(j);
+    amotor_touch(j);
+}
+extern "C" void dJointGetAMotorAxis(dJointID j, int anum, dVector3 r)
+{
+    if (!is_amotor(j) || anum < 0 || anum > 2) return;
+    if (j->world) j->world->to_host();
+    if (j->am.mode == DMX_AMOTOR_EULER) {
+        dmx::V3<double> a[3];
+        double th[3];
+        amotor_now(j, a, th);
+        r[0] = (dReal)a[anum].x; r[1] = (dReal)a[anum].y; r[2] = (dReal)a[anum].z;
+        return;
+    }
+    to_world(amotor_side(j, j->am.rel[anum]), j->am.axis[anum], false, r);
+}
+extern "C" int dJointGetAMotorAxisRel(dJointID j, int anum) { return is_amotor(j) && anum >= 0 && anum <= 2 ? j->am.rel[anum] : 0; }
+extern "C" void dJointSetAMotorAngle(dJointID j, int anum, dReal angle)
+{
+    if (!is_amotor(j) || anum < 0 || anum > 2) return;
+    const double v = (double)angle;
+    if (!(v > -__builtin_huge_val() && v < __builtin_huge_val())) { fprintf(stderr, "libode_mi355: dJointSetAMotorAngle: an angle that is not finite; ignored\n"); return; }
+    if (j->am.mode != DMX_AMOTOR_USER) return;       // (Euler mode computes its angles)
+    j->am.angle[anum] = v;
+    amotor_touch(j);
+}
+extern "C" dReal dJointGetAMotorAngle(dJointID j, int anum)
+{
+    if (!is_amotor(j) || anum < 0 || anum > 2) return 0;
+    if (j->am.mode == DMX_AMOTOR_USER) return (dReal)j->am.angle[anum];
+    if (j->world) j->world->to_host();
+    dmx::V3<double> a[3];
+    double th[3];
+    amotor_now(j, a, th);
+    return (dReal)th[anum];
+}
+// a_i . (omega_1 - omega_2) of the sides as attached: the velocity axis i's row acts on (include/dmx_batch.h, "rate")
+extern "C" dReal dJointGetAMotorAngleRate(dJointID j, int anum)
+{
+    if (!is_amotor(j) || anum < 0 || anum > 2 || anum >= j->am.num_axes) return 0;
+    if (j->world) j->world->to_host();
+    dmx::V3<double> a[3];
+    double th[3];
+    amotor_now(j, a, th);
+    const dxBody *g1 = amotor_side(j, 1), *g2 = amotor_side(j, 2);
+    double d[3];
+    for (int k = 0; k < 3; k++) d[k] = (g1 ? (double)g1->avel[k] : 0.0) - (g2 ? (double)g2->avel[k] : 0.0);
+    return (dReal)(a[anum].x * d[0] + a[anum].y * d[1] + a[anum].z * d[2]);
+}
+// dParamLoStop / HiStop / Vel / FMax and their ...2 / ...3 groups are honoured (fudge factor 1, no bounce, the world's ERP / CFM at the
+// stops); the other parameters say so once each call and are ignored
+extern "C" void dJointSetAMotorParam(dJointID j, int parameter, dReal value)
+{
+    if (!is_amotor(j)) return;
+    const int i = parameter / dParamGroup, base = parameter % dParamGroup;
+    const double v = (double)value;
+    const bool finite = v > -__builtin_huge_val() && v < __builtin_huge_val();
+    if (parameter < 0 || i > 2) { fprintf(stderr, "libode_mi355: dJointSetAMotorParam: parameter %d is not supported; ignored\n", parameter); return; }
+    switch (base) {
+    case dParamLoStop: case dParamHiStop:
+        if (v != v) { fprintf(stderr, "libode_mi355: dJointSetAMotorParam: a stop that is not a number; ignored\n"); return; }
+        (base == dParamLoStop ? j->am.lo_stop : j->am.hi_stop)[i] = v;
+        break;
+    case dParamVel: case dParamFMax:
+        if (!finite) { fprintf(stderr, "libode_mi355: dJointSetAMotorParam: dParamVel / dParamFMax must be finite; ignored\n"); return; }
+        (base == dParamVel ? j->am.vel : j->am.fmax)[i] = v;
+        break;
+    default:
+        fprintf(stderr, "libode_mi355: dJointSetAMotorParam: parameter %d is not supported (dParamLoStop, HiStop, Vel, FMax and their groups are); ignored\n", parameter);
+        return;
+    }
+    amotor_touch(j);
+}
+extern "C" dReal dJointGetAMotorParam(dJointID j, int parameter)
+{
+    if (!is_amotor(j) || parameter < 0 || parameter / dParamGroup > 2) return 0;
+    const int i = parameter / dParamGroup;
+    switch (parameter % dParamGroup) {
+    case dParamLoStop: return (dReal)j->am.lo_stop[i];
+    case dParamHiStop: return (dReal)j->am.hi_stop[i];
+    case dParamVel: return (dReal)j->am.vel[i];
+    case dParamFMax: return (dReal)j->am.fmax[i];
+    default: return 0;
+    }
+}
+// +sum t_i a_i on body 1 and the opposite on body 2 (the sides as attached), through the bodies' torque accumulators
+extern "C" void dJointAddAMotorTorques(dJointID j, dReal torque1, dReal torque2, dReal torque3)
+{
+    if (!is_amotor(j) || !j->b1) return;
+    if (j->world) j->world->to_host();
+    dmx::V3<double> a[3];
+    double th[3];
+    amotor_now(j, a, th);
+    const double t[3] = { (double)torque1, (double)torque2, (double)torque3 };
+    double s[3] = { 0, 0, 0 };
+    for (int i = 0; i < j->am.num_axes && i < 3; i++) { s[0] += t[i] * a[i].x; s[1] += t[i] * a[i].y; s[2] += t[i] * a[i].z; }
+    const dxBody *g1 = amotor_side(j, 1), *g2 = amotor_side(j, 2);
+    if (g1) dBodyAddTorque(const_cast<dxBody *>(g1), (dReal)s[0], (dReal)s[1], (dReal)s[2]);
+    if (g2) dBodyAddTorque(const_cast<dxBody *>(g2), (dReal)-s[0], (dReal)-s[1], (dReal)-s[2]);
+}
+
 extern "C" int dAreConnected(dBodyID b1, dBodyID b2) { return dAreConnectedExcluding(b1, b2, dJointTypeNone); }
 
 // ================================================================================ rotation helpers
